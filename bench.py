@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Cellulus hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train2d|train3d]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train2d|train3d] [--dump-outputs DIR] [--full]
 
 A "step" is one `train_iteration` (U-Net forward, fused gather + OCE loss,
 backward, [RCCL all-reduce SUM], Adam) on one batch of synthetic crops per GPU,
@@ -9,12 +9,20 @@ at BASELINE.json configs[1]: 2-D 1x256x256 crops, num_fmaps=256,
 fmap_inc_factor=3, downsampling [[2,2]], batch 8 per GPU.  Inputs are resident
 in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the line (`value` in crops/s,
+`ms_per_step` of one timed step); nothing else.  The last timed step starts again from the seeded weights
+(parameters and Adam's state are put back just before it: `SeededState`), so what it computes is the same from run to
+run up to rounding.  `--dump-outputs DIR` then writes what that step returned on rank 0 (float64 `loss.npy`,
+`oce_loss.npy`; float32 `offsets.npy`): two builds can be compared output for output.
+Everything below — the profiled passes, the other precision and workload, inference, the real train(), the
+baselines and the data-parallel checks — runs only with `--full` (the `--no-*` options trim a `--full` run).
+
 `--gpus N` with N > 1: either the caller starts the ranks (`python -m
 torch.distributed.run --nproc-per-node N bench.py --gpus N ...`, WORLD_SIZE set) or —
 plain `python bench.py --gpus N` — this process starts N children itself, one per GPU,
 BEFORE anything touches the GPU, waits for them and relays rank 0's JSON line.
 
-Extra objects on that line:
+Extra objects on the `--full` line:
   roofline     — the dominant kernel (f32 MFMA implicit-GEMM convolution):
                  FLOPs its launches execute / their HIP-event durations,
                  against the 157.3 TFLOP/s f32 MFMA peak.
@@ -89,6 +97,64 @@ def release_device_memory():
 
     gc.collect()
     torch.cuda.empty_cache()
+
+
+DUMP_LIMIT_BYTES = 63 * 2 ** 20      # the .npy headers stay inside 64 MB
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes ``arrays`` (name -> float32 / float64 numpy array) as ``out_dir/<name>.npy``.  Should they hold more than
+    ``limit`` bytes in all, each is cut to its share by a fixed, seeded sample of its flattened elements (the same
+    indices on every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    share = limit - 8 * len(arrays)          # every array keeps at least one element (at most 8 bytes)
+    for name, a in arrays.items():
+        keep = a.size if total <= limit else max(1, a.size * share // total)
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+class SeededState:
+    """The state a model and its Adam optimizer start from (before their first step): ``restore()`` puts the parameters
+    back (one device copy) and Adam's moments and step counters to zero, so that the next step is the first train step
+    from the seeded weights again.  The steps before it drift apart from run to run: the weight-gradient split-K, the
+    bias gradients and the pair-gradient scatter add with float atomics in a run-dependent order, and Adam carries those
+    roundings from step to step far beyond rounding.  A restore costs one repack of the weights (the step
+    packs the next step's weights right behind Adam), so a run restores once, before its last timed step, inside the
+    timed region: a parameter copy, two fills of Adam's moments and that repack, about 0.4 ms at the benchmark
+    configuration (measured as the difference of runs restoring before every step and never), i.e. 0.4 / K ms on
+    `ms_per_step` — work the headline step itself does not do."""
+
+    def __init__(self, model, optimizer):
+        self.model, self.optimizer = model, optimizer
+        self.flat0 = model._flat.detach().clone()
+        self.states = self.moments = None
+
+    def restore(self):
+        import torch
+
+        if not self.optimizer.state:              # no step taken yet: the parameters are still the seeded ones
+            return
+        if self.moments is None:                  # Adam's state appears with its first step: flat moment buffers
+            self.states = list(self.optimizer.state.values())
+            bases = {}
+            for st in self.states:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    t = st[key] if st[key]._base is None else st[key]._base
+                    bases[t.data_ptr()] = t
+            self.moments = list(bases.values())
+        with torch.no_grad():
+            self.model._flat.copy_(self.flat0)
+            for t in self.moments:
+                t.zero_()
+        self.model.mark_weights_changed()         # the packed weights are redone from the restored parameters
+        for st in self.states:
+            st["step"].zero_()
+
 
 def self_launch(n, argv):
     """Start one child per GPU, wait, relay rank 0's stdout.  Children are FRESH processes
@@ -305,9 +371,11 @@ def build_step_inputs(wl_key, rank, device, broadcast=True):
 # ------------------------------------------------------------------------------------------------
 # the timed workload
 # ------------------------------------------------------------------------------------------------
-def run_workload(wl_key, args, rank, world, device):
+def run_workload(wl_key, args, rank, world, device, dump_dir=None):
     """W warm-up steps, then exactly K timed steps between barrier + synchronize; returns the
-    metrics dict on rank 0 (None elsewhere).  Every rank calls this (collectives inside)."""
+    metrics dict on rank 0 (None elsewhere).  Every rank calls this (collectives inside).
+    ``dump_dir``: rank 0 writes what the last timed step returned there (``dump_outputs``).  Without
+    ``args.full`` the timed steps run unprofiled and nothing follows them but the timing."""
     import ctypes
     import gc
 
@@ -322,6 +390,7 @@ def run_workload(wl_key, args, rank, world, device):
     B = wl["batch"]
     torch.cuda.reset_peak_memory_stats(device)
     first_losses = []
+    seeded = SeededState(model, optimizer)
 
     def barrier():
         if world > 1:
@@ -329,7 +398,7 @@ def run_workload(wl_key, args, rank, world, device):
         torch.cuda.synchronize()
 
     timer = ConvTimer()
-    detail = bool(os.environ.get("CLX_BENCH_DETAIL"))
+    detail = args.full and bool(os.environ.get("CLX_BENCH_DETAIL"))
     if detail:
         os.environ["CLX_STREAMS"] = "1"      # the per-layer table times calls one after the other: one stream
         timer.install()      # installed before the warm-up so lazy HIP-event setup is not timed
@@ -339,18 +408,53 @@ def run_workload(wl_key, args, rank, world, device):
     timer.records.clear()
     gc.collect()
     gc.disable()     # a cyclic-GC pause inside one step would be charged to the GPU path
-    _clx.call("clx_profile_enable", 2)      # HIP events around every MFMA kernel launch, on its stream
-    _lib0 = _clx.load()
-    _lib0.clx_profile_clock(None, None, 1)
+    if args.full:
+        _clx.call("clx_profile_enable", 2)      # HIP events around every MFMA kernel launch, on its stream
+        _lib0 = _clx.load()
+        _lib0.clx_profile_clock(None, None, 1)
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss, oce, _ = train_iteration(batch, model, criterion, optimizer, device)
+    for i in range(args.steps):
+        if i == args.steps - 1:
+            seeded.restore()         # the last timed step starts from the seeded state: the same outputs on every run
+        loss, oce, offsets = train_iteration(batch, model, criterion, optimizer, device)
         first_losses.append(loss)
     barrier()
     dt_local = time.perf_counter() - t0
     gc.enable()
     timer.uninstall()
+    if dump_dir and rank == 0:
+        import numpy as np
+
+        dump_outputs(dump_dir, dict(loss=np.array(loss, dtype=np.float64), oce_loss=np.array(oce, dtype=np.float64),
+                                    offsets=offsets.detach().float().cpu().numpy()))
+
+    def config(streams):
+        _fwd, flops, _ = conv_flops(next(iter(model._plans.values())).topo, 1)
+        return {"workload": wl["name"], "global_batch": world * B, "parallelism": f"dp{world}",
+                "gflop_per_crop_train": round(flops / 1e9, 1), "streams_per_gpu": streams}
+
+    if not args.full:
+        # the headline only: the slowest rank's time, its crops/s, the losses
+        dt, per_rank = dt_local, [dt_local]
+        if world > 1:
+            t = torch.tensor([dt_local], dtype=torch.float64, device=device)
+            gathered = [torch.zeros_like(t) for _ in range(world)]
+            torch.distributed.all_gather(gathered, t)
+            per_rank = [g.item() for g in gathered]
+            dt = max(per_rank)
+        if rank != 0:
+            return None
+        from cellulus_amd.models.plan import DualPlan
+
+        out = {"value": round(world * B * args.steps / dt, 3), "unit": "crops/s",
+               "ms_per_step": round(dt / args.steps * 1e3, 3),
+               "config": config(2 if isinstance(next(iter(model._plans.values())), DualPlan) else 1),
+               "loss": round(float(loss), 4)}
+        if world > 1:
+            out["per_rank_ms_per_step"] = [round(t / args.steps * 1e3, 3) for t in per_rank]
+        out["losses_from_first_step"] = [float(x) for x in first_losses]
+        return out
 
     lib = _clx.load()
     kinds = {0: "conv_igemm_kernel<128,128,2,2>", 1: "conv_igemm_kernel<128,64,4,1>", 2: "conv_wgrad_kernel",
@@ -531,9 +635,7 @@ def run_workload(wl_key, args, rank, world, device):
         "value": round(crops_per_s, 3),
         "unit": "crops/s",
         "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "config": {"workload": wl["name"], "global_batch": world * B,
-                   "parallelism": f"dp{world}", "gflop_per_crop_train": round(train_flops / 1e9, 1),
-                   "streams_per_gpu": 2 if overlapped is not None else 1},
+        "config": config(2 if overlapped is not None else 1),
         "loss": round(float(loss), 4),
         "roofline": roofline,
     }
@@ -840,10 +942,15 @@ def main():
                          "the PMC profiles are taken from")
     ap.add_argument("--precision", default="both", choices=["f32", "f32x3bf16", "both"],
                     help="both (default): the line in the product's default arithmetic (f32x3bf16: the plain products on the "
-                         "bf16 matrix cores from an exact three-way split of the float32 operands, csrc/gemm_sp.hip), then the "
-                         "2-D workload and the inference tile AGAIN with CLX_PRECISION=f32 (float32 MFMA everywhere, the "
+                         "bf16 matrix cores from an exact three-way split of the float32 operands, csrc/gemm_sp.hip); with --full "
+                         "the 2-D workload and the inference tile AGAIN with CLX_PRECISION=f32 (float32 MFMA everywhere, the "
                          "arithmetic of rounds 1-5) as the objects `train2d_f32_mfma` / `infer_f32_mfma`; f32 / f32x3bf16: "
                          "the whole line in that precision only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: rooflines and the one-stream pass, the f32 leg, train3d, infer, "
+                         "the real train(), the CPU and GPU-library baselines, the data-parallel checks")
     args = ap.parse_args()
     if args.streams:
         os.environ["CLX_STREAMS"] = str(args.streams)
@@ -868,9 +975,9 @@ def main():
     from cellulus_amd.models.plan import precision_name
 
     line_precision = precision_name()
-    res = run_workload(args.workload, args, rank, world, device)
+    res = run_workload(args.workload, args, rank, world, device, dump_dir=args.dump_outputs)
     res_f32 = infer_f32 = None
-    if args.precision == "both" and line_precision != "f32" and args.workload == "train2d":
+    if args.full and args.precision == "both" and line_precision != "f32" and args.workload == "train2d":
         keep_env = os.environ.get("CLX_PRECISION")
         os.environ["CLX_PRECISION"] = "f32"
         release_device_memory()
@@ -887,12 +994,12 @@ def main():
             else:
                 os.environ["CLX_PRECISION"] = keep_env
     res3d = None
-    if args.workload == "train2d" and not args.no_train3d:
+    if args.full and args.workload == "train2d" and not args.no_train3d:
         release_device_memory()
         res3d = run_workload("train3d", args, rank, world, device)
     # ---- the other half of the metric and the real train(), on every rank when there are several
     infer_obj = e2e_obj = None
-    if world > 1:
+    if world > 1 and args.full:
         # (no try/except here: a rank that fails must EXIT, so that the launcher ends the ranks waiting in a barrier)
         if not args.no_infer:
             release_device_memory()
@@ -931,7 +1038,7 @@ def main():
                              "float32 product, float32 accumulation (roofline peak of those kernels: 2516.6 / 6 = 419.4 TFLOP/s "
                              "f32-equivalent); |HIP - float64 oracle| at a trained network's output scale 7.2e-5, the float32 "
                              "MFMA kernels' 7.3e-5 (profiles/r06_parity_trained_scale_2d*.txt); CLX_PRECISION=f32 = float32 MFMA "
-                             "everywhere: the objects train2d_f32_mfma / infer_f32_mfma of this line")
+                             "everywhere: the objects train2d_f32_mfma / infer_f32_mfma of a --full line")
     if res_f32 is not None:
         out["train2d_f32_mfma"] = dict(
             metric="train crops/sec, the same workload with CLX_PRECISION=f32 (float32 MFMA everywhere: the arithmetic of "
@@ -946,7 +1053,7 @@ def main():
         out["infer"] = infer_obj
     if e2e_obj is not None:
         out["train_e2e"] = e2e_obj
-    if world == 1 and not args.no_infer:
+    if world == 1 and args.full and not args.no_infer:
         try:
             release_device_memory()
             from bench_infer import infer_bench
@@ -954,7 +1061,7 @@ def main():
             out["infer"] = infer_bench(device)
         except Exception as e:  # the train line must survive an inference-side failure
             out["infer"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_train_e2e and args.workload in ("train2d", "train3d"):
+    if world == 1 and args.full and not args.no_train_e2e and args.workload in ("train2d", "train3d"):
         try:
             release_device_memory()
             out["train_e2e"] = train_e2e(args.workload, device, iterations=args.e2e_iterations)
@@ -964,13 +1071,13 @@ def main():
             out["train_e2e"]["with_16_loader_procs"] = {k: more[k] for k in ("value", "unit", "ms_per_iteration", "loader_procs")}
         except Exception as e:
             out["train_e2e"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(WORKLOADS[args.workload], device, seed=0)
         except Exception as e:
             out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
     # (--no-cpu-baseline switches BOTH baselines off: the profiling scripts pass it to keep foreign kernels out of their traces)
-    if world == 1 and not args.no_gpu_library_baseline and not args.no_cpu_baseline and args.workload in ("train2d", "train3d"):
+    if world == 1 and args.full and not args.no_gpu_library_baseline and not args.no_cpu_baseline and args.workload in ("train2d", "train3d"):
         try:
             release_device_memory()
             out["gpu_library_baseline"] = gpu_library_baseline(WORKLOADS[args.workload], device)

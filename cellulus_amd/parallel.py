@@ -49,7 +49,7 @@ def init_from_env(backend=None):
 
 def ranks_sharing_device():
     """Ranks that run on THIS rank's device: 1, or — under the test hook CLX_LOCAL_DEVICE, which pins every rank of the
-    host to one device (the 8-rank dress rehearsal of BASELINE configs[2] on one GPU) — the ranks on this host."""
+    host to one device (several ranks rehearsing a multi-GPU run on one GPU) — the ranks on this host."""
     if "CLX_LOCAL_DEVICE" not in os.environ:
         return 1
     return max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))

@@ -359,6 +359,7 @@ _DDP_SCRIPT = r"""
 import os, sys, torch, torch.distributed as dist
 sys.path.insert(0, sys.argv[1])
 from cellulus_amd import parallel
+torch.cuda.is_available = lambda: False          # host-side ranks: none of them opens a GPU, whatever the machine has
 rank, world, _ = parallel.init_from_env(backend="gloo")
 assert world == 2
 # loss is a SUM over pairs => global gradient = SUM of per-rank gradients (no averaging)
@@ -423,6 +424,7 @@ _DDP8_SCRIPT = r"""
 import os, sys, torch, torch.distributed as dist
 sys.path.insert(0, sys.argv[1])
 from cellulus_amd import parallel
+torch.cuda.is_available = lambda: False          # host-side ranks: none of them opens a GPU, whatever the machine has
 rank, world, _ = parallel.init_from_env(backend="gloo")
 assert world == 8 and parallel.world_size() == 8 and parallel.rank() == rank
 # 5 independent samples on 8 ranks: three ranks get nothing, the others one each, no overlap

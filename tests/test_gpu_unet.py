@@ -635,11 +635,11 @@ WINO_CASES = ["2d_small", "2d_wide", "2d_odd_channels", "2d_two_levels", "3d_sma
 def test_winograd_forward_backward_match_oracle(name, tile, device, monkeypatch):
     """Same parity bars with the Winograd path forced onto every eligible 3x3 layer
     (forward, data gradient and weight gradient), including odd extents and padded channels,
-    for both output tile sizes."""
+    for both output tile sizes.  3-D layers have the F(4x4) form only: asked for F(2x2), every 3-D layer stays on the
+    direct kernels and meets the same bars."""
     import cellulus_amd.models.plan as plan_mod
 
-    if name.startswith("3d") and tile == "2":
-        pytest.skip("3-D layers use the F(4x4) form only")
+    direct_3d = name.startswith("3d") and tile == "2"
     monkeypatch.setattr(plan_mod, "WINO_MIN_CHANNELS", 4)
     monkeypatch.setattr(plan_mod, "WINO_MIN_CHANNELS_3D", 4)
     monkeypatch.setenv("CLX_WINOGRAD", "1")
@@ -649,7 +649,11 @@ def test_winograd_forward_backward_match_oracle(name, tile, device, monkeypatch)
         ref = oracle(raw)
         got = model(raw.to(device)).cpu()
     plan = next(iter(model._plans.values()))
-    assert any(a["fwd"] == (2 if tile == "4" else 1) for a in plan.algo.values()), "Winograd was not selected"
+    three_d = [layer.name for layer in plan.topo.convs if layer.kernel[0] > 1]
+    if direct_3d:
+        assert three_d and not any(plan.algo[n]["fwd"] for n in three_d), "a 3-D layer took the F(2x2) form"
+    else:
+        assert any(a["fwd"] == (2 if tile == "4" else 1) for a in plan.algo.values()), "Winograd was not selected"
     assert (got - ref).abs().max().item() < 1e-4
     oracle = oracle.double()
     ref = oracle(raw.double())
@@ -659,7 +663,10 @@ def test_winograd_forward_backward_match_oracle(name, tile, device, monkeypatch)
     out = model(raw.to(device))
     out.backward(dout.to(device))
     plan = [p for k, p in model._plans.items() if k[2]][0]
-    assert any(a["wgrad"] for a in plan.algo.values()) and any(a["dgrad"] for a in plan.algo.values())
+    if direct_3d:
+        assert not any(plan.algo[n]["dgrad"] or plan.algo[n]["wgrad"] for n in three_d)
+    else:
+        assert any(a["wgrad"] for a in plan.algo.values()) and any(a["dgrad"] for a in plan.algo.values())
     if tile == "4" and name != "2d_two_levels":      # the 2x2 low-res conv of the sub-pixel form: F(4x4, 2x2)
         assert plan.subpixel and all(sp["wino"] == 2 and sp["wino_skip"] == 2 for sp in plan.subpixel.values())
         if name.startswith("3d"):          # ... and, in 3-D, the skip half's data gradient

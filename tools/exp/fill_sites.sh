@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/fills
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/fills -o t -- python3 $R/bench.py ${FILL_ARGS:---streams 1} --steps 2 --warmup 1 --no-infer --no-cpu-baseline --no-train-e2e --no-train3d > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/fills -o t -- python3 $R/bench.py --full ${FILL_ARGS:---streams 1} --steps 2 --warmup 1 --no-infer --no-cpu-baseline --no-train-e2e --no-train3d > /dev/null 2>&1
 f=$(find /tmp/fills -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'EOF'
 import csv, sys

@@ -40,7 +40,7 @@ def main():
                            bytes_per_launch=round(read + write))
     import os
 
-    cmd = os.environ.get("CLX_TRAFFIC_CMD", "bench.py --steps 1 --warmup 1 --no-infer --no-cpu-baseline")
+    cmd = os.environ.get("CLX_TRAFFIC_CMD", "bench.py --full --steps 1 --warmup 1 --no-infer --no-cpu-baseline")
     doc = dict(source="rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of "
                       f"{cmd}; mean over all launches of the run; FETCH_SIZE doubled (gfx950 correction)", kernels=rows)
     json.dump(doc, open(out, "w"), indent=1)

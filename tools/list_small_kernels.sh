@@ -2,11 +2,11 @@
 # One train step's kernels other than the MFMA GEMMs and the Winograd transforms, in launch order with durations
 # (run on the GPU box: gpurun -- bash tools/list_small_kernels.sh).
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
-rm -rf gpurun_out/small_kernels; mkdir -p gpurun_out/small_kernels
-rocprofv3 --kernel-trace --output-format csv -d gpurun_out/small_kernels -o t -- python3 bench.py --steps 2 --warmup 1 --no-infer --no-cpu-baseline --no-train3d > /dev/null 2>&1
+export O=$(mktemp -d)          # the trace; everything worth keeping is printed
+rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python3 bench.py --full --steps 2 --warmup 1 --no-infer --no-cpu-baseline --no-train3d > /dev/null 2>&1
 python3 - <<'PY'
-import csv,glob
-f=glob.glob('gpurun_out/small_kernels/**/*kernel_trace.csv',recursive=True)[0]
+import csv,glob,os
+f=glob.glob(os.environ['O'] + '/**/*kernel_trace.csv',recursive=True)[0]
 rows=list(csv.DictReader(open(f)))
 rows.sort(key=lambda r:int(r['Start_Timestamp']))
 # last step = rows after the last adam kernel before final... print the small kernels (non conv/wino) of the last step

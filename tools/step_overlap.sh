@@ -4,7 +4,7 @@
 set -euo pipefail
 cd "${GRAFT_REPO_ROOT:?run through gpurun (GRAFT_REPO_ROOT unset)}"; export TMPDIR=/tmp
 O="gpurun_out/overlap_${1:-train2d}"; rm -rf "$O"; mkdir -p "$O"
-rocprofv3 --kernel-trace --output-format csv -d "$O" -o t -- python3 bench.py --workload "${1:-train2d}" --steps 3 --warmup 2 --no-infer --no-cpu-baseline --no-train3d --no-train-e2e > "$O/bench.json" 2>/dev/null
+rocprofv3 --kernel-trace --output-format csv -d "$O" -o t -- python3 bench.py --full --workload "${1:-train2d}" --steps 3 --warmup 2 --no-infer --no-cpu-baseline --no-train3d --no-train-e2e > "$O/bench.json" 2>/dev/null
 python3 - "$O" <<'PY'
 import csv, glob, json, sys, collections
 O = sys.argv[1]
