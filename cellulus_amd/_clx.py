@@ -121,7 +121,7 @@ PROTOTYPES = {
     "clx_unpack_wgrad_wino": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "clx_conv_workspace_bytes": (c_size_t, [POINTER(ClxConvDesc), _I]),
     "clx_conv_vcache_bytes": (c_size_t, [POINTER(ClxConvDesc), _I]),
-    "clx_conv_sp_covers": (_I, [POINTER(ClxConvDesc)]),
+    "clx_conv_sp_covers": (_I, [POINTER(ClxConvDesc), _I]),
     "clx_planes_bytes": (c_size_t, [_LL, _I]),
     "clx_split_planes": (_I, [_P, _LL, _LL, _I, _P, _P]),
     "clx_join_planes": (_I, [_P, _LL, _I, _P, _LL, _P]),

@@ -69,9 +69,16 @@ int clx_igemm_launch(const clx_conv_desc* d, int batch, long long bs_in, long lo
                      long long bs_out, hipStream_t st);
 int clx_wgrad_launch(const clx_conv_desc* d, const float* dy, int ld_dy, float* dwpack, float* dbias,
                      int batch, long long bs_x, long long bs_dy, long long bs_out, hipStream_t st);
-// split-precision products (gemm_sp.hip): true if the plain product `d` describes — one source read pixel by pixel, 1x1x1
-// kernel — is one gemm_sp_kernel covers (precision switch set, N % 128 == 0, K % 64 == 0, K >= 128) and has its weight planes
+// split-precision products (gemm_sp.hip), the rules behind clx_conv_sp_covers — geometry and precision only:
+// the forward / data-gradient product `d` describes — one source read pixel by pixel, 1x1x1 kernel — is one gemm_sp_kernel
+// covers (precision switch set, N % 128 == 0, K % 64 == 0, K >= 128) ...
+bool clx_sp_fwd_rule(const clx_conv_desc* d);
+// ... the weight gradient of such a layer (both channel counts multiples of 128, operand planes below 4 GB) ...
+bool clx_sp_wgrad_rule(const clx_conv_desc* d);
+// ... and the forward rule with the weight planes supplied
 bool clx_sp_applicable(const clx_conv_desc* d);
+// does a 2-D Winograd layer's transform-domain arithmetic run in the split precision (wino.hip)?
+bool clx_wino_sp(const clx_conv_desc* d);
 // `batch` products out[b] = epilogue(A[b] B[b]^T) from P3 planes (strides: bytes, bytes, floats); the epilogue fields of
 // `ep` (out, ld_out, bias, relu, accumulate, mask, mask_bits, gate_out and their strides) are honoured
 int clx_sp_launch(const void* A, const void* B, int M, int N, int K, long long rows_a, int batch, long long bs_a, long long bs_b,

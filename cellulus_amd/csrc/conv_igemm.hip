@@ -673,6 +673,12 @@ extern "C" int clx_conv_fwd(const clx_conv_desc* d, clx_stream stream) {
   CLX_REQUIRE(d->algo == CLX_ALGO_DIRECT || d->algo == CLX_ALGO_WINOGRAD || d->algo == CLX_ALGO_WINOGRAD4 ||
                   d->algo == CLX_ALGO_WINOGRAD4_FUSED,
               "clx_conv_fwd: bad algo");
+  // out_planes / out_colsum / aplanes_valid are honoured by the split 1x1 product only (clx_igemm_launch): on any other path
+  // the planes would stay stale and the column sums (a bias gradient the caller has left out elsewhere) would be lost
+  CLX_REQUIRE((d->out_planes == nullptr && d->out_colsum == nullptr && !d->aplanes_valid) ||
+                  (d->algo == CLX_ALGO_DIRECT && d->aplanes != nullptr && clx_sp_applicable(d)),
+              "clx_conv_fwd: out_planes / out_colsum / aplanes_valid need the split-precision 1x1 product "
+              "(clx_conv_sp_covers, wplanes and aplanes)");
   if (d->algo == CLX_ALGO_WINOGRAD4_FUSED) return clx_wino_fused_fwd(d, (hipStream_t)stream);
   if (d->algo != CLX_ALGO_DIRECT) return clx_wino_fwd(d, (hipStream_t)stream);
   // pool_out / tile_list / adjoint are honoured by the Winograd paths only: a caller whose plan and dispatch disagree

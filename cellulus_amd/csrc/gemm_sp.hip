@@ -1317,17 +1317,33 @@ extern "C" int clx_join_planes(const void* planes, long long rows, int K, float*
   return CLX_OK;
 }
 
-bool clx_sp_applicable(const clx_conv_desc* d) {
-  if (d->precision != CLX_PREC_F32X3BF16 || d->wplanes == nullptr || d->nsrc != 1) return false;
+// a 1x1 layer over one plain source (no padding, crop or upsampling) in the split precision
+static bool sp_pointwise(const clx_conv_desc* d) {
+  if (d->precision != CLX_PREC_F32X3BF16 || d->nsrc != 1) return false;
   if (d->KD != 1 || d->KH != 1 || d->KW != 1 || d->PD || d->PH || d->PW) return false;
   const clx_src& S = d->src[0];
   if (S.fz != 1 || S.fy != 1 || S.fx != 1 || S.oz || S.oy || S.ox) return false;
-  if (S.D != d->ID || S.H != d->IH || S.W != d->IW) return false;
-  return d->N % SP_BN == 0 && S.C % 64 == 0 && S.C >= 128 && d->ld_out % 4 == 0;
+  return S.D == d->ID && S.H == d->IH && S.W == d->IW;
 }
 
-extern "C" int clx_conv_sp_covers(const clx_conv_desc* d) {
-  return d != nullptr && d->algo == CLX_ALGO_DIRECT && d->aplanes != nullptr && clx_sp_applicable(d) ? 1 : 0;
+bool clx_sp_fwd_rule(const clx_conv_desc* d) {
+  return sp_pointwise(d) && d->N % SP_BN == 0 && d->src[0].C % 64 == 0 && d->src[0].C >= 128 && d->ld_out % 4 == 0;
+}
+
+bool clx_sp_wgrad_rule(const clx_conv_desc* d) {
+  if (!sp_pointwise(d) || d->N % 128 != 0 || d->src[0].C % 128 != 0) return false;
+  // the weight-gradient product addresses its operand planes with 32-bit offsets
+  const long long ch = d->N > d->src[0].C ? d->N : d->src[0].C;
+  return (long long)d->B * d->ID * d->IH * d->IW * ch * 6 < (1ll << 32) - (1 << 24);
+}
+
+bool clx_sp_applicable(const clx_conv_desc* d) { return d->wplanes != nullptr && clx_sp_fwd_rule(d); }
+
+extern "C" int clx_conv_sp_covers(const clx_conv_desc* d, int pass) {
+  if (d == nullptr || (pass != CLX_PASS_FWD && pass != CLX_PASS_WGRAD)) return 0;
+  if (d->algo == CLX_ALGO_WINOGRAD || d->algo == CLX_ALGO_WINOGRAD4) return clx_wino_sp(d) ? 1 : 0;
+  if (d->algo != CLX_ALGO_DIRECT) return 0;
+  return (pass == CLX_PASS_FWD ? clx_sp_fwd_rule(d) : clx_sp_wgrad_rule(d)) ? 1 : 0;
 }
 
 // the batched product behind clx_gemm_planes and the precision switch of clx_conv_fwd: `batch` problems, operand b at

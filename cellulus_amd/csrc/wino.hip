@@ -912,6 +912,8 @@ int wino_wgrad_t(const clx_conv_desc* d, const float* dy, int ld_dy, float* dwpa
 
 }  // namespace
 
+bool clx_wino_sp(const clx_conv_desc* d) { return wino_sp(d); }
+
 extern "C" size_t clx_conv_workspace_bytes(const clx_conv_desc* d, int pass) {
   if (d == nullptr || !applicable(d)) return 0;
   if (pass == CLX_PASS_WGRAD && d->PH != 0) return 0;

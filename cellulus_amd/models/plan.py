@@ -476,7 +476,8 @@ class UNetPlan:
                                              dtype=torch.float32, device=self.device)
         if ws_bytes:
             self.workspace = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=self.device)
-        # packed weights
+        self._decide_sp()
+        # packed weights (with their P3 planes where the split-precision products read them)
         self.wpack_fwd = {}
         self.wpack_dgrad = {}
         for layer in t.convs:
@@ -484,20 +485,18 @@ class UNetPlan:
             taps = wino_taps(code, layer.kernel) if code else layer.taps
             self.wpack_fwd[layer.name] = torch.empty(
                 pad4(layer.cout) * taps * layer.cin_pad, dtype=torch.float32, device=self.device)
-            if code and layer.kernel[0] == 1:
-                self._register_wplanes(self.wpack_fwd[layer.name], pad4(layer.cout), WINO_TAPS[code], layer.cin_pad)
-            elif not code and self._pointwise_sp(layer)[0]:
-                self._register_wplanes(self.wpack_fwd[layer.name], pad4(layer.cout), 1, layer.cin_pad)
-        for sp in self.subpixel.values():
-            if sp["wino"] and sp["zk"][0] == 1:
-                self._register_wplanes(sp["wp_z_fwd"], sp["P"] * sp["N"], 25, sp["C1p"])
-        if self.precision:
-            # scratch for the planes of a 1x1 layer's input (a training plan keeps one buffer per layer instead)
-            rows_k = [(self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2], layer.cin_pad)
-                      for layer in t.convs if self._pointwise_sp(layer)[0]]
-            if rows_k:
-                self.aplanes = torch.empty(max(int(_clx.load().clx_planes_bytes(r, k)) for r, k in rows_k),
-                                           dtype=torch.uint8, device=self.device)
+            if self.sp_pass[layer.name][0]:
+                self._register_wplanes(self.wpack_fwd[layer.name], layer.cin_pad)
+        for info in t.r_info:
+            sp = self.subpixel.get(info["conv0"].name)
+            if sp and sp["wino"] and self._sp_covers(self._sp_descs(info["conv0"], sp)[0], 0, 3 if sp["fused_z"] else sp["wino"]):
+                self._register_wplanes(sp["wp_z_fwd"], sp["C1p"])
+        # scratch for the planes of a 1x1 layer's input (a training plan keeps one buffer per layer instead)
+        rows_k = [(self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2], layer.cin_pad)
+                  for layer in t.convs if self.sp_pass[layer.name][0] and not self.algo[layer.name]["fwd"]]
+        if rows_k:
+            self.aplanes = torch.empty(max(int(_clx.load().clx_planes_bytes(r, k)) for r, k in rows_k),
+                                       dtype=torch.uint8, device=self.device)
         self._packed_version = None
         self._bwd_ready = False
         self.vcache = {}
@@ -574,16 +573,15 @@ class UNetPlan:
                 sp["g_skip"] = torch.empty(layer.cout * sp["C0"] * layer.taps, dtype=torch.float32, device=self.device)
                 sp["g_z"] = torch.empty(sp["P"] * sp["N"] * sp["C1"] * sp["ztaps"], dtype=torch.float32,
                                         device=self.device)
+                dz, ds = self._sp_descs(layer, sp)
+                ds.N = layer.cout
                 if sp["wino_skip"] and not sp["fused_skip"] and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                    tiles = self.B * layer.in_shape[0] * -(-layer.out_shape[1] // 4) * -(-layer.out_shape[2] // 4)
-                    sp["vcache_skip"] = torch.empty(self._vfloats(36, tiles, sp["C0p"]), dtype=torch.float32, device=self.device)
+                    sp["vcache_skip"] = self._float_scratch(self._vcache_bytes(ds, sp["wino_skip"], 0))
                 sp["_dw_z_n"] = ztaps * sp["P"] * sp["N"] * sp["C1p"]
                 if sp["wino"] and not sp["fused_z"] and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                    zs = sp["zshape"]
-                    tiles = self.B * (zs[0] + sp["zk"][0] - 1) * -(-zs[1] // 4) * -(-zs[2] // 4)
-                    sp["vcache"] = torch.empty(self._vfloats(25, tiles, sp["C1p"]), dtype=torch.float32, device=self.device)
-                if sp["wino"] and sp["zk"][0] == 1:
-                    self._register_wplanes(sp["wp_z_dgrad"], sp["C1p"], 25, sp["P"] * sp["N"])
+                    sp["vcache"] = self._float_scratch(self._vcache_bytes(dz, sp["wino"], 0))
+                if sp["wino"] and self._sp_covers(self._sp_low_dgrad_desc(layer, sp, None), 0, sp["wino"]):
+                    self._register_wplanes(sp["wp_z_dgrad"], sp["P"] * sp["N"], dgrad=True)
         # ReLU gates as bits: written by the epilogue that produces a layer's output, read by the data
         # gradient that passes through that ReLU — 1/32 of the float tensor it would otherwise read (the
         # 64-channel 1x1 layers of the 3-D network are HBM-bound).  Whole words per pixel (channels %
@@ -614,30 +612,26 @@ class UNetPlan:
         self.dycache = None
         if os.environ.get("CLX_DY_DUAL", "1") != "0":
             need = 0
-
-            def dual_floats(code, out_shape, k, chans):
-                a2, m = (WINO_TAPS[code], WINO_TILE[code]) if k == 3 else (25, 4)
-                return self._vfloats(a2, self.B * out_shape[0] * (-(-(out_shape[1] + k - 1) // m)) * (-(-(out_shape[2] + k - 1) // m)),
-                                     chans)
-
             for layer in t.convs:
                 a = self.algo[layer.name]
                 if a["wgrad"] and a["wgrad"] == a["dgrad"] and layer.name not in self.subpixel and layer.name not in self.adjoint:
-                    need = max(need, dual_floats(a["wgrad"], layer.out_shape, 3, pad4(layer.cout)))
-            for name, sp in self.subpixel.items():
-                if sp["wino"]:
-                    need = max(need, dual_floats(2, sp["zshape"], 2, sp["P"] * sp["N"]))
+                    d = self._desc(layer)
+                    d.N = pad4(layer.cout)
+                    need = max(need, self._vcache_bytes(d, a["wgrad"], 1))
+            for info in t.r_info:
+                sp = self.subpixel.get(info["conv0"].name)
+                if sp and sp["wino"]:
+                    need = max(need, self._vcache_bytes(self._sp_descs(info["conv0"], sp)[0], sp["wino"], 1))
             if need:
-                self.dycache = torch.empty(need + 4, dtype=torch.float32, device=self.device)
+                self.dycache = self._float_scratch(need)
         # forward and weight gradient of a Winograd layer transform the same input: keep V
         self.vcache = {}
         for layer in t.convs:
             a = self.algo[layer.name]
             if a["fwd"] and a["fwd"] == a["wgrad"] and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                m = WINO_TILE[a["fwd"]]
-                tiles = self.B * layer.in_shape[0] * -(-layer.out_shape[1] // m) * -(-layer.out_shape[2] // m)
-                self.vcache[layer.name] = torch.empty(self._vfloats(WINO_TAPS[a["fwd"]], tiles, layer.cin_pad),
-                                                      dtype=torch.float32, device=self.device)
+                d = self._desc(layer)
+                d.N = layer.cout
+                self.vcache[layer.name] = self._float_scratch(self._vcache_bytes(d, a["fwd"], 0))
         total = 0
         self.dw_off = {}
         for layer in t.convs:
@@ -649,31 +643,29 @@ class UNetPlan:
                 taps = wino_taps(code, layer.kernel) if code else layer.taps
                 self.wpack_dgrad[layer.name] = torch.empty(
                     layer.cin_pad * taps * pad4(layer.cout), dtype=torch.float32, device=self.device)
-                if code and layer.kernel[0] == 1:
-                    self._register_wplanes(self.wpack_dgrad[layer.name], layer.cin_pad, WINO_TAPS[code], pad4(layer.cout))
-                elif not code and self._pointwise_sp(layer)[1]:
-                    self._register_wplanes(self.wpack_dgrad[layer.name], layer.cin_pad, 1, pad4(layer.cout))
-        if self.precision:
-            # training: the planes of a 1x1 layer's input stay for its weight gradient; one scratch for the planes of dY
-            need_dy = 0
-            for layer in t.convs:
-                fwd_sp, dgrad_sp, wgrad_sp = self._pointwise_sp(layer)
-                if layer.name in self.chains or layer.name in self.chain_second:
-                    continue
-                rows = self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2]
-                if fwd_sp or wgrad_sp:
-                    self.xplanes[layer.name] = self._planes_scratch(rows, layer.cin_pad)
-                if (dgrad_sp and layer.param_index > 0) or wgrad_sp:
-                    need_dy = max(need_dy, int(_clx.load().clx_planes_bytes(rows, pad4(layer.cout))))
-            if need_dy:
-                # two of them: a data gradient reads the planes of its dY out of one while its epilogue writes the planes
-                # of the next layer's dY into the other
-                self.dyplanes = torch.empty(need_dy, dtype=torch.uint8, device=self.device)
-                self.dyplanes2 = torch.empty(need_dy, dtype=torch.uint8, device=self.device)
-            # tensor -> the 1x1 layer that reads it as its one plain source and keeps planes of it
-            for layer in t.convs:
-                if layer.name in self.xplanes and pad4(t.shapes[layer.sources[0].tensor][1]) == layer.cin_pad:
-                    self._pointwise_reader[layer.sources[0].tensor] = layer
+                if self.sp_pass[layer.name][1]:
+                    self._register_wplanes(self.wpack_dgrad[layer.name], pad4(layer.cout), dgrad=True)
+        # training: the planes of a split 1x1 layer's input stay for its weight gradient; one scratch for the planes of dY
+        need_dy = 0
+        for layer in t.convs:
+            if layer.name in self.chains or layer.name in self.chain_second:
+                continue
+            a = self.algo[layer.name]
+            fwd_sp, dgrad_sp, wgrad_sp = (on and not a[k] for on, k in zip(self.sp_pass[layer.name], ("fwd", "dgrad", "wgrad")))
+            rows = self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2]
+            if fwd_sp or wgrad_sp:
+                self.xplanes[layer.name] = self._planes_scratch(rows, layer.cin_pad)
+            if dgrad_sp or wgrad_sp:
+                need_dy = max(need_dy, int(_clx.load().clx_planes_bytes(rows, pad4(layer.cout))))
+        if need_dy:
+            # two of them: a data gradient reads the planes of its dY out of one while its epilogue writes the planes
+            # of the next layer's dY into the other
+            self.dyplanes = torch.empty(need_dy, dtype=torch.uint8, device=self.device)
+            self.dyplanes2 = torch.empty(need_dy, dtype=torch.uint8, device=self.device)
+        # tensor -> the 1x1 layer that reads it as its one plain source and keeps planes of it
+        for layer in t.convs:
+            if layer.name in self.xplanes and pad4(t.shapes[layer.sources[0].tensor][1]) == layer.cin_pad:
+                self._pointwise_reader[layer.sources[0].tensor] = layer
         # the sub-pixel layers' weight-gradient accumulators live behind the others: one fill zeroes all
         sp_off = {}
         for name, sp in self.subpixel.items():
@@ -1054,47 +1046,56 @@ class UNetPlan:
         ts += list(self.xplanes.values()) + list(self.vcache.values())
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
-    def _register_wplanes(self, wp, n, batch, k):
-        """planes for the packed weights `wp` seen as `batch` matrices [n][k] (the B operand of a plain product), if
-        the split-precision kernels cover that product"""
-        if not self.precision or n % 128 or k % 64 or k < 128 or wp.data_ptr() in self._wplanes:
-            return
-        nbytes = int(_clx.load().clx_planes_bytes(batch * n, k))
-        self._wplanes[wp.data_ptr()] = (wp, torch.empty(nbytes, dtype=torch.uint8, device=self.device), batch * n, k)
+    def _sp_covers(self, d, pass_, algo):
+        """clx_conv_sp_covers: does the call of pass `pass_` (0: clx_conv_fwd, data-gradient form included; 1:
+        clx_conv_wgrad) with descriptor `d` and algorithm `algo` run its products in the split precision?"""
+        d.algo = algo
+        return bool(_clx.load().clx_conv_sp_covers(ctypes.byref(d), pass_))
+
+    def _decide_sp(self):
+        """sp_pass[layer name] = (forward, data gradient, weight gradient) in the split precision: the library's answer
+        for the descriptors the layer launches with.  (A sub-pixel layer launches descriptors of its own: _sp_descs.)"""
+        self.sp_pass = {}
+        for layer in self.topo.convs:
+            if layer.name in self.subpixel:
+                self.sp_pass[layer.name] = (False, False, False)
+                continue
+            a = self.algo[layer.name]
+            d = self._desc(layer)
+            d.N = layer.cout
+            fwd = self._sp_covers(d, 0, a["fwd"])
+            d.N = pad4(layer.cout)
+            wgrad = self._sp_covers(d, 1, a["wgrad"])
+            dgrad = layer.param_index > 0 and self._sp_covers(self._dgrad_desc(layer, None), 0, a["dgrad"])
+            self.sp_pass[layer.name] = (fwd, dgrad, wgrad)
+
+    def _register_wplanes(self, wp, k, dgrad=False):
+        """planes for the packed weights `wp` seen as [rows][k] (the B operand of the split-precision products that read
+        them); `dgrad`: data-gradient weights, split only after a packing that includes them"""
+        if wp.data_ptr() not in self._wplanes:
+            rows = wp.numel() // k
+            nbytes = int(_clx.load().clx_planes_bytes(rows, k))
+            self._wplanes[wp.data_ptr()] = (wp, torch.empty(nbytes, dtype=torch.uint8, device=self.device), rows, k, dgrad)
 
     def _set_wpack(self, d, wp):
         d.wpack = wp.data_ptr()
         e = self._wplanes.get(wp.data_ptr())
         d.wplanes = e[1].data_ptr() if e is not None else None
 
-    def _split_wplanes(self, st):
-        """the planes of every registered packed-weight tensor, after a (re)packing"""
-        for wp, planes, rows, k in self._wplanes.values():
-            _clx.call("clx_split_planes", _clx.ptr(wp), k, rows, k, _clx.ptr(planes), st)
+    def _split_wplanes(self, need_dgrad, st):
+        """the planes of every registered packed-weight tensor the last packing wrote"""
+        for wp, planes, rows, k, dgrad in self._wplanes.values():
+            if need_dgrad or not dgrad:
+                _clx.call("clx_split_planes", _clx.ptr(wp), k, rows, k, _clx.ptr(planes), st)
 
-    def _pointwise_sp(self, layer: ConvLayer):
-        """(forward product, data-gradient product, weight-gradient product) of a 1x1 layer over one plain source in the
-        split precision?  The rules of clx_sp_applicable / clx_conv_wgrad."""
-        if not self.precision or tuple(layer.kernel) != (1, 1, 1) or len(layer.sources) != 1:
-            return False, False, False
-        s = layer.sources[0]
-        shape, _c = self.topo.shapes[s.tensor]
-        if tuple(s.crop) != (0, 0, 0) or tuple(s.factor) != (1, 1, 1) or tuple(shape) != tuple(layer.in_shape):
-            return False, False, False
-        n, c = pad4(layer.cout), layer.cin_pad
-        if layer.cout != n:
-            return False, False, False
-        rows = self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2]
-        return (n % 128 == 0 and c % 64 == 0 and c >= 128, c % 128 == 0 and n % 64 == 0 and n >= 128,
-                # (the weight-gradient product addresses its operand planes with 32-bit offsets: clx_conv_wgrad's rule)
-                n % 128 == 0 and c % 128 == 0 and rows * max(n, c) * 6 < (1 << 32) - (1 << 24))
+    def _vcache_bytes(self, d, algo, which):
+        """clx_conv_vcache_bytes of the Winograd call `d` with algorithm `algo` (float32, or P3 planes where it runs in the
+        split precision)"""
+        d.algo = algo
+        return int(_clx.load().clx_conv_vcache_bytes(ctypes.byref(d), which))
 
-    def _vfloats(self, a2, tiles, chans):
-        """floats of a buffer for `a2` transformed tensors [tiles][chans]: float32, or P3 planes (6 bytes per element,
-        rows padded to 64) where the layer may run in the split precision"""
-        if not self.precision:
-            return a2 * tiles * chans
-        return a2 * max(128, (tiles + 63) // 64 * 64) * chans * 3 // 2 + 16
+    def _float_scratch(self, nbytes):
+        return torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=self.device)
 
     def _planes_scratch(self, rows, k):
         return torch.empty(int(_clx.load().clx_planes_bytes(rows, k)), dtype=torch.uint8, device=self.device)
@@ -1297,7 +1298,7 @@ class UNetPlan:
             _clx.call("clx_pack_weights_batch", _clx.ptr(cache["table"]), cache["njobs"], cache["biggest"], st)
         for layer in cache["singles"]:
             self._pack_layer(layer, params[2 * layer.param_index], need_dgrad, st)
-        self._split_wplanes(st)
+        self._split_wplanes(need_dgrad, st)
 
     def pack_weights(self, params, version, need_dgrad):
         """(Re)pack weights when the parameters changed (version = tuple of tensor versions)."""
@@ -1318,7 +1319,7 @@ class UNetPlan:
                 self._sp_pack(layer, self.subpixel[layer.name], w, need_dgrad, st)
                 continue
             self._pack_layer(layer, w, need_dgrad, st)
-        self._split_wplanes(st)
+        self._split_wplanes(need_dgrad, st)
         self._packed_version = key
 
     # ----------------------------------------------------------------- forward
@@ -1421,7 +1422,7 @@ class UNetPlan:
         d.ld_out = pad4(op.cout)
         if op.relu and self.keep:
             self._set_gate_out(d, op.out)
-        if self.precision and not self.algo[op.name]["fwd"] and self._pointwise_sp(op)[0]:
+        if self.sp_pass[op.name][0] and not self.algo[op.name]["fwd"]:
             xp = self.xplanes.get(op.name) if self.keep and self._bwd_ready and tiles is None else None
             d.aplanes = (xp if xp is not None else self.aplanes).data_ptr()
             if xp is not None:
@@ -1430,7 +1431,7 @@ class UNetPlan:
                 self._xplanes_fresh.add(op.name)
                 # ... and this layer's epilogue writes the planes of the 1x1 layer that reads its output
                 nxt = self._pointwise_reader.get(op.out)
-                if nxt is not None and nxt.name in self.xplanes and os.environ.get("CLX_SP_EPILOGUE_PLANES", "1") != "0":
+                if nxt is not None and os.environ.get("CLX_SP_EPILOGUE_PLANES", "1") != "0":
                     d.out_planes = self.xplanes[nxt.name].data_ptr()
                     self._xplanes_fresh.add(nxt.name)
         if self.algo[op.name]["fwd"]:
@@ -1674,7 +1675,7 @@ class UNetPlan:
             dy_ready = dy_planes is not None
             if dy_planes is None and self.dyplanes is not None:
                 dy_planes = self.dyplanes
-            if not wino_w and self._pointwise_sp(layer)[2] and layer.name in self.xplanes and dy_planes is not None:
+            if self.sp_pass[layer.name][2] and not wino_w:
                 d.aplanes = self.xplanes[layer.name].data_ptr()
                 d.aplanes_valid = 1 if layer.name in self._xplanes_fresh else 0
                 d.dyplanes = dy_planes.data_ptr()
@@ -1691,7 +1692,7 @@ class UNetPlan:
                 continue
             dd = self._dgrad_desc(layer, dy)
             self._set_wpack(dd, self.wpack_dgrad[layer.name])
-            dgrad_sp = not self.algo[layer.name]["dgrad"] and self._pointwise_sp(layer)[1] and dy_planes is not None
+            dgrad_sp = self.sp_pass[layer.name][1] and not self.algo[layer.name]["dgrad"]
             if dgrad_sp:
                 dd.aplanes = dy_planes.data_ptr()
                 dd.aplanes_valid = 1 if dy_ready else 0          # (left by the weight gradient above, or by the layer behind)
@@ -1743,10 +1744,10 @@ class UNetPlan:
                     self._set_mask(dd, prev.out, relu=prev.relu)
                     dd.out = self.gbuf[prev.out].data_ptr()
                     dd.ld_out = pad4(prev.cout)
-                    if (dgrad_sp and prev.name in self.xplanes and self._pointwise_sp(prev)[2] and prev.name not in self.chains
-                            and prev.name not in self.chain_second and prev.cout == pad4(prev.cout)
+                    if (dgrad_sp and prev.name in self.xplanes and self.sp_pass[prev.name][2]
                             and os.environ.get("CLX_SP_EPILOGUE_PLANES", "1") != "0"):
-                        # the epilogue writes the planes of prev's dY and adds prev's bias gradient (its column sums)
+                        # the epilogue writes the planes of prev's dY and adds prev's bias gradient (its column sums): prev
+                        # is a split 1x1 layer (xplanes: not one of a fused pair) whose weight gradient reads those planes
                         other = self.dyplanes2 if dy_planes is self.dyplanes else self.dyplanes
                         dd.out_planes = other.data_ptr()
                         gbp = grads[2 * prev.param_index + 1]

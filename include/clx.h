@@ -169,8 +169,9 @@ typedef struct clx_conv_desc {
    * vcache / accumulate with a list. */
   const int* tile_list;
   int tile_count;
-  /* clx_conv_precision.  CLX_PREC_F32 (0, default): float32 MFMA — the reference's arithmetic.  CLX_PREC_F32X3BF16: where the
-   * convolution is a plain matrix product — 1x1 layers, the transform-domain products of the 2-D Winograd layers,
+  /* clx_conv_precision.  CLX_PREC_F32 (0, the default of a zeroed descriptor): float32 MFMA — the reference's arithmetic.
+   * (The Python layer, models/plan.py, defaults to CLX_PREC_F32X3BF16; CLX_PRECISION=f32 selects float32 there.)
+   * CLX_PREC_F32X3BF16: where the convolution is a plain matrix product — 1x1 layers, the transform-domain products of the 2-D Winograd layers,
    * forward, data gradient and weight gradient; N % 128 == 0, contraction length % 64 == 0 and >= 128 — the operands
    * are split exactly into three bfloat16 pieces and six exact products per float32 product are accumulated in float32
    * on the bf16 matrix cores ("P3 planes" above; csrc/gemm_sp.hip).  Everything else stays on the float32 kernels.
@@ -179,7 +180,8 @@ typedef struct clx_conv_desc {
    * whenever wpack is); those of the activations are made by the library: by the Winograd transforms themselves inside
    * `workspace` / `vcache` (clx_conv_workspace_bytes and clx_conv_vcache_bytes grow accordingly), by a split pass into
    * `aplanes` (clx_planes_bytes(M, C) bytes of scratch) for a 1x1 layer.  A layer without wplanes (or a 1x1 layer
-   * without aplanes) runs in float32.
+   * without aplanes) runs in float32.  clx_conv_sp_covers(d, pass) says, from geometry and precision alone, which calls run
+   * in this precision once the planes are supplied.
    * aplanes_valid = 1: `aplanes` already holds the planes of src[0] (an earlier call of the same layer left them: the
    * forward pass for the weight gradient, the weight gradient's dyplanes for the data gradient) — no split pass.
    * dyplanes (clx_conv_wgrad of a 1x1 layer only): clx_planes_bytes(M, N) bytes that receive the planes of dY; the bias
@@ -188,7 +190,9 @@ typedef struct clx_conv_desc {
    * epilogue ALSO writes the P3 planes of `out` (clx_planes_bytes(M, N) bytes: the operand planes of the layer that reads
    * `out` next — its aplanes with aplanes_valid = 1, or a weight gradient's dyplanes with dyplanes_valid = 1) and adds the
    * column sums of `out` into out_colsum[N] (the bias gradient of the layer whose dY this data-gradient call produces).
-   * clx_conv_sp_covers(d) says whether a call will honour them. */
+   * Only the split 1x1 product honours out_planes / out_colsum / aplanes_valid: clx_conv_fwd refuses them (an error before
+   * any launch) on every other path — Winograd, fused, small-channel, float32, or planes missing.  Likewise
+   * clx_conv_wgrad refuses aplanes_valid / dyplanes_valid on a call that will not read the planes. */
   int precision;
   const void* wplanes;
   void* aplanes;
@@ -247,15 +251,16 @@ size_t clx_conv_workspace_bytes(const clx_conv_desc* d, int pass);
 /* Bytes of the buffers a caller may hand to a Winograd layer to carry transformed tensors from one call to the next:
  * which = 0: clx_conv_desc.vcache (V = B^T d B of the layer's input: written by clx_conv_fwd, reused by clx_conv_wgrad);
  * which = 1: clx_conv_desc.dy_vcache (the data gradient's input transform of dY, written by clx_conv_wgrad).  Float32
- * tensors, or P3 planes — 1.5x the bytes — where the layer runs in the split precision.  0 if Winograd does not apply. */
+ * tensors, or P3 planes — 1.5x the bytes — where the layer runs in the split precision (clx_conv_sp_covers).  0 if
+ * Winograd does not apply. */
 size_t clx_conv_vcache_bytes(const clx_conv_desc* d, int which);
 
 /* ---- Split-precision operands ("P3 planes", round 6) ----
  * The precision CLX_PREC_F32X3BF16 of clx_conv_desc computes float32 products on the bf16 matrix cores: every operand
- * element is split EXACTLY into three bfloat16 pieces x = h0 + h1 + h2 (truncation, 8 + 8 + 8 significand bits) and
- * the six products a_i b_j, i + j <= 2, are accumulated in float32 (v_mfma_f32_32x32x16_bf16) — the dropped terms are
- * <= 2^-24 relative, one float32 rounding.  The pieces are made ONCE where a tensor is produced, in the layout the
- * matrix core consumes ("P3"): an [R][K] operand (K % 16 == 0) as 1-KB fragments, fragment (rb, ks, p) = piece p of
+ * element is split EXACTLY into three bfloat16 pieces x = h0 + h1 + h2 (round to nearest: h0 = rn(x), h1 = rn(x - h0),
+ * h2 = x - h0 - h1; csrc/sp_planes.h) and the six products a_i b_j, i + j <= 2, are accumulated in float32
+ * (v_mfma_f32_32x32x16_bf16) — the dropped terms are <= 2^-25 relative, below one float32 rounding.  The pieces are
+ * made ONCE where a tensor is produced, in the layout the matrix core consumes ("P3"): an [R][K] operand (K % 16 == 0) as 1-KB fragments, fragment (rb, ks, p) = piece p of
  * rows 32 rb .. 32 rb + 31, k = 16 ks .. 16 ks + 15 at byte ((rb * K/16 + ks) * 3 + p) * 1024; inside a fragment the 16 bytes
  * at 512 h + 16 r hold x_p[32 rb + r][16 ks + 8 h .. + 7].  Rows up to the next multiple of 64 (at least 128 rows) exist and are ZERO.  6 bytes
  * per element.  (No reference counterpart: the reference's torch.nn.Conv{2,3}d keep float32 operands,
@@ -278,9 +283,18 @@ int clx_gemm_planes(const void* a_planes, const void* b_planes, int M, int N, in
 int clx_wgrad_planes(const void* dy_planes, const void* x_planes, long long rows, int N, int C, float* dw, int ld_dw,
                      clx_stream stream);
 
-/* 1 if clx_conv_fwd(d) runs as the split-precision product from planes (1x1 layer, precision / wplanes / aplanes set, N % 128
- * == 0, C % 64 == 0, C >= 128) — the form that honours out_planes / out_colsum —, else 0 */
-int clx_conv_sp_covers(const clx_conv_desc* d);
+/* 1 if a call of pass `pass` (CLX_PASS_FWD: clx_conv_fwd, the data-gradient form included — ask with the data-gradient
+ * descriptor; CLX_PASS_WGRAD: clx_conv_wgrad) with descriptor `d` runs its products in the split precision once the planes
+ * buffers are supplied, else 0.  Judges `algo`, geometry and `precision` only — no pointer field is read, so a caller can
+ * ask before it allocates:
+ *   CLX_ALGO_DIRECT, FWD:   1x1 layer over one plain source (no padding, crop or upsampling), N % 128 == 0, C % 64 == 0,
+ *                           C >= 128 — the form that honours out_planes / out_colsum / aplanes_valid;
+ *   CLX_ALGO_DIRECT, WGRAD: the same layer with N % 128 == 0, C % 128 == 0 and the operand planes below 4 GB;
+ *   CLX_ALGO_WINOGRAD / _WINOGRAD4, either pass: 2-D layer, N % 128 == 0, C % 128 == 0, one transform point's planes below
+ *                           4 GB (forward, data gradient and weight gradient of a layer share V / A dY A^T as planes);
+ *   CLX_ALGO_WINOGRAD4_FUSED: 0 (float32 throughout).
+ * The launches still run in float32 where wplanes (or, for a 1x1 layer, aplanes / dyplanes) are missing. */
+int clx_conv_sp_covers(const clx_conv_desc* d, int pass);
 
 /* out = act(conv(in) + bias).  f32 MFMA implicit GEMM (M = output pixels,
  * N = output channels, K = taps x channels). Also used for the data gradient

@@ -1074,7 +1074,7 @@ def test_native_pair_offsets_are_numpys_stream_value_for_value_and_leave_its_sta
     assert after[3] == 1 and after[4] == before[4]
 
 
-def test_planes_geometry_and_argument_validation_without_gpu():
+def test_planes_format_and_argument_validation_without_gpu():
     """The P3 plane format of the split-precision products (include/clx.h, csrc/sp_planes.h): 6 bytes per element, rows
     padded to a multiple of 64 and at least 128; the entry points refuse what the kernels do not cover before any launch."""
     from cellulus_amd import _clx
@@ -1098,8 +1098,116 @@ def test_planes_geometry_and_argument_validation_without_gpu():
     with pytest.raises(_clx.ClxError, match="128"):
         _clx.call("clx_wgrad_planes", p, p, 1000, 128, 64, p, 64, null)
     d = _clx.ClxConvDesc()
-    assert lib.clx_conv_sp_covers(ctypes.byref(d)) == 0
+    assert lib.clx_conv_sp_covers(ctypes.byref(d), 0) == 0 and lib.clx_conv_sp_covers(ctypes.byref(d), 1) == 0
     # the switch of the Python layer
     from cellulus_amd.models import plan as P
 
     assert P.DEFAULT_PRECISION == "f32x3bf16"
+
+
+def _sp_desc(C, N, hw=(64, 64), B=2, k=1, D=1, algo=0, precision=1, crop=0, factor=1):
+    """a one-source convolution descriptor with fake aligned pointers (geometry queries and argument checks only)"""
+    from cellulus_amd import _clx
+
+    d = _clx.ClxConvDesc()
+    d.nsrc = 1
+    src = _clx.ClxSrc()
+    src.ptr = 4096
+    src.C = src.ld = C
+    src.D, src.H, src.W = D, -(-(hw[0] + crop) // factor), -(-(hw[1] + crop) // factor)
+    src.oz, src.oy, src.ox = 0, crop, crop
+    src.fz, src.fy, src.fx = 1, factor, factor
+    d.src[0] = src
+    d.B = B
+    d.ID, d.IH, d.IW = D, hw[0], hw[1]
+    d.KD, d.KH, d.KW = (k if D > 1 else 1), k, k
+    d.N = N
+    d.algo = algo
+    d.precision = precision
+    d.wpack = d.out = d.wplanes = d.aplanes = d.dyplanes = 4096
+    d.ld_out = N
+    return d
+
+
+def test_split_precision_query_and_refusals_without_gpu():
+    """clx_conv_sp_covers(d, pass) is the one statement of which calls run in the split precision (geometry and precision
+    only, no pointer read); clx_conv_fwd / clx_conv_wgrad refuse plane hand-overs a call would not honour — before any
+    launch; clx_conv_vcache_bytes sizes float32 or planes by the same rule."""
+    from cellulus_amd import _clx
+
+    lib = _clx.load()
+    bench = dict(B=8, hw=(254, 254))              # the 2-D benchmark network's top level
+    table = [
+        # (descriptor, forward / data gradient, weight gradient)
+        (_sp_desc(256, 256, **bench), 1, 1),
+        (_sp_desc(768, 768, B=8, hw=(124, 124)), 1, 1),
+        (_sp_desc(1024, 256, **bench), 1, 1),
+        (_sp_desc(256, 64, **bench), 0, 0),
+        (_sp_desc(768, 64, **bench), 0, 0),
+        (_sp_desc(256, 768, **bench), 1, 1),
+        (_sp_desc(96, 256), 0, 0),                # C % 64
+        (_sp_desc(256, 96), 0, 0),                # N % 128
+        (_sp_desc(192, 256), 1, 0),               # the product covers C % 64, the weight gradient C % 128 only
+        (_sp_desc(64, 128), 0, 0),                # C < 128
+        (_sp_desc(256, 256, crop=4), 0, 0),       # cropped source
+        (_sp_desc(256, 256, factor=2), 0, 0),     # upsampled source
+        (_sp_desc(256, 256, k=3), 0, 0),          # 3x3, direct
+        (_sp_desc(256, 256, precision=0), 0, 0),
+        (_sp_desc(768, 768, B=8, hw=(512, 512)), 1, 0),     # the weight gradient's planes would pass 4 GB
+        (_sp_desc(256, 256, D=16, hw=(16, 16)), 1, 1),      # a 3-D 1x1 layer
+        (_sp_desc(256, 256, k=3, algo=2), 1, 1),            # 2-D Winograd: wino_sp for every pass
+        (_sp_desc(256, 256, k=3, algo=1), 1, 1),
+        (_sp_desc(192, 256, k=3, algo=2), 0, 0),
+        (_sp_desc(256, 64, k=3, algo=2), 0, 0),
+        (_sp_desc(256, 256, k=3, algo=2, precision=0), 0, 0),
+        (_sp_desc(256, 256, k=3, algo=2, D=10), 0, 0),      # 3-D Winograd
+        (_sp_desc(256, 256, k=3, algo=3), 0, 0),            # fused Winograd: float32 throughout
+    ]
+    for i, (d, fwd, wgrad) in enumerate(table):
+        assert lib.clx_conv_sp_covers(ctypes.byref(d), 0) == fwd, i
+        assert lib.clx_conv_sp_covers(ctypes.byref(d), 1) == wgrad, i
+        d.wplanes = d.aplanes = d.dyplanes = None                # pointers are not part of the answer
+        assert lib.clx_conv_sp_covers(ctypes.byref(d), 0) == fwd, i
+    assert lib.clx_conv_sp_covers(ctypes.byref(_sp_desc(256, 256)), 2) == 0
+
+    # out_planes / out_colsum / aplanes_valid on a call that does not take the split 1x1 product
+    null = ctypes.c_void_p(0)
+    for d in (_sp_desc(256, 256, precision=0), _sp_desc(256, 64), _sp_desc(256, 256, k=3, algo=2)):
+        d.out_planes = 4096
+        with pytest.raises(_clx.ClxError, match="out_planes"):
+            _clx.call("clx_conv_fwd", ctypes.byref(d), null)
+    d = _sp_desc(256, 256, precision=0)
+    d.out_colsum = 4096
+    with pytest.raises(_clx.ClxError, match="out_planes"):
+        _clx.call("clx_conv_fwd", ctypes.byref(d), null)
+    d = _sp_desc(256, 256)
+    d.aplanes_valid = 1
+    d.wplanes = None                              # (no weight planes: the float32 product)
+    with pytest.raises(_clx.ClxError, match="aplanes_valid"):
+        _clx.call("clx_conv_fwd", ctypes.byref(d), null)
+    # dyplanes_valid / aplanes_valid on a weight gradient that does not read the planes
+    for d in (_sp_desc(192, 256), _sp_desc(256, 256, precision=0), _sp_desc(256, 256, k=3, algo=2)):
+        d.dyplanes_valid = 1
+        with pytest.raises(_clx.ClxError, match="dyplanes_valid"):
+            _clx.call("clx_conv_wgrad", ctypes.byref(d), ctypes.c_void_p(4096), 256, ctypes.c_void_p(4096), null, null)
+    d = _sp_desc(256, 256)
+    d.dyplanes = None
+    d.aplanes_valid = 1
+    with pytest.raises(_clx.ClxError, match="aplanes_valid"):
+        _clx.call("clx_conv_wgrad", ctypes.byref(d), ctypes.c_void_p(4096), 256, ctypes.c_void_p(4096), null, null)
+
+    # transform caches: planes where wino_sp holds, float32 elsewhere.  66 x 66 -> 64 x 64 outputs, 16 x 16 tiles of 4 x 4
+    def vcache(d, which):
+        return int(lib.clx_conv_vcache_bytes(ctypes.byref(d), which))
+
+    tiles = 2 * 16 * 16
+    dy_tiles = 2 * 17 * 17                        # the data gradient's (K - 1)-padded grid: 66 x 66 outputs
+    d = _sp_desc(256, 256, hw=(66, 66), k=3, algo=2)
+    assert vcache(d, 0) == 36 * lib.clx_planes_bytes(tiles, 256)
+    assert vcache(d, 1) == 36 * lib.clx_planes_bytes(dy_tiles, 256)
+    for d in (_sp_desc(256, 256, hw=(66, 66), k=3, algo=2, precision=0), _sp_desc(192, 256, hw=(66, 66), k=3, algo=2),
+              _sp_desc(256, 64, hw=(66, 66), k=3, algo=2)):
+        assert vcache(d, 0) == 36 * tiles * d.src[0].C * 4
+        assert vcache(d, 1) == 36 * dy_tiles * d.N * 4
+    d = _sp_desc(256, 256, hw=(66, 66), k=3, algo=2, D=10)          # 3-D: 8 output planes, 10 input planes
+    assert vcache(d, 0) == 36 * 10 * tiles * 256 * 4

@@ -610,6 +610,45 @@ def test_gate_bits_and_dual_dy_transform_change_nothing(device, monkeypatch):
             assert torch.allclose(g, r, rtol=1e-4, atol=1e-5 * r.abs().max().item()), key
 
 
+def test_epilogue_planes_change_nothing_but_the_bias_gradient_order(device, monkeypatch):
+    """CLX_SP_EPILOGUE_PLANES=0: the split 1x1 layers split their operands themselves instead of taking the planes (and,
+    in the backward pass, the bias gradient of the layer behind) from the epilogue of the product before them — the same
+    planes, so the forward is bit-identical and the gradients agree up to the summation order of the bias gradients."""
+    results = {}
+    for flag in ("1", "0"):
+        monkeypatch.setenv("CLX_SP_EPILOGUE_PLANES", flag)
+        _o, model, raw = _make("2d_sp128", device, seed=2)
+        x = raw.to(device)
+        out = model(x)
+        plan = next(iter(model._plans.values()))
+        assert plan._pointwise_reader and all(plan.sp_pass[n] == (True, True, True) for n in plan.xplanes)
+        out.backward(torch.randn(out.shape, generator=torch.Generator().manual_seed(3)).to(device))
+        results[flag] = (out.detach().clone(), [(n, p.grad.clone()) for n, p in model.named_parameters()])
+    assert torch.equal(results["1"][0], results["0"][0])
+    for (n, g), (_n, r) in zip(results["1"][1], results["0"][1]):
+        l2 = ((g - r).norm() / (r.norm() + 1e-30)).item()
+        assert l2 < 1e-5, (n, l2)
+
+
+def test_float32_layers_get_float32_caches_in_the_default_precision(device, monkeypatch):
+    """Winograd layers the split precision does not cover (64 and 192 channels) keep float32 transform caches, sized by
+    clx_conv_vcache_bytes: the training plan takes the same bytes in the default precision as with CLX_PRECISION=f32."""
+    cfg = dict(in_channels=1, out_channels=2, num_fmaps=64, fmap_inc_factor=3, features_in_last_layer=64,
+               downsampling_factors=[[2, 2]], num_spatial_dims=2)
+    arena = {}
+    for precision in ("f32x3bf16", "f32"):
+        monkeypatch.setenv("CLX_PRECISION", precision)
+        torch.manual_seed(7)
+        model = get_model(**cfg).to(device)
+        out = model(torch.rand(2, 1, 76, 84, device=device))
+        out.sum().backward()
+        plan = next(iter(model._plans.values()))
+        assert plan.vcache
+        assert not any(any(s) for s in plan.sp_pass.values())
+        arena[precision] = plan.arena_bytes()
+    assert arena["f32x3bf16"] == arena["f32"]
+
+
 def test_rejects_cpu_tensors():
     from cellulus_amd._clx import ClxError
 
