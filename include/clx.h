@@ -50,8 +50,8 @@ enum clx_profile_kind {
   CLX_PROF_IGEMM_WIDE = 0,   /* conv_igemm_kernel<128,128> */
   CLX_PROF_IGEMM_NARROW = 1, /* conv_igemm_kernel<128,64>  */
   CLX_PROF_WGRAD = 2,        /* conv_wgrad_kernel<...>     */
-  CLX_PROF_GEMM_SP = 3,      /* gemm_sp_kernel: split-precision products (clx_conv_desc.precision = CLX_PREC_F32X3BF16;
-                                FLOPs = the f32-equivalent 2*M*N*K) */
+  CLX_PROF_GEMM_SP = 3,      /* gemm_sp_kernel (and gemm_sp16_kernel, CLX_SP_MFMA=16): split-precision products
+                                (clx_conv_desc.precision = CLX_PREC_F32X3BF16; FLOPs = the f32-equivalent 2*M*N*K) */
   CLX_PROF_WGRAD_SP = 4,     /* wgrad_sp_kernel: the weight gradient of the same precision */
   CLX_PROF_SPLIT_PLANES = 5, /* sp_split_kernel (HBM-bound: no FLOPs) */
   CLX_PROF_CHAIN64 = 6,      /* chain64_fwd / _bwd kernels (fused pairs of 64-channel 1x1 layers) */

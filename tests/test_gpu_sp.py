@@ -53,11 +53,13 @@ def test_planes_are_an_exact_split(rows, K, ld):
 
 
 @pytest.mark.parametrize("kernel", ["tile256", "tile128", "mfma16"])
-@pytest.mark.parametrize("M,N,K,relu", [(256, 128, 128, 0), (1000, 256, 256, 1), (70000, 256, 768, 1), (257, 768, 2304, 0)])
+@pytest.mark.parametrize("M,N,K,relu", [(256, 128, 128, 0), (1000, 256, 256, 1), (70000, 256, 768, 1), (257, 768, 2304, 0),
+                                        (5, 128, 192, 1), (100, 384, 320, 0), (1000, 128, 1088, 1), (100, 256, 1088, 0)])
 def test_product_from_planes_against_float64(M, N, K, relu, kernel, monkeypatch):
     """The three forward kernels on every shape (the library picks by K; the switches are read per launch): 256 x 128 tiles,
     one workgroup per CU (gemm_sp_kernel<0>: K > 1024); 128 x 128 tiles, two per CU (gemm_sp2_kernel: K <= 1024); the opt-in
-    one on v_mfma_f32_16x16x32_bf16 (CLX_SP_MFMA=16): the same products, the same bars"""
+    one on v_mfma_f32_16x16x32_bf16 (CLX_SP_MFMA=16): the same products, the same bars.  K = 192, 320 and 1088 are odd
+    numbers of 64-wide periods (each kernel peels a different last period then); M = 5 and 100 are below one tile."""
     if kernel == "mfma16":
         monkeypatch.setenv("CLX_SP_MFMA", "16")
     else:
