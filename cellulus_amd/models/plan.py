@@ -355,6 +355,7 @@ class UNetPlan:
         self.dyplanes = None        # planes of the dY a 1x1 layer's weight gradient has split, reused by its data gradient
         self.dyplanes2 = None
         self._pointwise_reader = {}
+        self.dx_bufs = {}           # the generic route of the input-image gradient (first_dgrad): scratch, made on first use
         self.buf = {}
         self._alloc()
 
@@ -1386,11 +1387,13 @@ class UNetPlan:
         return op, WINO_TILE[code]
 
     def _compact(self, slot, rows, width):
-        """grow-only scratch for `rows` compact rows of `width` floats"""
+        """grow-only scratch for `rows` compact rows of `width` floats, ZEROED when made: the 1x1 layers write their real
+        channels only, and the pad lanes are read by the next layer (times zero weights) and copied into the dense tensor
+        by the scatter — left as the allocator's memory, a NaN there becomes NaN * 0 = NaN, which a ReLU turns into 0"""
         bufs = self.__dict__.setdefault("_compact_bufs", {})
         b = bufs.get(slot)
         if b is None or b.shape[0] < rows or b.shape[1] != width:
-            b = bufs[slot] = torch.empty((max(rows, 1), width), dtype=torch.float32, device=self.device)
+            b = bufs[slot] = _clx.zeros((max(rows, 1), width), torch.float32, self.device)
         return b
 
     def forward_prefix(self, raw, params, nlayers):
@@ -1576,16 +1579,17 @@ class UNetPlan:
         return out
 
     # ---------------------------------------------------------------- backward
-    def backward(self, dout, params, grads, on_layer_done=None, flat_grad=None):
+    def backward(self, dout, params, grads, on_layer_done=None, flat_grad=None, dx=None):
         """dout: (B, out_channels, *out_spatial) gradient of the loss w.r.t. forward()'s result.
         grads: list aligned with params; every entry is OVERWRITTEN with the gradient.
         flat_grad: the flat buffer the entries of `grads` are views of, if there is one.
         on_layer_done(param_index): called once the kernels that write a layer's weight and bias
         gradient are enqueued (layers finish in reverse forward order: the data-parallel step
-        starts reducing the tail of the flat gradient while the rest is still being computed)."""
+        starts reducing the tail of the flat gradient while the rest is still being computed).
+        dx: contiguous float32 tensor shaped like raw, OVERWRITTEN with the gradient w.r.t. raw (first_dgrad); None: none."""
         st = _clx.stream_ptr(self.device)
         self.zero_gradients(grads, flat_grad)
-        for done, unpack in self.backward_steps(dout, params, grads):
+        for done, unpack in self.backward_steps(dout, params, grads, dx=dx):
             unpack(st)
             if on_layer_done is not None:
                 for i in done:
@@ -1611,12 +1615,46 @@ class UNetPlan:
                 if g is not None:
                     g.zero_()
 
-    def backward_steps(self, dout, params, grads):
+    def first_dgrad(self, layer, dy, w, dx, st):
+        """dx (planar, raw's shape) = the data gradient of the first convolution, from `dy` = gbuf[layer.out] (its
+        pre-activation gradient, the ReLU gate applied by the consumer).  1-4 channels: clx_conv_first_dgrad straight from
+        the torch weight; otherwise (or CLX_FIRST_DGRAD=0) the generic route every other layer takes — the data-gradient
+        convolution (clx_conv_fwd with _dgrad_desc) into pixel-major scratch, then clx_pixel_to_planar.  That route's
+        weight pack and scratch are made here, on first use, and packed on every call."""
+        assert dx.is_contiguous() and dx.dtype == torch.float32 and dx.shape[0] == self.B
+        wv = w.detach()
+        if not wv.is_contiguous():
+            wv = wv.contiguous()
+        OD, OH, OW = layer.out_shape
+        if _first_dgrad_kernel_wanted(layer):
+            _clx.call("clx_conv_first_dgrad", _clx.ptr(dy), dy.shape[1], _clx.ptr(wv), layer.cout, layer.cin, self.B,
+                      OD, OH, OW, layer.kernel[0], _clx.ptr(dx), st)
+            return
+        if not self.dx_bufs:
+            n = self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2]
+            self.dx_bufs["wpack"] = torch.empty(layer.cin_pad * layer.taps * pad4(layer.cout), dtype=torch.float32,
+                                                device=self.device)
+            self.dx_bufs["pixels"] = torch.empty((n, layer.cin_pad), dtype=torch.float32, device=self.device)
+        wp, px = self.dx_bufs["wpack"], self.dx_bufs["pixels"]
+        _clx.call("clx_pack_weights", _clx.ptr(wv), _clx.ptr(wp), layer.cout, layer.cin, layer.taps, layer.cin_pad,
+                  pad4(layer.cout), 1, st)
+        dd = self._dgrad_desc(layer, dy)
+        dd.wpack = wp.data_ptr()
+        dd.mask = None
+        dd.ld_mask = 0
+        dd.out = px.data_ptr()
+        dd.ld_out = layer.cin_pad
+        _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
+        _clx.call("clx_pixel_to_planar", _clx.ptr(px), _clx.ptr(dx), self.B, layer.cin,
+                  layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2], layer.cin_pad, st)
+
+    def backward_steps(self, dout, params, grads, dx=None):
         """The backward pass as a generator, one step per layer (or fused pair) in reverse order.  Each step
         enqueues the layer's weight/bias-gradient kernels — they ADD into self.dwpack and the bias gradients, which
         the caller has zeroed (zero_gradients) — and yields (param_indices, unpack): unpack(stream) enqueues the
         launches that turn the packed weight gradient of those layers into `grads`; the layer's data gradient is
-        enqueued when the generator is resumed.  DualPlan drives two of these on two streams over one accumulator."""
+        enqueued when the generator is resumed.  DualPlan drives two of these on two streams over one accumulator.
+        dx: see backward; the first layer's data gradient is enqueued after its weight gradient."""
         t = self.topo
         st = _clx.stream_ptr(self.device)
         assert self._bwd_ready, "pack_weights(need_dgrad=True) must run before backward"
@@ -1689,6 +1727,8 @@ class UNetPlan:
             yield (layer.param_index,), self._unpack_step(layer, dwp, grads[2 * layer.param_index], wino_w)
             # ---- data gradient
             if layer.param_index == 0:
+                if dx is not None:
+                    self.first_dgrad(layer, dy, params[0], dx, st)
                 continue
             dd = self._dgrad_desc(layer, dy)
             self._set_wpack(dd, self.wpack_dgrad[layer.name])
@@ -1755,6 +1795,12 @@ class UNetPlan:
                         dy_planes_of[prev.out] = other
                     _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
         assert not pending_skip
+
+
+def _first_dgrad_kernel_wanted(layer):
+    """clx_conv_first_dgrad for the input-image gradient of `layer` (the first convolution)?  1-4 input channels, unless
+    CLX_FIRST_DGRAD=0 asks for the generic data-gradient convolution (A/B runs, tests)."""
+    return layer.cin <= 4 and os.environ.get("CLX_FIRST_DGRAD", "1") != "0"
 
 
 def forward_flops(topo, batch):
@@ -1869,12 +1915,15 @@ class DualPlan:
             ev.append(torch.cuda.Event())
         return ev[k]
 
-    def backward(self, dout, params, grads, on_layer_done=None, flat_grad=None):
+    def backward(self, dout, params, grads, on_layer_done=None, flat_grad=None, dx=None):
         dout = dout.contiguous()
         h = self.B // 2
         self.parts[0].zero_gradients(grads, flat_grad)           # the one set of accumulators, on the caller's stream
         main = self._fork()
-        self._backward_halves([dout[:h], dout[h:]], params, grads, on_layer_done, main)
+        # (dx is allocated on the caller's stream before the fork; each half writes its slice on its own stream and the
+        #  join orders both behind the caller)
+        dxs = [dx[:h], dx[h:]] if dx is not None else [None, None]
+        self._backward_halves([dout[:h], dout[h:]], params, grads, on_layer_done, main, dxs=dxs)
         self._join(main)
 
     def train_pass(self, raw, params, grads, flat_grad, loss_fn, after_loss=None, on_layer_done=None):
@@ -1907,12 +1956,12 @@ class DualPlan:
         self._join(main)
         return out
 
-    def _backward_halves(self, douts, params, grads, on_layer_done, main):
+    def _backward_halves(self, douts, params, grads, on_layer_done, main, dxs=(None, None)):
         st_main = _clx.stream_ptr(self.device)
         gens = []
-        for p, s, d in zip(self.parts, self.streams, douts):
+        for p, s, d, dx in zip(self.parts, self.streams, douts, dxs):
             with torch.cuda.stream(s):
-                gens.append(p.backward_steps(d, params, grads))
+                gens.append(p.backward_steps(d, params, grads, dx=dx))
         k = 1
         while True:
             items = []

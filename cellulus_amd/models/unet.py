@@ -56,7 +56,9 @@ class _Backbone(nn.Module):
 
 
 class _UNetFunction(torch.autograd.Function):
-    """autograd glue: one node for the whole network."""
+    """autograd glue: one node for the whole network.  Its backward returns the gradient w.r.t. raw when raw requires
+    grad (plan.first_dgrad) and the parameter gradients of the parameters that require grad; with every parameter frozen
+    the parameter gradients are still computed into the flat buffer and dropped."""
 
     @staticmethod
     def forward(ctx, model, raw, *params):
@@ -66,6 +68,7 @@ class _UNetFunction(torch.autograd.Function):
         ctx.model = model
         ctx.plan = plan
         ctx.params = params
+        ctx.raw_shape = tuple(raw.shape)
         return out
 
     @staticmethod
@@ -82,8 +85,11 @@ class _UNetFunction(torch.autograd.Function):
                 views.append(flat[off:off + g.numel()].view(g.shape))
                 off += g.numel()
             grads = views
-        plan.backward(dout, ctx.params, grads, flat_grad=flat)
-        return (None, None) + tuple(grads)
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = torch.empty(ctx.raw_shape, dtype=torch.float32, device=dout.device)
+        plan.backward(dout, ctx.params, grads, flat_grad=flat, dx=dx)
+        return (None, dx) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
 
 
 def _pointwise_desc(x, B, shape3, cin_p, n):
@@ -526,7 +532,7 @@ class UNetModel(nn.Module):  # type: ignore
     def forward(self, raw):
         if self.mode == "train":
             params = self._ordered_params()
-            if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            if torch.is_grad_enabled() and (raw.requires_grad or any(p.requires_grad for p in params)):
                 self.flatten_parameters()
                 params = self._ordered_params()
                 return _UNetFunction.apply(self, raw, *params)

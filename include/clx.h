@@ -578,6 +578,16 @@ int clx_changed_tiles(const void* workspace, int T, int ID, int IH, int IW, int 
  * same bits (the changed rows of noisy copies never pass through a dense first-layer tensor). */
 int clx_grey_rows(const float* x, int B, int ID, int IH, int IW, int KD, const int* rows, long long n, const float* wpack,
                   const float* bias, int relu, int N, float* out, int ld_out, clx_stream stream);
+/* Data gradient of the first convolution with respect to the raw image: the input gradient of l_conv.0.conv_pass.0,
+ * nn.Conv{2,3}d(in_channels -> num_fmaps, 3) with valid padding (cellulus/models/unet.py:24-51), which autograd leaves in
+ * raw.grad there.  For 1-4 input channels and a 3x3 (KD = 1) or 3x3x3 (KD = 3) kernel:
+ *   dx[b][c][z][y][x] = sum over kz < KD, ky < 3, kx < 3, n < N of w[n][c][kz][ky][kx] * dy[(b, z-kz, y-ky, x-kx)][n]
+ * with the taps outside [0, OD) x [0, OH) x [0, OW) dropped; dx extent D = OD + KD - 1, H = OH + 2, W = OW + 2.
+ * dy: pixel-major [B * OD * OH * OW][ld_dy] (16-byte aligned, ld_dy >= N, ld_dy % 4 == 0; lanes n >= N are not read);
+ * w: the torch parameter (N, cin, KD, 3, 3) as it stands; dx: planar (B, cin, D, H, W), overwritten.  Float32 products and
+ * sums whatever the precision switch; no atomics: the same inputs give the same bits. */
+int clx_conv_first_dgrad(const float* dy, int ld_dy, const float* w, int N, int cin, int B, int OD, int OH, int OW, int KD,
+                         float* dx, clx_stream stream);
 /* dst[r][0..width) = src[rows[r]][0..width) for r < n (row strides ld_src / ld_dst floats; width, strides % 4 == 0,
  * 16-byte aligned bases). */
 int clx_gather_rows(const float* src, int ld_src, const int* rows, long long n, int width, float* dst, int ld_dst,
