@@ -10,6 +10,9 @@ linear interpolation), rejection of all-zero crops (zarr_dataset.py:139-158).
 The pair sampler (`sample_coordinates`, `sample_offsets_within_radius`) follows
 zarr_dataset.py:177-251 call for call on the global numpy RNG, so seeding
 ``np.random`` reproduces the reference's coordinates.
+
+Opt-in (``CLX_DEVICE_AUGMENT=1``): `DeviceCropSource` makes the same crops on the device
+from the same kind of draws (``ZarrDataset.elastic_params`` + ``clx_elastic_crop``).
 """
 
 import math
@@ -164,6 +167,42 @@ class ZarrDataset(IterableDataset):  # type: ignore
         out = np.stack([map_coordinates(ch, coords, order=1, mode=mode, cval=0.0) for ch in data])
         return out.astype(np.float32)
 
+    def elastic_params(self, array_shape, py_rng=random, np_rng=np.random):
+        """The random numbers of one crop, without touching image data: exactly the draws ``_random_crop`` (+
+        ``_elastic_crop``) consume from ``random`` / ``np.random``, in their order, so that the two generators end in the
+        same state as after a host crop.  ``array_shape``: the data set's ``(S, C, *spatial)``.
+
+        Elastic: ``dict(s, angle, scale, grids, u)`` — ``grids`` the ``nd`` jittered control-point grids, ``u`` the
+        ``nd`` uniform numbers behind the placement: ``_elastic_crop`` calls ``random.uniform(0, max(room_d, 0))``, which
+        is ``max(room_d, 0) * random()`` — the draw does not depend on ``room``, so it is taken here and the origin is
+        formed later as ``u_d * max(room_d, 0) - lo_d`` (``clx_elastic_crop`` does, on the device).
+        Plain crop: ``dict(s, offsets)``."""
+        s = py_rng.randint(0, array_shape[0] - 1)
+        if not self.elastic_deform:
+            off = [py_rng.randint(0, n - c) for n, c in zip(array_shape[2:], self.crop_size)]
+            return dict(s=s, offsets=off)
+        _rel0, cp_shape, _mats = self._elastic_ops()
+        angle = py_rng.uniform(0, math.pi / 2)
+        scale = py_rng.uniform(0.9, 1.1)
+        grids = [np_rng.normal(0.0, self.control_point_jitter, size=cp_shape) for _ in range(self.num_spatial_dims)]
+        u = [py_rng.random() for _ in range(self.num_spatial_dims)]
+        return dict(s=s, angle=angle, scale=scale, grids=grids, u=u)
+
+    def pack_params(self, params):
+        """``elastic_params`` results -> the float64 records ``clx_elastic_crop`` reads (include/clx.h), one row per crop."""
+        nd = self.num_spatial_dims
+        rows = []
+        for q in params:
+            if not self.elastic_deform:
+                rows.append(np.asarray([q["s"], *q["offsets"]], dtype=np.float64))
+                continue
+            rot = np.eye(nd)
+            c_, s_ = math.cos(q["angle"]), math.sin(q["angle"])
+            rot[-2:, -2:] = [[c_, -s_], [s_, c_]]          # rotate in the (y, x) plane, as _elastic_crop
+            rows.append(np.concatenate([[float(q["s"])], (rot * q["scale"]).ravel(), np.asarray(q["u"], dtype=np.float64),
+                                        *[np.asarray(g, dtype=np.float64).ravel() for g in q["grids"]]]))
+        return np.ascontiguousarray(np.stack(rows), dtype=np.float64)
+
     def __yield_sample(self):
         """An infinite generator of crops."""
         while True:
@@ -300,3 +339,174 @@ class DevicePairSampler:
                   self.offsets.shape[0], batch_size, self.num_anchors, self.num_refs, self.nd, self.lo, self._hi_c,
                   self.seed, int(step) & 0xFFFFFFFFFFFFFFFF, _clx.stream_ptr(self.device))
         return anchor, reference
+
+
+_AUG_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}     # enum clx_aug_dtype
+
+
+def elastic_crop_on_device(dataset, data, shape, stored_dtype, factor, records, device, out=None, maxima=None):
+    """``clx_elastic_crop`` for ``records`` (``ZarrDataset.pack_params``: a float64 numpy array, or a device tensor of
+    it) on the current stream of ``device``.  ``data``: the device-resident data set of ``shape = (S, C, *spatial)``
+    as a tensor of its bytes, element type ``stored_dtype`` (uint8, uint16 or float32); ``dataset`` supplies the crop
+    size and the augmentation's settings.  Returns ``(raw, maxima)``: ``(B, C, *crop)`` float32 and ``max(raw[b])``."""
+    import ctypes
+
+    import torch
+
+    from .. import _clx
+
+    nd = dataset.num_spatial_dims
+    shape = tuple(int(n) for n in shape)
+    B = int(records.shape[0])
+    if not torch.is_tensor(records):
+        records = np.ascontiguousarray(records, dtype=np.float64)
+        s = records[:, 0]
+        if s.min() < 0 or s.max() >= shape[0]:
+            raise IndexError(f"sample index outside [0, {shape[0]})")
+        records = torch.from_numpy(records).pin_memory().to(device, non_blocking=True)
+    _clx.require_device(records, "records")
+    crop = (ctypes.c_int * nd)(*dataset.crop_size)
+    spatial = (ctypes.c_int * nd)(*shape[2:])
+    if out is None:
+        out = torch.empty((B, shape[1]) + tuple(dataset.crop_size), dtype=torch.float32, device=device)
+    if maxima is None:
+        maxima = torch.empty(B, dtype=torch.float32, device=device)
+    cp_c = mats = work = None
+    if dataset.elastic_deform:
+        cache = getattr(dataset, "_device_elastic_cache", None)
+        if cache is None or cache[0] != device:
+            _rel0, cp_shape, m = dataset._elastic_ops()
+            flat = np.concatenate([np.ascontiguousarray(a, dtype=np.float64).ravel() for a in m])
+            cache = dataset._device_elastic_cache = (device, list(cp_shape), torch.from_numpy(flat).to(device))
+        cp_c = (ctypes.c_int * nd)(*cache[1])
+        mats = cache[2]
+        need = int(_clx.load().clx_elastic_crop_workspace(nd, crop, B))
+        work = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    _clx.call("clx_elastic_crop", _clx.ptr(data), _AUG_DTYPES[np.dtype(stored_dtype)], shape[0], shape[1], nd, spatial,
+              crop, cp_c, float(np.float32(factor)), int(bool(dataset.elastic_deform)), B, _clx.ptr(records),
+              _clx.ptr(mats), _clx.ptr(work), _clx.ptr(out), _clx.ptr(maxima), _clx.stream_ptr(device))
+    return out, maxima
+
+
+class DeviceCropSource:
+    """The crops of ``ZarrDataset`` made on the device (opt-in: ``CLX_DEVICE_AUGMENT=1``): the data set is uploaded once,
+    the random numbers of every crop are drawn on the host (``ZarrDataset.elastic_params``, from private generators), and
+    ``clx_elastic_crop`` builds the deformation field, resamples and takes the maximum of every crop of a batch in one
+    call.  An iterable of ``(raw,)`` batches that are already device tensors: it stands where the DataLoader stands, in
+    front of ``train._DevicePrefetcher``, starts no process, and its kernels run on the stream it is given
+    (``use_stream``: the prefetcher's side stream).
+
+    One batch is kept in flight: a call launches the batch after the one it returns, so the maxima it reads back
+    (one small D2H copy) were written a training step earlier and the host does not wait for the device.
+
+    Empty-crop rule (``np.max(crop) <= 0`` -> draw again, zarr_dataset.py:139-158): the rejected crops of a batch, and
+    only they, get new parameters and are made again until none is left — the host path's distribution.  The host path
+    redraws crop ``b`` before it draws crop ``b + 1``; here a batch is drawn first and its rejects afterwards, so the
+    host's stream ORDER is reproduced only while no crop is rejected.
+
+    ``DeviceCropSource.decide`` tells, without a device, whether a data set can be served (budget
+    ``CLX_DEVICE_AUGMENT_MB``, default 8192; crop within the data set) and why not."""
+
+    SEED_OFFSET = 104729
+
+    @staticmethod
+    def decide(dataset, budget_mb=None):
+        """(True, summary) or (False, reason): never raises what the host loader would not raise."""
+        if budget_mb is None:
+            budget_mb = float(os.environ.get("CLX_DEVICE_AUGMENT_MB", "8192"))
+        container = zarr_io.open(dataset.dataset_config.container_path, "r")
+        arr = container[dataset.dataset_config.dataset_name]
+        shape, dtype = tuple(arr.shape), np.dtype(arr.dtype)
+        if any(n < c for n, c in zip(shape[2:], dataset.crop_size)):
+            return False, (f"crop_size {dataset.crop_size} exceeds the data set's spatial extent {shape[2:]}: "
+                           "the host loader reports it")
+        if dataset.normalization_factor is None and dtype not in _AUG_DTYPES and dtype.kind != "f":
+            return False, f"no automatic normalization for dtype {dtype}: the host loader reports it"
+        itemsize = dtype.itemsize if dtype in _AUG_DTYPES else 4
+        mb = float(np.prod(shape, dtype=np.float64)) * itemsize / 2 ** 20
+        if mb > budget_mb:
+            return False, (f"the data set takes {mb:.0f} MB on the device, over the budget of {budget_mb:.0f} MB "
+                           "(CLX_DEVICE_AUGMENT_MB)")
+        if dataset.elastic_deform:
+            _rel0, cp_shape, _m = dataset._elastic_ops()
+            lds = 8 * (sum(c * p for c, p in zip(dataset.crop_size, cp_shape))
+                       + dataset.num_spatial_dims * (dataset.num_spatial_dims + 1 + int(np.prod(cp_shape))))
+            if lds > 60000:
+                return False, (f"control_point_spacing {dataset.control_point_spacing} gives {cp_shape} control points: "
+                               f"{lds} bytes of LDS per block, over clx_elastic_crop's 60000")
+        return True, f"{mb:.1f} MB {dtype} {shape} resident on the device"
+
+    def __init__(self, dataset, device, batch_size, seed):
+        import torch
+
+        self.dataset = dataset
+        self.device = device
+        self.batch_size = int(batch_size)
+        container = zarr_io.open(dataset.dataset_config.container_path, "r")
+        arr = container[dataset.dataset_config.dataset_name]
+        host = np.ascontiguousarray(arr[...])
+        self.factor = dataset.normalization_factor
+        if self.factor is None:
+            self.factor = default_normalization_factor(host.dtype)
+        if host.dtype not in _AUG_DTYPES:
+            host = host.astype(np.float32)               # what the host path makes of it before it multiplies
+        self.stored_dtype = host.dtype
+        self.shape = tuple(host.shape)
+        self.data = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device)
+        seed = int(seed) + self.SEED_OFFSET
+        self.py_rng = random.Random(seed)
+        self.np_rng = np.random.RandomState(seed % 2 ** 32)
+        self.stream = None
+        self.rejected = 0                                # crops drawn again under the empty-crop rule
+        self._flying = None
+
+    def use_stream(self, stream):
+        self.stream = stream
+
+    def _launch(self, count, out=None, maxima=None):
+        params = [self.dataset.elastic_params(self.shape, self.py_rng, self.np_rng) for _ in range(count)]
+        return elastic_crop_on_device(self.dataset, self.data, self.shape, self.stored_dtype, self.factor,
+                                      self.dataset.pack_params(params), self.device, out, maxima)
+
+    def _start(self):
+        """Launch one batch and the copy of its maxima: (raw, maxima, pinned host maxima, event behind the copy)."""
+        import torch
+
+        raw, maxima = self._launch(self.batch_size)
+        host = torch.empty(self.batch_size, dtype=torch.float32).pin_memory()
+        host.copy_(maxima, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self.device))
+        return raw, maxima, host, done
+
+    def _finish(self, flying):
+        """Wait for a launched batch and make its empty crops again until none is left."""
+        import torch
+
+        raw, maxima, host, done = flying
+        done.synchronize()
+        while True:
+            empty = np.flatnonzero(host.numpy() <= 0.0)
+            if len(empty) == 0:
+                return raw
+            self.rejected += len(empty)
+            for b in empty:
+                self._launch(1, raw[b:b + 1], maxima[b:b + 1])
+            host.copy_(maxima, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        import torch
+
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(self.device)
+        with torch.cuda.stream(self.stream):
+            if self._flying is None:
+                self._flying = self._start()
+            raw = self._finish(self._flying)
+            self._flying = self._start()
+        raw.record_stream(torch.cuda.current_stream(self.device))      # made on self.stream, read by the caller's
+        return (raw,)

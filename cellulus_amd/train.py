@@ -43,7 +43,7 @@ def _require_hip_device(device_str):
     return device
 
 
-def loader_policy(world, num_workers):
+def loader_policy(world, num_workers, device_augment=None):
     """How the input pipeline of ONE rank uses the host (the reference is one process with
     ``num_workers`` loader processes, train.py:38-44).
 
@@ -55,7 +55,11 @@ def loader_policy(world, num_workers):
       that share minus one (the rank's own Python), and the pair coordinates are drawn on the device by
       default (``CLX_DEVICE_PAIRS=0`` keeps the np.random stream): at 8 ranks x 8 crops x 5 steps/s the
       np.random stream alone needed 8 cores PER RANK when numpy drew it (about 1 since libclx restates it), the
-      device sampler 2.5 for crops + augmentation."""
+      device sampler 2.5 for crops + augmentation.
+    * ``CLX_DEVICE_AUGMENT=1`` (opt-in, one rank or many; ``device_augment`` overrides the environment): the crops and
+      their augmentation are made on the device too (``DeviceCropSource``) — no loader process at all, ``num_workers``
+      is ignored, and the pairs come from the device sampler.  ``train()`` asks again with ``device_augment=False``
+      when the data set cannot be served from the device (over ``CLX_DEVICE_AUGMENT_MB``)."""
     try:
         cores = len(os.sched_getaffinity(0))
     except AttributeError:
@@ -64,6 +68,11 @@ def loader_policy(world, num_workers):
     if world > 1 and os.environ.get("LOCAL_WORLD_SIZE", "").isdigit():
         local_world = max(1, min(world, int(os.environ["LOCAL_WORLD_SIZE"])))
     per_rank = max(1, cores // max(local_world, 1))
+    if device_augment is None:
+        device_augment = os.environ.get("CLX_DEVICE_AUGMENT", "0") not in ("", "0")
+    if device_augment:
+        return dict(loader_procs=0, host_cores_per_rank=per_rank, device_pairs=True, device_augment=True,
+                    why=f"CLX_DEVICE_AUGMENT=1: crops, augmentation and pairs on the device; num_workers {int(num_workers)} ignored")
     env = os.environ.get("CLX_DEVICE_PAIRS")
     procs = int(num_workers)
     if world > 1:
@@ -112,7 +121,24 @@ def train(experiment_config):
     # the input pipeline's share of the host: every loader process draws the np.random pair stream of its
     # crops (3 ms of one core per 256^2 crop since libclx restates that stream) next to the zarr reads and the augmentation
     policy = loader_policy(world, train_config.num_workers)
-    if is_main:
+    crop_source = None
+    if policy.get("device_augment"):
+        from .datasets.zarr_dataset import DeviceCropSource
+
+        usable, why = DeviceCropSource.decide(train_dataset)
+        if usable:
+            # private generators, seeded like the pair sampler's: a seeded run is reproducible, ranks draw different crops
+            crop_source = DeviceCropSource(train_dataset, device, train_config.batch_size,
+                                           seed=torch.initial_seed() + 7919 * rank)
+        else:
+            if is_main:
+                print(f"[cellulus_amd] CLX_DEVICE_AUGMENT=1 not used, the loader processes stay: {why}")
+            policy = loader_policy(world, train_config.num_workers, device_augment=False)
+    if is_main and crop_source is not None:
+        print(f"[cellulus_amd] input pipeline: device crop source (DeviceCropSource, clx_elastic_crop: {why}), 0 loader "
+              f"processes per rank, num_workers {train_config.num_workers} ignored ({policy['host_cores_per_rank']} host "
+              f"cores per rank, world size {world}), pair coordinates drawn on the device (clx_sample_pairs) [{policy['why']}]")
+    elif is_main:
         print(f"[cellulus_amd] input pipeline: {policy['loader_procs']} loader processes per rank "
               f"({policy['host_cores_per_rank']} host cores per rank, world size {world}), pair coordinates "
               f"drawn {'on the device (clx_sample_pairs)' if policy['device_pairs'] else 'in the loader processes (np.random, the reference stream)'}"
@@ -126,7 +152,7 @@ def train(experiment_config):
         pair_sampler = DevicePairSampler(train_dataset, device, seed=torch.initial_seed() + 7919 * rank)
 
     # create train dataloader (every rank draws its own random crops)
-    train_dataloader = torch.utils.data.DataLoader(
+    train_dataloader = crop_source if crop_source is not None else torch.utils.data.DataLoader(
         dataset=train_dataset,
         batch_size=train_config.batch_size,
         drop_last=True,
@@ -276,6 +302,8 @@ class _DevicePrefetcher:
         self.it = iter(loader)
         self.device = device
         self.stream = torch.cuda.Stream(device)
+        if hasattr(loader, "use_stream"):        # a DeviceCropSource: its kernels take the place of the H2D copy
+            loader.use_stream(self.stream)
         self.next = None
         self.pair_sampler = pair_sampler
         self.step = first_step

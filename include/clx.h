@@ -651,6 +651,32 @@ size_t clx_ms_bucket_workspace(int n, long long ncells);
 int clx_ms_bucket(const double* fit, int n, int ND, const double* origin, double cell, int nx,
                   int ny, int nz, double* fit_sorted, int* cell_start, void* workspace,
                   clx_stream stream);
+/* A batch of random crops with the elastic augmentation from a data set held on the device: gunpowder's RandomLocation +
+ * Normalize + ElasticAugment(control_point_spacing, jitter_sigma, rotation [0, pi/2], scale [0.9, 1.1]) as the
+ * reference's datasets/zarr_dataset.py:84-131 chains them, with the arithmetic of ZarrDataset._random_crop /
+ * _elastic_crop (the numpy / scipy restatement that runs in the loader processes).  The random numbers are drawn on the
+ * host (ZarrDataset.elastic_params) and arrive in `params`; the deformation field, the placement, the resampling and
+ * the maximum of every crop (the empty-crop rule) are computed here.
+ * data: DEVICE (S, C, *spatial) contiguous, element type `dtype` (enum below); spatial, crop, cp_shape: HOST arrays of nd
+ * ints (cp_shape, mats, workspace may be NULL when elastic = 0); factor: the float32 normalisation factor.
+ * params: DEVICE float64, one record per crop —
+ *   elastic:  [sample index, A = rot * scale (nd x nd, row-major), u_0..u_{nd-1} in [0, 1), nd control-point grids of
+ *              prod(cp_shape) values each]                      (1 + nd * nd + nd + nd * prod(cp_shape) doubles)
+ *   plain:    [sample index, offset_0..offset_{nd-1}]          (1 + nd doubles)
+ * (sample indices and offsets outside the data set are clamped into it, never followed.)
+ * mats: DEVICE float64, axis after axis the (crop_d x cp_shape_d) row-major matrix that up-samples a control-point grid
+ * along axis d.  workspace: DEVICE, clx_elastic_crop_workspace(nd, crop, B) bytes, need not be initialised.
+ * Per voxel, float64:  rel = A . (index - (crop - 1) / 2) + sum_ijk M_0[z][i] M_1[y][j] M_2[x][k] grid_d[i][j][k];
+ * lo / hi = min / max of rel over the crop; room = spatial - 1 - (hi - lo); all room >= 0: mode `constant` (cval 0), else
+ * scipy's `reflect`; coordinate = rel + u * max(room, 0) - lo; value = multilinear interpolation (float64 weights and sums)
+ * of float32(data) * factor, rounded once to float32.  elastic = 0: raw = float32(data[window]) * factor, bit for bit.
+ * raw: (B, C, *crop) float32 out, 16-byte aligned; maxima: B floats out, max(raw[b]).  Two launches (one when
+ * elastic = 0) and one 4 * B byte fill on `stream`; no allocation, no float atomic adds: the same inputs give the same bits. */
+enum clx_aug_dtype { CLX_AUG_U8 = 0, CLX_AUG_U16 = 1, CLX_AUG_F32 = 2 };
+size_t clx_elastic_crop_workspace(int nd, const int* crop, int B);
+int clx_elastic_crop(const void* data, int dtype, int S, int C, int nd, const int* spatial, const int* crop,
+                     const int* cp_shape, float factor, int elastic, int B, const double* params, const double* mats,
+                     void* workspace, float* raw, float* maxima, clx_stream stream);
 /* HOST function: the offsets of the reference's pair sampler (cellulus/datasets/zarr_dataset.py:185-198,
  * sample_offsets_within_radius) drawn from numpy's LEGACY global generator — MT19937, 32-bit outputs, masked rejection,
  * i.e. what `np.random.randint(-radius, radius + 1, size = ND * number_offsets)` called ND times produces — filtered
