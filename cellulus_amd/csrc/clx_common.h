@@ -71,9 +71,9 @@ int clx_wgrad_launch(const clx_conv_desc* d, const float* dy, int ld_dy, float* 
                      int batch, long long bs_x, long long bs_dy, long long bs_out, hipStream_t st);
 // split-precision products (gemm_sp.hip), the rules behind clx_conv_sp_covers — geometry and precision only:
 // the forward / data-gradient product `d` describes — one source read pixel by pixel, 1x1x1 kernel — is one gemm_sp_kernel
-// covers (precision switch set, N % 128 == 0, K % 64 == 0, K >= 128) ...
+// covers (precision switch set, N % 128 == 0 — CLX_PREC_F32X3BF16_G64: N % 64 == 0 and N >= 128 —, K % 64 == 0, K >= 128) ...
 bool clx_sp_fwd_rule(const clx_conv_desc* d);
-// ... the weight gradient of such a layer (both channel counts multiples of 128, operand planes below 4 GB) ...
+// ... the weight gradient of such a layer (both channel counts multiples of 128 — _G64: of 64 and both >= 128 —, operand planes below 4 GB) ...
 bool clx_sp_wgrad_rule(const clx_conv_desc* d);
 // ... and the forward rule with the weight planes supplied
 bool clx_sp_applicable(const clx_conv_desc* d);

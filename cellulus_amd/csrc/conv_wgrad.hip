@@ -505,7 +505,7 @@ extern "C" int clx_conv_wgrad(const clx_conv_desc* d, const float* dy, int ld_dy
   }
   CLX_REQUIRE(d->algo == CLX_ALGO_DIRECT || d->algo == CLX_ALGO_WINOGRAD || d->algo == CLX_ALGO_WINOGRAD4,
               "clx_conv_wgrad: bad algo");
-  // opt-in precision: a 1x1 layer over one plain source, both channel counts multiples of 128 (clx_sp_wgrad_rule) — planes
+  // split precision: a 1x1 layer over one plain source, both channel counts multiples of 128 or, CLX_PREC_F32X3BF16_G64, of 64 (clx_sp_wgrad_rule) — planes
   // of x (left by the forward pass, or split here) and of dY (split here; the bias gradient is that pass's column sums)
   const bool sp = d->algo == CLX_ALGO_DIRECT && d->aplanes != nullptr && d->dyplanes != nullptr && d->det_turns == nullptr &&
                   clx_sp_wgrad_rule(d);

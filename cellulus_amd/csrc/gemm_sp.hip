@@ -29,9 +29,11 @@
 // Three forward / data-gradient kernels share the format, the arithmetic and the epilogue: gemm_sp_kernel<0> (this one: K >
 // 1024), gemm_sp2_kernel (128 x 128 tiles, two workgroups per CU: the default up to K = 1024, i.e. every product of the
 // benchmark networks) and gemm_sp16_kernel (v_mfma_f32_16x16x32_bf16, opt-in); gemm_sp_kernel<1> is the weight gradient.
+// N % 64 == 0 throughout (B's planes hold whole 64-row groups): gemm_sp2_kernel<64> walks N % 128 == 64 in 128 x 64 tiles, the
+// 256 x 128 kernels clamp the row blocks of a half-dead last tile column and mask its stores.
 //
 // Replaces nn.Conv{2,3}d 1x1 (+ReLU) and the transform-domain products of the 3x3 layers, forward and data gradient
-// (cellulus/models/unet.py:24-63, cellulus/train.py:178) when clx_conv_desc.precision = CLX_PREC_F32X3BF16.
+// (cellulus/models/unet.py:24-63, cellulus/train.py:178) when clx_conv_desc.precision = CLX_PREC_F32X3BF16 or _G64.
 #include "clx_common.h"
 #include "sp_planes.h"
 #include <stdlib.h>
@@ -184,6 +186,7 @@ struct SpP {
   float* out;
   int M, N, ksteps;                   // forward: ksteps = K / 16, a multiple of 4.  Weight gradient: M = N of dY (rows of dW), N = C
   int rb_a;                           // 32-row blocks A holds (row blocks past it are clamped: their results are never stored)
+  int rb_b;                           // forward: 32-row blocks B holds (N % 128 == 64: the last 128-wide tile's are clamped the same way)
   const float* bias;
   const float* mask;
   const unsigned int* mask_bits;
@@ -200,17 +203,21 @@ struct SpP {
 
 // The tile's epilogue out of LDS (Cs: [SP_BM][LDC] floats, bias added, written and barrier-synchronised by the caller):
 // previous output, ReLU, gates, masks, the float32 store, the output's own planes, its column sums.
-template <int BM = SP_BM, int NWAVES = 8>
+template <int BM = SP_BM, int NWAVES = 8, int BN = SP_BN>
 __device__ __forceinline__ void sp_epilogue_from_lds(const SpP& p, const float* Cs, int m0, int n0, int batch, int tid, int lane) {
   // A wavefront takes 8 rows x 32 channels per pass (the eight lanes of a row hold one gate word; the float32 stores are
   // 128-byte runs, and so are the stores of every piece of the output's own planes: sp_planes.h); the 8 (4) waves of a pass
-  // cover 16 (8) rows x 128 channels, 16 passes the tile.
-  constexpr int PASS_ROWS = NWAVES / 4 * 8;
-  constexpr int ITERS = BM / PASS_ROWS;                 // 16
+  // cover 16 (8) rows x 128 channels, 16 passes the tile.  A 64-wide tile: two waves side by side, 16 rows per pass of four.
+  // Channels at or past N (the second half of a 128-wide tile over N % 128 == 64) are dead: nothing is read or written for them.
+  constexpr int WPR = BN / 32;                          // waves side by side
+  constexpr int LDC = BN + 4;
+  constexpr int PASS_ROWS = NWAVES / WPR * 8;
+  constexpr int ITERS = BM / PASS_ROWS;                 // 16 (8 for the 128 x 64 tile)
   constexpr int PH = 8;
+  static_assert(ITERS % PH == 0, "whole groups of passes");
   const int wv = tid >> 6;
-  const int c4 = (wv & 3) * 32 + (lane & 7) * 4;
-  const int row0 = (wv >> 2) * 8 + (lane >> 3);
+  const int c4 = (wv % WPR) * 32 + (lane & 7) * 4;
+  const int row0 = (wv / WPR) * 8 + (lane >> 3);
   const int n = n0 + c4;
   const bool n_live = n < p.N;
   f32x4 csum = {0.f, 0.f, 0.f, 0.f};
@@ -261,7 +268,7 @@ __device__ __forceinline__ void sp_epilogue_from_lds(const SpP& p, const float* 
         word |= __shfl_xor(word, 1, 64);
         word |= __shfl_xor(word, 2, 64);
         word |= __shfl_xor(word, 4, 64);
-        if ((lane & 7) == 0 && mrow[j] < p.M && n < p.ld_out) p.gate_out[(size_t)mrow[j] * p.ld_gate + (n >> 5)] = word;
+        if ((lane & 7) == 0 && mrow[j] < p.M && n_live) p.gate_out[(size_t)mrow[j] * p.ld_gate + (n >> 5)] = word;
       }
     }
     if (p.mask) {
@@ -276,7 +283,7 @@ __device__ __forceinline__ void sp_epilogue_from_lds(const SpP& p, const float* 
     }
 #pragma unroll
     for (int j = 0; j < PH; ++j)
-      if (live[j]) *reinterpret_cast<f32x4*>(out_base + (size_t)mrow[j] * p.ld_out) = val[j];      // N % 128 == 0: whole groups
+      if (live[j]) *reinterpret_cast<f32x4*>(out_base + (size_t)mrow[j] * p.ld_out) = val[j];      // N % 64 == 0: whole groups
     if (p.out_planes) {
       // the result as the next product's operand: its three pieces, split here instead of by a pass of its own; the
       // padding rows of the planes (all inside the last tile of rows) as zeros
@@ -357,7 +364,8 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
         return Ab + ((long long)rb * ksteps * 3 + f % 3) * FRAG;
       }
       const int g = f - A_FRAGS;
-      const int nb = tile_n * (SP_BN / 32) + g / 3;
+      int nb = tile_n * (SP_BN / 32) + g / 3;
+      if (nb > p.rb_b - 1) nb = p.rb_b - 1;               // (columns past N: computed, never stored)
       return Bb + ((long long)nb * ksteps * 3 + g % 3) * FRAG;
     } else {
       // 32-channel block cb of an operand = its k steps 2 cb, 2 cb + 1 (both halves): the lane term picks the octet
@@ -367,7 +375,8 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
         return Ab + ((long long)(2 * cb) * 3 + f % 3) * FRAG;
       }
       const int g = f - A_FRAGS;
-      const int cb = tile_n * (SP_BN / 32) + g / 3;
+      int cb = tile_n * (SP_BN / 32) + g / 3;
+      if (cb > p.N / 32 - 1) cb = p.N / 32 - 1;            // (columns of dW past C: computed, never added)
       return Bb + ((long long)(2 * cb) * 3 + g % 3) * FRAG;
     }
   };
@@ -680,7 +689,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
   }
   // ---- epilogue (conv_igemm.hip's): plain products on whole tiles store straight from the accumulators, everything else
   // goes through an LDS transpose so that every lane stores — and reads the optional operands as — 16-byte channel runs
-  if (!p.bias && !p.relu && !p.accumulate && !p.mask && !p.mask_bits && !p.gate_out && !p.out_planes && !p.colsum && m0 + SP_BM <= p.M) {
+  if (!p.bias && !p.relu && !p.accumulate && !p.mask && !p.mask_bits && !p.gate_out && !p.out_planes && !p.colsum && m0 + SP_BM <= p.M && n0 + SP_BN <= p.N) {
     float* const ob = p.out + batch * p.bs_out;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -720,16 +729,30 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
 // CU — one wave of each on every SIMD, 256 registers each — and one's fill and epilogue fall under the other's products.
 // No late half: the two workgroups of a CU are out of phase by themselves.  Costs: 24 KB of operands per 0.52 MFLOP
 // instead of 36 KB per 1.05 (a third more traffic out of L2), six LDS-DMA requests per wave and step instead of 4.5.
-constexpr int S2_BM = 128, S2_BN = 128;
-constexpr int S2_A_FRAGS = S2_BM / 32 * 3, S2_B_FRAGS = S2_BN / 32 * 3;      // 12 + 12
-constexpr int S2_STAGE = (S2_A_FRAGS + S2_B_FRAGS) * FRAG;                   // 24 KB
+//
+// BN = 64: the 128 x 64 tile for N % 128 == 64 (N = 64 above all: a half-empty 128-wide tile does 12 of its 24 MFMAs per step
+// for nothing).  The four waves stay 2 x 2, each 64 x 32: 12 + 6 fragments per stage, a ring of 54 KB, still two workgroups
+// per CU.  Per output element nothing changes — the same steps in the same order, the same six products, periods and
+// signs: the result equals the 128-wide form's bit for bit.  18 fragments over four waves: every wave requests four, and
+// fragments 16 and 17 go to waves 0, 1 in even steps and to waves 2, 3 in odd ones (nine requests per wave and pair of steps,
+// as in gemm_sp_kernel); the counted wait in front of a step allows the 4 or 5 requests of the step behind it.
+constexpr int S2_BM = 128;
+constexpr int S2_A_FRAGS = S2_BM / 32 * 3;                                   // 12
 constexpr int S2_RING = 3;
+template <int BN>
 __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
-  __shared__ __attribute__((aligned(16))) char smem[S2_RING * S2_STAGE];       // 72 KB; the C tile (66 KB) in the epilogue
+  constexpr int S2_BN = BN;
+  constexpr int NJ = BN / 64;                                                // 32-column tiles of a wave
+  constexpr int S2_B_FRAGS = S2_BN / 32 * 3;                                 // 12 (6)
+  constexpr int S2_STAGE = (S2_A_FRAGS + S2_B_FRAGS) * FRAG;                 // 24 KB (18 KB)
+  constexpr int NQ = (S2_A_FRAGS + S2_B_FRAGS) / 4;                          // requests every wave makes in every step: 6 (4)
+  constexpr bool FIFTH = (S2_A_FRAGS + S2_B_FRAGS) % 4 != 0;                 // and two fragments left over
+  constexpr int LDC = BN + 4;
+  __shared__ __attribute__((aligned(16))) char smem[S2_RING * S2_STAGE];       // 72 KB (54 KB); the C tile (66 / 34 KB) in the epilogue
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 1, wn = w & 1;
-  const int nbm = (p.M + S2_BM - 1) / S2_BM, nbn = p.N / S2_BN;
+  const int nbm = (p.M + S2_BM - 1) / S2_BM, nbn = (p.N + S2_BN - 1) / S2_BN;
   const int v = xcd_remap(blockIdx.x, nbm * nbn);
   const int tile_n = v % nbn, tile_m = v / nbn;
   const int batch = blockIdx.y;
@@ -742,33 +765,38 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
   // loads: the 24 fragments of a stage, six per wave (f = w + 4 q): A's twelve, then B's
   const char* const Ab = p.A + batch * p.bs_a;
   const char* const Bb = p.B + batch * p.bs_b;
-  const char* gsrc[6];
-#pragma unroll
-  for (int q = 0; q < 6; ++q) {
-    const int f = w + 4 * q;
+  auto frag_base = [&](int f) __attribute__((always_inline)) -> const char* {
     if (f < S2_A_FRAGS) {
       int rb = tile_m * (S2_BM / 32) + f / 3;
       if (rb > p.rb_a - 1) rb = p.rb_a - 1;
-      gsrc[q] = Ab + ((long long)rb * ksteps * 3 + f % 3) * FRAG;
-    } else {
-      const int g = f - S2_A_FRAGS;
-      const int nb = tile_n * (S2_BN / 32) + g / 3;
-      gsrc[q] = Bb + ((long long)nb * ksteps * 3 + g % 3) * FRAG;
+      return Ab + ((long long)rb * ksteps * 3 + f % 3) * FRAG;
     }
-  }
+    const int g = f - S2_A_FRAGS;
+    int nb = tile_n * (S2_BN / 32) + g / 3;
+    if (nb > p.rb_b - 1) nb = p.rb_b - 1;                 // (columns past N: computed, never stored)
+    return Bb + ((long long)nb * ksteps * 3 + g % 3) * FRAG;
+  };
+  const char* gsrc[NQ + 1];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) gsrc[q] = frag_base(w + 4 * q);
+  gsrc[NQ] = FIFTH ? frag_base(4 * NQ + (w & 1)) : nullptr;
+  const bool low_half = w < 2;
   const unsigned int lane16 = (unsigned int)lane * 16u;
-  auto issue = [&](int t, int slot) __attribute__((always_inline)) {
+  auto issue = [&](int t, int slot, bool odd) __attribute__((always_inline)) {
     char* const dst = smem + slot * S2_STAGE;
     const unsigned int voff = lane16 + (unsigned int)t * KSTEP;
 #pragma unroll
-    for (int q = 0; q < 6; ++q) glds16(gsrc[q] + (size_t)voff, dst + (w + 4 * q) * FRAG);
+    for (int q = 0; q < NQ; ++q) glds16(gsrc[q] + (size_t)voff, dst + (w + 4 * q) * FRAG);
+    if constexpr (FIFTH) {
+      if (low_half != odd) glds16(gsrc[NQ] + (size_t)voff, dst + (4 * NQ + (w & 1)) * FRAG);
+    }
   };
 
-  f32x16 acc[2][2], tot[2][2];
+  f32x16 acc[2][NJ], tot[2][NJ];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; tot[i][j][r] = 0.f; }
   const int li = lane & 31, lh = lane >> 5;
@@ -776,10 +804,10 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
 #pragma unroll
   for (int k = 0; k < S2_RING; ++k) {
     la[k] = k * S2_STAGE + (wm * 2 * 3) * FRAG + lane * 16;
-    lb[k] = k * S2_STAGE + (S2_A_FRAGS + wn * 2 * 3) * FRAG + lane * 16;
+    lb[k] = k * S2_STAGE + (S2_A_FRAGS + wn * NJ * 3) * FRAG + lane * 16;
     asm volatile("" : "+v"(la[k]), "+v"(lb[k]));
   }
-  u32x4 fa[2][3], fb[2][3];
+  u32x4 fa[2][3], fb[NJ][3];
   auto read_frags = [&](int slot) __attribute__((always_inline)) {
     const char* const as = smem + la[slot];
     const char* const bs = smem + lb[slot];
@@ -789,8 +817,10 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
     fb[0][2] = *reinterpret_cast<const u32x4*>(bs + 2 * FRAG);
     fa[0][1] = *reinterpret_cast<const u32x4*>(as + FRAG);
     fb[0][1] = *reinterpret_cast<const u32x4*>(bs + FRAG);
+    if constexpr (NJ == 2) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) fb[1][q] = *reinterpret_cast<const u32x4*>(bs + (3 + q) * FRAG);
+      for (int q = 0; q < 3; ++q) fb[NJ - 1][q] = *reinterpret_cast<const u32x4*>(bs + (3 + q) * FRAG);
+    }
 #pragma unroll
     for (int q = 0; q < 3; ++q) fa[1][q] = *reinterpret_cast<const u32x4*>(as + (3 + q) * FRAG);
   };
@@ -808,7 +838,7 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
     for (int i = 0; i < 2; ++i)
       if (ROW < 0 || ROW == i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         f32x16 c = acc[i][j];
         const bf16x8 a0 = __builtin_bit_cast(bf16x8, fa[i][0]), a1 = __builtin_bit_cast(bf16x8, fa[i][1]),
                      a2 = __builtin_bit_cast(bf16x8, fa[i][2]);
@@ -829,7 +859,7 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         if constexpr (NEG) tot[i][j] -= acc[i][j];
         else tot[i][j] += acc[i][j];
 #pragma unroll
@@ -840,21 +870,26 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
   // step t: this wave's six loads of step t have landed when at most the six of step t + 1 are in flight; behind the barrier
   // the whole stage is in LDS and every wave is past its reads of step t - 1, whose slot takes step t + 2.
   // TAIL: 0 = a step t + 2 exists; 1 = the last but one step; 2 = the last
-  auto step = [&](int t, int slot, auto tail_tag, auto neg_tag) __attribute__((always_inline)) {
+  // (ODD: the step's parity — a period starts at an even step.  The 128 x 64 tile's step t + 1 is five requests for the waves
+  //  that take a left-over fragment in steps of that parity, four for the others: a wave-uniform choice between two waits)
+  auto step = [&](int t, int slot, auto tail_tag, auto neg_tag, auto odd_tag) __attribute__((always_inline)) {
     constexpr int TAIL = decltype(tail_tag)::value;
+    constexpr bool ODD = decltype(odd_tag)::value;
     if constexpr (TAIL == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else if constexpr (!FIFTH) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else if (low_half == ODD) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // the fragment reads in front of the LDS-DMA requests: a wave's ds_reads behind its own global_load_lds return late
     // (gemm_sp16_kernel's stamps), and with a second workgroup on the CU the requests' lead matters less than in
     // gemm_sp_kernel<0> (-DSP2_DMA_FIRST, the other order: -1 ... -7 % on the benchmark shapes)
 #ifdef SP2_DMA_FIRST
-    if constexpr (TAIL == 0) issue(t + 2, slot == 0 ? 2 : slot - 1);
+    if constexpr (TAIL == 0) issue(t + 2, slot == 0 ? 2 : slot - 1, ODD);
     read_frags(slot);
 #else
     read_frags(slot);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TAIL == 0) issue(t + 2, slot == 0 ? 2 : slot - 1);
+    if constexpr (TAIL == 0) issue(t + 2, slot == 0 ? 2 : slot - 1, ODD);
 #endif
     mfma_step(neg_tag, std::integral_constant<int, -1>{});
     __builtin_amdgcn_sched_barrier(0);
@@ -866,14 +901,16 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
   auto period = [&](int t0, int s0, auto neg_tag, auto last_tag) __attribute__((always_inline)) {
     constexpr bool LAST = decltype(last_tag)::value;
     const int s1 = s0 == 2 ? 0 : s0 + 1, s2 = s1 == 2 ? 0 : s1 + 1;
-    step(t0, s0, T0{}, neg_tag);
-    step(t0 + 1, s1, T0{}, neg_tag);
-    if constexpr (LAST) { step(t0 + 2, s2, T1{}, neg_tag); step(t0 + 3, s0, T2{}, neg_tag); }
-    else { step(t0 + 2, s2, T0{}, neg_tag); step(t0 + 3, s0, T0{}, neg_tag); }
+    using EVEN = std::false_type;
+    using ODD = std::true_type;
+    step(t0, s0, T0{}, neg_tag, EVEN{});
+    step(t0 + 1, s1, T0{}, neg_tag, ODD{});
+    if constexpr (LAST) { step(t0 + 2, s2, T1{}, neg_tag, EVEN{}); step(t0 + 3, s0, T2{}, neg_tag, ODD{}); }
+    else { step(t0 + 2, s2, T0{}, neg_tag, EVEN{}); step(t0 + 3, s0, T0{}, neg_tag, ODD{}); }
     flush(neg_tag);
   };
-  issue(0, 0);
-  issue(1, 1);
+  issue(0, 0, false);
+  issue(1, 1, true);
   {
     const int nper = ksteps >> 2;           // K >= 128: at least two periods; signs alternate, starting with +
     int s0 = 0;                             // slot of the period's first step: (4 per) % 3 = per % 3
@@ -887,13 +924,13 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
   }
   if (clk_block) { atomicAdd(&g_sp_clk_ticks[0], clock64() - clk_c0); atomicAdd(&g_sp_clk_ticks[1], wall_clock64() - clk_w0); }
   // ---- epilogue, as gemm_sp_kernel<0>'s
-  if (!p.bias && !p.relu && !p.accumulate && !p.mask && !p.mask_bits && !p.gate_out && !p.out_planes && !p.colsum && m0 + S2_BM <= p.M) {
+  if (!p.bias && !p.relu && !p.accumulate && !p.mask && !p.mask_bits && !p.gate_out && !p.out_planes && !p.colsum && m0 + S2_BM <= p.M && n0 + S2_BN <= p.N) {
     float* const ob = p.out + batch * p.bs_out;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = n0 + (wn * 2 + j) * 32 + li;
+      for (int j = 0; j < NJ; ++j) {
+        const int col = n0 + (wn * NJ + j) * 32 + li;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int row = m0 + (wm * 2 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -905,8 +942,8 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
   __syncthreads();
   float* Cs = reinterpret_cast<float*>(smem);
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = (wn * 2 + j) * 32 + li;
+  for (int j = 0; j < NJ; ++j) {
+    const int col = (wn * NJ + j) * 32 + li;
     const int n = n0 + col;
     const float bv = (p.bias && n < p.N) ? p.bias[n] : 0.f;
 #pragma unroll
@@ -918,7 +955,7 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
       }
   }
   __syncthreads();
-  sp_epilogue_from_lds<S2_BM, 4>(p, Cs, m0, n0, batch, tid, lane);
+  sp_epilogue_from_lds<S2_BM, 4, BN>(p, Cs, m0, n0, batch, tid, lane);
 }
 
 // ---- the forward / data-gradient product on v_mfma_f32_16x16x32_bf16 (opt-in: CLX_SP_MFMA=16) -------------------------------
@@ -1319,19 +1356,29 @@ extern "C" int clx_join_planes(const void* planes, long long rows, int K, float*
 
 // a 1x1 layer over one plain source (no padding, crop or upsampling) in the split precision
 static bool sp_pointwise(const clx_conv_desc* d) {
-  if (d->precision != CLX_PREC_F32X3BF16 || d->nsrc != 1) return false;
+  if ((d->precision != CLX_PREC_F32X3BF16 && d->precision != CLX_PREC_F32X3BF16_G64) || d->nsrc != 1) return false;
   if (d->KD != 1 || d->KH != 1 || d->KW != 1 || d->PD || d->PH || d->PW) return false;
   const clx_src& S = d->src[0];
   if (S.fz != 1 || S.fy != 1 || S.fx != 1 || S.oz || S.oy || S.ox) return false;
   return S.D == d->ID && S.H == d->IH && S.W == d->IW;
 }
 
+// CLX_PREC_F32X3BF16 keeps the channel granule of the 128-wide tiles it arrived with; CLX_PREC_F32X3BF16_G64 takes the
+// 64-row granule of the planes.  N = 64 is EXCLUDED from its rules although the kernels cover it: with one 64-wide tile
+// column the product reads its A planes (6 bytes per element, float32 MFMA reads 4) exactly once for 2 * 64 FLOPs per
+// element — 21 FLOPs per byte: HBM-bound at ~105 TFLOP/s, which is what float32 MFMA reaches there (measured at M = 516128:
+// x1.03 / x0.92 / x0.98 of float32 MFMA at K = 256 / 768 / 1024, inside the spread between rounds; the weight gradient, a
+// quarter of its 256-row tiles live, x0.62 / x0.55 / x0.55: profiles/sp64.txt).
 bool clx_sp_fwd_rule(const clx_conv_desc* d) {
-  return sp_pointwise(d) && d->N % SP_BN == 0 && d->src[0].C % 64 == 0 && d->src[0].C >= 128 && d->ld_out % 4 == 0;
+  if (!sp_pointwise(d)) return false;
+  const bool g64 = d->precision == CLX_PREC_F32X3BF16_G64;
+  return d->N % (g64 ? 64 : SP_BN) == 0 && d->N >= 128 && d->src[0].C % 64 == 0 && d->src[0].C >= 128 && d->ld_out % 4 == 0;
 }
 
 bool clx_sp_wgrad_rule(const clx_conv_desc* d) {
-  if (!sp_pointwise(d) || d->N % 128 != 0 || d->src[0].C % 128 != 0) return false;
+  if (!sp_pointwise(d)) return false;
+  const int granule = d->precision == CLX_PREC_F32X3BF16_G64 ? 64 : 128;
+  if (d->N % granule != 0 || d->src[0].C % granule != 0 || d->N < 128 || d->src[0].C < 128) return false;
   // the weight-gradient product addresses its operand planes with 32-bit offsets
   const long long ch = d->N > d->src[0].C ? d->N : d->src[0].C;
   return (long long)d->B * d->ID * d->IH * d->IW * ch * 6 < (1ll << 32) - (1 << 24);
@@ -1350,7 +1397,8 @@ extern "C" int clx_conv_sp_covers(const clx_conv_desc* d, int pass) {
 // A + b * bs_a / B + b * bs_b (bytes), result at out + b * bs_out (floats)
 int clx_sp_launch(const void* A, const void* B, int M, int N, int K, long long rows_a, int batch, long long bs_a, long long bs_b,
                   long long bs_out, const clx_conv_desc* ep, hipStream_t st) {
-  CLX_REQUIRE(M > 0 && N > 0 && N % SP_BN == 0 && K >= 128 && K % 64 == 0, "clx_gemm_planes: needs N %% 128 == 0, K %% 64 == 0 and K >= 128");
+  CLX_REQUIRE(M > 0 && N > 0 && N % 64 == 0 && K >= 128 && K % 64 == 0,
+              "clx_gemm_planes: needs N %% 64 == 0 (whole 128-wide tiles: N %% 128 == 0), K %% 64 == 0 and K >= 128");
   CLX_REQUIRE(rows_a >= M, "clx_gemm_planes: the A planes hold fewer rows than M");
   SpP p = {};
   p.A = (const char*)A; p.B = (const char*)B;
@@ -1358,6 +1406,7 @@ int clx_sp_launch(const void* A, const void* B, int M, int N, int K, long long r
   p.out = ep->out; p.ld_out = ep->ld_out;
   p.M = M; p.N = N; p.ksteps = K / 16;
   p.rb_a = (int)(sp::padded_rows(rows_a) / 32);
+  p.rb_b = (int)(sp::padded_rows(N) / 32);
   p.bias = ep->bias; p.mask = ep->mask; p.mask_bits = ep->mask_bits; p.gate_out = ep->gate_out;
   p.relu = ep->relu; p.accumulate = ep->accumulate; p.ld_mask = ep->ld_mask; p.ld_mask_bits = ep->ld_mask_bits; p.ld_gate = ep->ld_gate;
   p.zeros = sp_zero_buffer();
@@ -1365,9 +1414,12 @@ int clx_sp_launch(const void* A, const void* B, int M, int N, int K, long long r
   p.out_planes = batch == 1 ? (char*)ep->out_planes : nullptr;
   p.colsum = batch == 1 ? ep->out_colsum : nullptr; p.colsum_n = N;
   CLX_REQUIRE(p.out_planes == nullptr || ep->ld_out == N, "clx_gemm_planes: out_planes needs a dense output (ld_out == N)");
-  p.nbm = cdiv(M, SP_BM); p.nbn = N / SP_BN;
+  p.nbm = cdiv(M, SP_BM); p.nbn = cdiv(N, SP_BN);
   // CLX_SP_TILE=128: gemm_sp2_kernel (128 x 128 tiles, two workgroups per CU) always; =256: never; unset: up to K = 1024
-  // (measured against gemm_sp_kernel<0>: K = 256 +8 ... +22 %, K = 768 0 ... +6 %, K = 2304 -4 %)
+  // (measured against gemm_sp_kernel<0>: K = 256 +8 ... +22 %, K = 768 0 ... +6 %, K = 2304 -4 %).
+  // N % 128 == 64: the same switches choose between the same two kernels.  gemm_sp2_kernel then runs on 128 x 64 tiles
+  // THROUGHOUT (no half-empty tile, one launch, and N = 64 / 192 / 576 are the counts that matter); gemm_sp_kernel<0> keeps its
+  // 256 x 128 tiles with the last tile column half dead (its B row blocks clamped, its stores masked).
   const char* const tile_env = getenv("CLX_SP_TILE");
   const int tile_choice = tile_env != nullptr ? atoi(tile_env) : 0;
   const char* const maxk_env = getenv("CLX_SP_TILE_MAXK");           // (the rule's threshold, for measurements)
@@ -1376,13 +1428,15 @@ int clx_sp_launch(const void* A, const void* B, int M, int N, int K, long long r
   // CLX_SP_MFMA=16: the 16 x 16 x 32 form of the kernel (gemm_sp16_kernel: faster from K ~ 2000 on, slower on the contraction
   // lengths of the benchmark networks, 256 and 768; read per launch so that a test can switch it)
   const char* const shape_env = getenv("CLX_SP_MFMA");
-  const bool mfma16 = shape_env != nullptr && atoi(shape_env) == 16;
+  // (N % 128 == 64: that kernel has no clamped B side — such products fall back to the 32 x 32 x 16 form)
+  const bool mfma16 = shape_env != nullptr && atoi(shape_env) == 16 && N % SP_BN == 0;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   // (gemm_sp16_kernel has the 256 x 128 tiles and the one workgroup per CU of gemm_sp_kernel: it is profiled as that kind)
   if (clx_prof_enabled())
     clx_prof_events(small_tiles && !mfma16 ? CLX_PROF_GEMM_SP2 : CLX_PROF_GEMM_SP, 2.0 * M * N * K * batch, &e0, &e1);
   if (mfma16) CLX_LAUNCH_TIMED(gemm_sp16_kernel, dim3(p.nbm * p.nbn, batch), dim3(512), st, e0, e1, p);
-  else if (small_tiles) CLX_LAUNCH_TIMED(gemm_sp2_kernel, dim3(cdiv(M, S2_BM) * (N / S2_BN), batch), dim3(256), st, e0, e1, p);
+  else if (small_tiles && N % 128 == 0) CLX_LAUNCH_TIMED(gemm_sp2_kernel<128>, dim3(cdiv(M, S2_BM) * (N / 128), batch), dim3(256), st, e0, e1, p);
+  else if (small_tiles) CLX_LAUNCH_TIMED(gemm_sp2_kernel<64>, dim3(cdiv(M, S2_BM) * (N / 64), batch), dim3(256), st, e0, e1, p);
   else CLX_LAUNCH_TIMED(gemm_sp_kernel<0>, dim3(p.nbm * p.nbn, batch), dim3(512), st, e0, e1, p);
   return CLX_OK;
 }
@@ -1390,7 +1444,8 @@ int clx_sp_launch(const void* A, const void* B, int M, int N, int K, long long r
 // dW[b][n][c] += sum_pixels dY[b][pixel][n] x[b][pixel][c] from the planes of dY ([rows][N]) and x ([rows][C]); `batch` problems
 int clx_sp_wgrad_launch(const void* dy_planes, const void* x_planes, long long rows, int N, int C, int batch, long long bs_dy,
                         long long bs_x, long long bs_out, float* dw, int ld_dw, hipStream_t st) {
-  CLX_REQUIRE(rows > 0 && N > 0 && C > 0 && N % 128 == 0 && C % 128 == 0, "clx_wgrad_planes: needs N %% 128 == 0 and C %% 128 == 0");
+  CLX_REQUIRE(rows > 0 && N > 0 && C >= 128 && N % 64 == 0 && C % 64 == 0,
+              "clx_wgrad_planes: needs N %% 64 == 0, C %% 64 == 0 and C >= 128");
   SpP p = {};
   p.A = (const char*)dy_planes; p.B = (const char*)x_planes;
   p.bs_a = bs_dy; p.bs_b = bs_x; p.bs_out = bs_out;
@@ -1399,7 +1454,7 @@ int clx_sp_wgrad_launch(const void* dy_planes, const void* x_planes, long long r
   p.stride_a = (unsigned int)(N / 16) * KSTEP; p.stride_b = (unsigned int)(C / 16) * KSTEP;
   CLX_REQUIRE(sp::planes_bytes(rows, N) < (1ll << 32) && sp::planes_bytes(rows, C) < (1ll << 32), "clx_wgrad_planes: operand planes beyond 4 GB");
   p.total_steps = (int)(sp::padded_rows(rows) / 16);
-  p.nbm = cdiv(N, SP_BM); p.nbn = C / SP_BN;
+  p.nbm = cdiv(N, SP_BM); p.nbn = cdiv(C, SP_BN);        // (both sides clamped: the last tile's dead rows / columns are never added)
   const int tiles = p.nbm * p.nbn * batch;
   // pixel slices: the grid that costs the fewest rounds of co-resident blocks (one per CU), a block's prologue + atomics
   // priced as 12 steps.  A slice is an EVEN number of four-step periods (all but the last one): the periods alternate in

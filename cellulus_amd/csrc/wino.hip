@@ -734,9 +734,15 @@ inline int pad4(int n) { return (n + 3) / 4 * 4; }
 
 // Does this layer's transform-domain arithmetic run in the split precision (clx_conv_desc.precision; gemm_sp.hip)?  ONE
 // rule for the forward, data-gradient and weight-gradient calls of a layer — they hand V and A dY A^T to each other as
-// P3 planes (vcache, dy_vcache, the workspace) —: 2-D layer, both channel counts multiples of 128.
+// P3 planes (vcache, dy_vcache, the workspace) —: 2-D layer, both channel counts multiples of 128
+// (CLX_PREC_F32X3BF16_G64: multiples of 64 and at least 128 — each is the contraction length of one of the three products).
 inline bool wino_sp(const clx_conv_desc* d) {
-  if (d->precision != CLX_PREC_F32X3BF16 || d->KD != 1 || d->ID != 1 || d->N % 128 != 0 || d->src[0].C % 128 != 0) return false;
+  if (d->KD != 1 || d->ID != 1) return false;
+  if (d->precision == CLX_PREC_F32X3BF16_G64) {
+    if (d->N % 64 != 0 || d->src[0].C % 64 != 0 || d->N < 128 || d->src[0].C < 128) return false;
+  } else if (d->precision != CLX_PREC_F32X3BF16 || d->N % 128 != 0 || d->src[0].C % 128 != 0) {
+    return false;
+  }
   // the weight-gradient product addresses its operand planes with 32-bit offsets: one transform point's planes stay below
   // 4 GB (the tiles of the layer's LARGER grid — the data-gradient form's — decide for all three calls)
   const int mt = d->algo == CLX_ALGO_WINOGRAD ? 2 : 4;

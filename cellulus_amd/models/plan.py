@@ -66,22 +66,27 @@ def wino_min_channels(kernel):
 #       per float32 product accumulated in float32 on the bf16 matrix cores (csrc/gemm_sp.hip).  Results
 #       are float32; distance from the float64 oracle at a trained network's output scale 7.2e-5 (float32 MFMA: 7.3e-5).
 #   "f32": float32 MFMA everywhere (v_mfma_f32_32x32x2_f32), the only arithmetic of rounds 1-5; CLX_PRECISION=f32.
+#   "f32x3bf16g64" (opt-in, CLX_PRECISION=f32x3bf16g64): the arithmetic of "f32x3bf16" for channel counts that are multiples
+#       of 64 instead of 128, from 128 channels on (the 192 / 576-channel layers of the 64-feature-map networks).  Which layers that reaches is the library's answer
+#       (clx_conv_sp_covers; include/clx.h), as for the default: this module holds no copy of either rule.
 DEFAULT_PRECISION = "f32x3bf16"
+PRECISION_CODES = {"f32": 0, "f32x3bf16": 1, "f32x3bf16g64": 2}
 
 
 def precision_name() -> str:
     name = os.environ.get("CLX_PRECISION", "") or DEFAULT_PRECISION
-    if name not in ("f32", "f32x3bf16"):
-        raise ValueError(f"CLX_PRECISION must be 'f32' or 'f32x3bf16', got {name!r}")
+    if name not in PRECISION_CODES:
+        raise ValueError(f"CLX_PRECISION must be 'f32', 'f32x3bf16' or 'f32x3bf16g64', got {name!r}")
     return name
 
 
 def precision_code() -> int:
-    """clx_conv_precision: 0 = float32 MFMA, 1 = the three-way bfloat16 split (CLX_PREC_F32X3BF16).  The run-to-run
-    reproducible mode (CLX_DETERMINISTIC=1) exists in float32 only and selects it."""
+    """clx_conv_precision: 0 = float32 MFMA, 1 = the three-way bfloat16 split (CLX_PREC_F32X3BF16), 2 = the same split
+    with the 64-channel granule (CLX_PREC_F32X3BF16_G64).  The run-to-run reproducible mode (CLX_DETERMINISTIC=1) exists
+    in float32 only and selects it."""
     if os.environ.get("CLX_DETERMINISTIC", "0") == "1":
         return 0
-    return 1 if precision_name() == "f32x3bf16" else 0
+    return PRECISION_CODES[precision_name()]
 
 
 def winograd_enabled() -> bool:
@@ -1039,7 +1044,7 @@ class UNetPlan:
         d.workspace = self.workspace.data_ptr()
         d.workspace_bytes = self.workspace.numel() * 4
 
-    # ------------------------------------------------- split precision (CLX_PRECISION=f32x3bf16; csrc/gemm_sp.hip)
+    # ------------------------------------------------- split precision (CLX_PRECISION=f32x3bf16 / f32x3bf16g64; csrc/gemm_sp.hip)
     def arena_bytes(self):
         """device bytes of this plan's own activations and scratch (not the packed weights and their planes, which plans of one
         model share): what a second plan of the same shape on another stream takes"""

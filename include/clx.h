@@ -65,7 +65,7 @@ enum clx_profile_kind {
   CLX_PROF_NOISE_STATS = 13, /* noise_stats kernels */
   CLX_PROF_WINO_FUSED = 14,  /* wino_fused_kernel (CLX_ALGO_WINOGRAD4_FUSED; FLOPs = 2 * a^2 * tiles * N * C executed) */
   CLX_PROF_WINO_TRANSFORM = 15, /* the HBM-bound transform kernels of CLX_ALGO_WINOGRAD / _WINOGRAD4 (no FLOPs) */
-  CLX_PROF_GEMM_SP2 = 16     /* gemm_sp2_kernel: the split-precision product on 128 x 128 tiles, two workgroups per CU (K <= 1024) */
+  CLX_PROF_GEMM_SP2 = 16     /* gemm_sp2_kernel: the split-precision product on 128 x 128 (N % 128 == 64: 128 x 64) tiles, two workgroups per CU (K <= 1024) */
 };
 int clx_profile_enable(int on);
 int clx_profile_read(int kind, double* launches, double* total_ms, double* total_flops);
@@ -169,12 +169,20 @@ typedef struct clx_conv_desc {
    * vcache / accumulate with a list. */
   const int* tile_list;
   int tile_count;
-  /* clx_conv_precision.  CLX_PREC_F32 (0, the default of a zeroed descriptor): float32 MFMA — the reference's arithmetic.
-   * (The Python layer, models/plan.py, defaults to CLX_PREC_F32X3BF16; CLX_PRECISION=f32 selects float32 there.)
+  /* clx_conv_precision.  CLX_PREC_F32 (0): float32 MFMA — the reference's arithmetic.
+   * The default at each layer: this C ABI — CLX_PREC_F32, the value of a zeroed descriptor; the Python layer
+   * (models/plan.py, DEFAULT_PRECISION) — CLX_PREC_F32X3BF16 ("f32x3bf16"; CLX_PRECISION=f32 selects float32 and
+   * CLX_PRECISION=f32x3bf16g64 the wider rules below; CLX_DETERMINISTIC=1 forces float32); bench.py — whatever the Python
+   * layer resolves, unless --precision names one.
    * CLX_PREC_F32X3BF16: where the convolution is a plain matrix product — 1x1 layers, the transform-domain products of the 2-D Winograd layers,
    * forward, data gradient and weight gradient; N % 128 == 0, contraction length % 64 == 0 and >= 128 — the operands
-   * are split exactly into three bfloat16 pieces and six exact products per float32 product are accumulated in float32
-   * on the bf16 matrix cores ("P3 planes" above; csrc/gemm_sp.hip).  Everything else stays on the float32 kernels.
+   * are split exactly into three bfloat16 pieces (each rounded to nearest) and six exact products per float32 product are
+   * accumulated in float32 on the bf16 matrix cores ("P3 planes" above; csrc/gemm_sp.hip).  Everything else stays on the
+   * float32 kernels.
+   * CLX_PREC_F32X3BF16_G64 (opt-in): the same arithmetic, kernels and plane hand-overs under the channel granule of the
+   * planes, 64, instead of the 128 of the first kernels' tiles — the 192 / 320 / 576-channel layers of the 64-feature-map
+   * networks (both channel counts at least 128: N = 64 does not pay and stays float32).  Rules:
+   * clx_conv_sp_covers below.  What CLX_PREC_F32X3BF16 covers, this value covers with the same launches and bits.
    * The planes of the weights come from the caller (wplanes: clx_split_planes of `wpack` seen as [rows][K], K = the
    * product's contraction length — Ctot for a 1x1 layer, KD * C per transform point for a Winograd layer — refreshed
    * whenever wpack is); those of the activations are made by the library: by the Winograd transforms themselves inside
@@ -203,7 +211,7 @@ typedef struct clx_conv_desc {
   float* out_colsum;
 } clx_conv_desc;
 
-enum clx_conv_precision { CLX_PREC_F32 = 0, CLX_PREC_F32X3BF16 = 1 };
+enum clx_conv_precision { CLX_PREC_F32 = 0, CLX_PREC_F32X3BF16 = 1, CLX_PREC_F32X3BF16_G64 = 2 };
 
 enum clx_conv_algo {
   CLX_ALGO_DIRECT = 0,
@@ -271,15 +279,22 @@ size_t clx_planes_bytes(long long rows, int K);
 int clx_split_planes(const float* x, long long ld, long long rows, int K, void* planes, clx_stream stream);
 /* x[rows][ld] <- h0 + h1 + h2 of the planes (exact; tests and diagnostics) */
 int clx_join_planes(const void* planes, long long rows, int K, float* x, long long ld, clx_stream stream);
-/* out[m][n] = act(sum_k A[m][k] B[n][k] + bias[n]) from the P3 planes of A ([M][K]) and B ([N][K]): N % 128 == 0,
- * K % 64 == 0, ld_out % 4 == 0.  The plain-product form of clx_conv_fwd with precision = CLX_PREC_F32X3BF16 (which
- * splits / reuses planes by itself); exported for tests and for callers that keep planes of their own. */
+/* out[m][n] = act(sum_k A[m][k] B[n][k] + bias[n]) from the P3 planes of A ([M][K]) and B ([N][K]): N % 64 == 0,
+ * K % 64 == 0, K >= 128, ld_out % 4 == 0.  The plain-product form of clx_conv_fwd with precision = CLX_PREC_F32X3BF16 /
+ * _G64 (which splits / reuses planes by itself); exported for tests and for callers that keep planes of their own.
+ * Per output element the arithmetic does not depend on N or on the tile: with the same operand rows the N = 64 result equals
+ * columns [0, 64) of the N = 128 one bit for bit.
+ * Environment, read per launch: CLX_SP_TILE=128 — the two-workgroups-per-CU kernel always (128 x 128 tiles; 128 x 64 tiles
+ * throughout where N % 128 == 64), =256 — the 256 x 128 kernel always (N % 128 == 64: its last tile column half dead),
+ * unset — the former up to K = CLX_SP_TILE_MAXK (default 1024), the latter beyond, whatever N;
+ * CLX_SP_MFMA=16 — the 16 x 16 x 32 form of the 256 x 128 kernel for N % 128 == 0 (other N fall back to the 32 x 32 x 16 kernels
+ * above). */
 int clx_gemm_planes(const void* a_planes, const void* b_planes, int M, int N, int K, const float* bias, int relu,
                     float* out, int ld_out, clx_stream stream);
-/* dw[n][c] += sum over rows of dY[row][n] * x[row][c] from the P3 planes of dY ([rows][N]) and x ([rows][C]), N % 128 == 0,
- * C % 128 == 0, rows >= 128: float atomics into the caller's (zeroed or accumulating) dw[N][ld_dw].  The plain-product form
- * of clx_conv_wgrad with precision = CLX_PREC_F32X3BF16 (replaces the autograd weight gradient of nn.Conv{2,3}d,
- * cellulus/train.py:178). */
+/* dw[n][c] += sum over rows of dY[row][n] * x[row][c] from the P3 planes of dY ([rows][N]) and x ([rows][C]), N % 64 == 0,
+ * C % 64 == 0, C >= 128: float atomics into the caller's (zeroed or accumulating) dw[N][ld_dw] (256 x 128 tiles of dW; rows
+ * and columns of a last partial tile are computed and not added).  The plain-product form of clx_conv_wgrad with
+ * precision = CLX_PREC_F32X3BF16 / _G64 (replaces the autograd weight gradient of nn.Conv{2,3}d, cellulus/train.py:178). */
 int clx_wgrad_planes(const void* dy_planes, const void* x_planes, long long rows, int N, int C, float* dw, int ld_dw,
                      clx_stream stream);
 
@@ -293,6 +308,19 @@ int clx_wgrad_planes(const void* dy_planes, const void* x_planes, long long rows
  *   CLX_ALGO_WINOGRAD / _WINOGRAD4, either pass: 2-D layer, N % 128 == 0, C % 128 == 0, one transform point's planes below
  *                           4 GB (forward, data gradient and weight gradient of a layer share V / A dY A^T as planes);
  *   CLX_ALGO_WINOGRAD4_FUSED: 0 (float32 throughout).
+ * precision = CLX_PREC_F32X3BF16_G64 answers by the 64-channel granule instead:
+ *   CLX_ALGO_DIRECT, FWD:   N % 64 == 0, C % 64 == 0, both >= 128 (a data-gradient descriptor has N and C swapped; passes are
+ *                           judged one by one, and with both counts >= 128 a layer's three passes get the same answer);
+ *   CLX_ALGO_DIRECT, WGRAD: N % 64 == 0, C % 64 == 0, both >= 128 and the operand planes below 4 GB;
+ *                           (N = 64 is excluded although the kernels cover it — clx_gemm_planes / clx_wgrad_planes take it —:
+ *                           one 64-wide tile column reads 6-byte planes once for 128 FLOPs per element, HBM-bound at the
+ *                           ~105 TFLOP/s float32 MFMA reaches there, and the weight gradient fills a quarter of its tile
+ *                           rows: measured x0.92 .. x1.03 and x0.55 .. x0.62 of float32 MFMA, profiles/sp64.txt)
+ *   CLX_ALGO_WINOGRAD / _WINOGRAD4, either pass: 2-D layer, both counts % 64 == 0 and >= 128 (each is the contraction
+ *                           length of one of the layer's three products), one transform point's planes below 4 GB;
+ *   3-D Winograd and CLX_ALGO_WINOGRAD4_FUSED: 0.
+ * clx_conv_vcache_bytes, clx_conv_workspace_bytes and the out_planes / aplanes_valid / dyplanes_valid refusals follow the
+ * same answers.  precision = CLX_PREC_F32X3BF16 answers as it always has.
  * The launches still run in float32 where wplanes (or, for a 1x1 layer, aplanes / dyplanes) are missing. */
 int clx_conv_sp_covers(const clx_conv_desc* d, int pass);
 
