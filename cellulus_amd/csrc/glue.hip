@@ -302,6 +302,7 @@ extern "C" int clx_maxpool_bwd(const float* x, const float* y, const float* dy_p
                                int W, int C, int fz, int fy, int fx, clx_stream stream) {
   CLX_REQUIRE(x && y && dy_pool && dx, "clx_maxpool_bwd: null pointer");
   CLX_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "clx_maxpool_bwd: bad extents");
+  CLX_REQUIRE(fz >= 1 && fy >= 1 && fx >= 1, "clx_maxpool_bwd: bad factors");
   CLX_REQUIRE(D % fz == 0 && H % fy == 0 && W % fx == 0, "clx_maxpool_bwd: extent not divisible");
   CLX_REQUIRE(dskip == nullptr || (ld_skip % 4 == 0 && ld_skip >= C), "clx_maxpool_bwd: bad ld_skip");
   const long long total = (long long)B * D * H * W * (C / 4);
@@ -321,6 +322,7 @@ extern "C" int clx_upsample_bwd(const float* dcat, int ld_cat, int coff, int LD,
                                 clx_stream stream) {
   CLX_REQUIRE(dcat && y && dy, "clx_upsample_bwd: null pointer");
   CLX_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "clx_upsample_bwd: bad extents");
+  CLX_REQUIRE(fz >= 1 && fy >= 1 && fx >= 1, "clx_upsample_bwd: bad factors");
   CLX_REQUIRE(ld_cat % 4 == 0 && coff % 4 == 0 && coff + C <= ld_cat, "clx_upsample_bwd: bad ld/coff");
   const long long total = (long long)B * D * H * W * (C / 4);
   CLX_REQUIRE(total < (1ll << 31), "clx_upsample_bwd: tensor too large");
