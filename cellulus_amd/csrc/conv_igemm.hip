@@ -16,18 +16,6 @@
 #include "clx_common.h"
 #include <stdlib.h>
 
-#ifdef IG_STAMP
-// diagnostic build (tools/build_variant.sh ... -DIG_STAMP): per block, wall-clock stamps (100 MHz counter) at start, first
-// MFMA, end of the K loop, end of the block, and the hardware id — read back with clx_debug_stamps
-__device__ unsigned long long g_stamps[8 * 32768];
-extern "C" int clx_debug_stamps(unsigned long long* host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * n) == hipSuccess ? 0 : 1;
-}
-#define STAMP(k) do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 32768) g_stamps[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define STAMP(k) do {} while (0)
-#endif
-
 // Shader clock under load: the middle block of every launch adds the shader-clock ticks (s_memtime) and the 100-MHz wall-clock
 // ticks (s_memrealtime) of its own life to two counters — their ratio is the clock the matrix cores actually ran at
 // (bench.py: roofline.shader_clock_mhz; the 157.3 TFLOP/s peak is 2.4 GHz).  Two atomics per launch.
@@ -54,10 +42,6 @@ extern "C" int clx_profile_clock(double* shader_ticks, double* wall_ticks_100mhz
   }
   return CLX_OK;
 }
-
-#ifndef CLX_FLUSH_FORM
-#define CLX_FLUSH_FORM 0
-#endif
 
 namespace {
 
@@ -133,16 +117,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
   const bool clk_block = blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.y / 2 && threadIdx.x == 0;   // mid-launch
   unsigned long long clk_c0 = 0, clk_w0 = 0;
   if (clk_block) { clk_c0 = clock64(); clk_w0 = wall_clock64(); }
-  STAMP(0);
-#ifdef IG_STAMP
-  if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 32768) {
-    unsigned int hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    unsigned int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    g_stamps[blockIdx.x * 8 + 4] = ((unsigned long long)xcc << 32) | hw;
-  }
-#endif
   const int v = xcd_remap(blockIdx.x, p.nbm * p.nbn);
   const int tile_n = v % p.nbn;
   const int tile_m = v / p.nbn;
@@ -314,7 +288,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
   load_chunk();
   store_chunk(0);
   __syncthreads();
-  STAMP(1);
 
   int buf = 0;
   bool more = advance();
@@ -361,14 +334,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
             //  other tiles back — the static_assert below keeps it that way — and the s_nop covers the rest for the first tile.)
             if (a == 0 && c == 0) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 1" ::: "memory");
 #pragma unroll
-#if CLX_FLUSH_FORM == 1        // four 32-bit instructions per pair (the first version of this flush)
-            for (int r = 0; r < 16; ++r) {
-              float t = tot[a][c][r], x = acc[a][c][r];
-              asm volatile("v_add_f32 %0, %0, %1\n\tv_mov_b32 %1, 0" : "+v"(t), "+v"(x));
-              tot[a][c][r] = t;
-              acc[a][c][r] = x;
-            }
-#else                          // one packed add + one 64-bit move per pair
+            // one packed add + one 64-bit move per pair
             for (int r = 0; r < 16; r += 2) {
               typedef float f32x2 __attribute__((ext_vector_type(2)));
               f32x2 t = {tot[a][c][r], tot[a][c][r + 1]}, x = {acc[a][c][r], acc[a][c][r + 1]};
@@ -376,7 +342,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
               tot[a][c][r] = t[0]; tot[a][c][r + 1] = t[1];
               acc[a][c][r] = x[0]; acc[a][c][r + 1] = x[1];
             }
-#endif
           }
           acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[slot][a][e], bf[slot][c][e], acc[a][c], 0, 0, 0);
         }
@@ -391,9 +356,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
   // vmcnt(<=3) — the B loads then waited for the A loads issued one MFMA group earlier, every
   // chunk.  The last chunk (nothing left to prefetch) runs after the loop.
   load_frags(buf, 0, 0);
-#ifdef IG_STAMP
-  unsigned long long stamp_prev_ = wall_clock64(), stamp_max_ = 0, stamp_min_ = ~0ull;
-#endif
   while (more) {
     load_a();
     load_frags(buf, 1, 1);
@@ -414,15 +376,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
     mfma_group(1);
     __builtin_amdgcn_sched_barrier(0);     // keep the barrier BEHIND the last group: the MFMAs
     __syncthreads();                       // already issued absorb the skew between the waves
-#ifdef IG_STAMP
-    {
-      const unsigned long long now_ = wall_clock64();
-      const unsigned long long dt_ = now_ - stamp_prev_;
-      stamp_prev_ = now_;
-      if (dt_ > stamp_max_) stamp_max_ = dt_;
-      if (dt_ < stamp_min_) stamp_min_ = dt_;
-    }
-#endif
     buf ^= 1;
     load_frags(buf, 0, 0);
     more = advance();
@@ -445,17 +398,13 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
 #pragma unroll
     for (int b = 0; b < TN; ++b) acc[a][b] += tot[a][b];
 
-  STAMP(2);
-#ifdef IG_STAMP
-  if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 32768) g_stamps[blockIdx.x * 8 + 7] = (stamp_max_ << 32) | (stamp_min_ & 0xffffffffull);
-#endif
   // ---- epilogue: bias in registers, transpose through LDS so that every lane stores (and reads the ReLU-gate mask
   // as) 16-byte channel runs of one output pixel.  Written in PHASES over eight rows-of-four at a time — all LDS
   // reads, then each optional operand (previous output, gate bits, float mask) as one batch of loads, then the
   // arithmetic, then the stores: with the options tested inside one loop body the compiler put an s_waitcnt vmcnt(0)
   // behind every optional load (on gfx9 that also waits for the STORES before it) and never had two LDS reads in
   // flight — 3.4-4.9 us of a 43-us tile at K = 256, plus 1.5-5 us for four bias loads waited for one by one
-  // (tools/exp/tile_stamps.py); the bias is now fetched before the K loop.
+  // (per-block wall-clock timestamps of a diagnostic build); the bias is now fetched before the K loop.
   // Plain products (no bias / ReLU / gates / accumulate: the per-xi products of the Winograd layers) on whole tiles
   // leave the accumulators as they are — per register two full 128-byte lines, no LDS round trip, no barriers
   // (+ 1 % on the step.  With bias / ReLU / gate words by ballot / gate bits folded into this path as well the step was
@@ -473,12 +422,10 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
           ob[(size_t)row * p.ld_out + col] = acc[a][b][r];
         }
       }
-    STAMP(3);
     if (clk_block) { atomicAdd(&g_clk_ticks[0], clock64() - clk_c0); atomicAdd(&g_clk_ticks[1], wall_clock64() - clk_w0); }
     return;
   }
   __syncthreads();
-  STAMP(5);
   float* Cs = smem;
 #pragma unroll
   for (int a = 0; a < TM; ++a) {
@@ -493,7 +440,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
     }
   }
   __syncthreads();
-  STAMP(6);
   constexpr int F4_PER_ROW = BN / 4;
   constexpr int ITERS = BM * F4_PER_ROW / 256;
   constexpr int PH = 8;                       // rows-of-four per phase
@@ -581,7 +527,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 3 : 2) void conv_igemm_kernel(const
       }
     }
   }
-  STAMP(3);
   if (clk_block) { atomicAdd(&g_clk_ticks[0], clock64() - clk_c0); atomicAdd(&g_clk_ticks[1], wall_clock64() - clk_w0); }
 }
 

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, (BMN == 128 && BNC == 128) ? 3 : 2) void conv_
   constexpr int B_F4 = BNC / 4, B_RPP = 256 / B_F4, B_PASSES = BKP / B_RPP;
   static_assert(WAVES_M * WAVES_N * KS == 4, "4 waves");
   constexpr int NIT = BKP / 2 / KS;           // k-pairs per wave and chunk
-  static_assert(NIT * KS * 2 == BKP && NIT % 8 == 0 || KS == 1, "k-pairs divide");
+  static_assert((NIT * KS * 2 == BKP && NIT % 8 == 0) || KS == 1, "k-pairs divide");
 
   __shared__ float Ys[2][BKP * BMN];
   __shared__ float Xs[2][BKP * BNC];
@@ -105,7 +105,9 @@ __global__ __launch_bounds__(256, (BMN == 128 && BNC == 128) ? 3 : 2) void conv_
   const int a_row = tid / A_F4, a_col = (tid % A_F4) * 4;
   const int b_row = tid / B_F4, b_col = (tid % B_F4) * 4;
   const int n_g = tile_n * BMN + a_col;       // first of this thread's 4 dy columns
-  const bool n_ok = n_g < p.N;
+  // (never tested: columns past N read into the next row, see below.  The dead comparison stays because without it the
+  //  compiler allocates and schedules the kernel's prologue differently)
+  [[maybe_unused]] const bool n_ok = n_g < p.N;
   const int c_g = tile_c * BNC + b_col;       // first of this thread's 4 input channels
   const bool c_ok = c_g < p.Ctot;
   const int s = (p.nsrc == 2 && c_g >= p.src[0].C) ? 1 : 0;
@@ -127,7 +129,6 @@ __global__ __launch_bounds__(256, (BMN == 128 && BNC == 128) ? 3 : 2) void conv_
   // the descriptor and read as zeros, and a load costs no vector instruction (the 64-bit address + zero-pointer select
   // of the plain form: ~6 per load, on the issue port the MFMAs use).  Columns past N read into the next row: their
   // products land in rows of dW that are never stored.
-  typedef int i32x4_ __attribute__((ext_vector_type(4)));
   int dyoff[A_PASSES];
 #pragma unroll
   for (int j = 0; j < A_PASSES; ++j) dyoff[j] = ((a_row + j * A_RPP) * p.ld_dy + n_g) * 4;

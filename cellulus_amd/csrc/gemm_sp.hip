@@ -39,12 +39,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-// timing-only ablations (tools/build_variant.sh sp<k> gemm_sp.hip -DSP_ABL=<k>; results are wrong; 8 = the products as 16x16x32 MFMAs): 1 = no loads in the K
-// loop, 2 = no barriers / waits, 3 = fragments read once, 4 = no epilogue
-#ifndef SP_ABL
-#define SP_ABL 0
-#endif
-
 // shader clock under load (as conv_igemm.hip): the middle block of every launch adds the shader-clock and 100-MHz wall-clock
 // ticks of its own life to two counters; clx_profile_clock (conv_igemm.hip) adds them to its own
 __device__ unsigned long long g_sp_clk_ticks[2];
@@ -59,15 +53,6 @@ int clx_sp_clock_read(double* shader_ticks, double* wall_ticks, int reset) {
   }
   return CLX_OK;
 }
-
-#ifdef SP16_STAMP
-// diagnostic build (tools/build_variant.sh stamp gemm_sp.hip -DSP16_STAMP): s_memtime stamps of waves 0 and 4 of block 0 around the
-// segments of double steps 16 .. 19 of gemm_sp16_kernel; tools/exp/sp16_stamps.py prints them
-__device__ unsigned long long g_sp16_stamps[2][64];
-extern "C" int clx_sp16_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sp16_stamps), sizeof(unsigned long long) * 128) == hipSuccess ? 0 : 1;
-}
-#endif
 
 namespace {
 
@@ -393,7 +378,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
                                         : (unsigned int)((l_oct >> 1) * KSTEP + (l_oct & 1) * 512 + l_pix * 16);
   const bool low_half = w < 4;
   auto issue = [&](int t, int slot, bool odd) __attribute__((always_inline)) {
-    if (SP_ABL == 1 && t > 2) return;
     char* const dst = smem + slot * STAGE;
     if constexpr (MODE == 0) {
       const unsigned int voff = lane16 + (unsigned int)t * KSTEP;        // (K * 192 bytes per row block: far below 4 GB)
@@ -412,7 +396,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
     }
   };
   // own loads of the step about to be multiplied have landed when at most the two steps behind it are in flight
-  auto wait_two = [&]() __attribute__((always_inline)) { if (SP_ABL != 2) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); };
+  auto wait_two = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); };
   auto wait_one = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); };
 
   f32x16 acc[2][2], tot[2][2];
@@ -458,15 +442,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
   // multiplies while the other talks to memory (MI355X_MICROARCH.md, "Two waves per SIMD", item 9).  (Fragments
   // double-buffered in registers, the textbook answer, do not fit: 128 accumulators + 96 > 256.)
   u32x4 fa[2][3], fb[2][3];               // [tile][piece]
-#if SP_ABL == 6
-  u32x4 sa[2][3], sb[2][3];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { sa[i][q] = u32x4{(unsigned)lane, 1u, 2u, 3u}; sb[i][q] = u32x4{4u, (unsigned)lane, 6u, 7u}; }
-#endif
   auto read_frags = [&](int slot) __attribute__((always_inline)) {
-#if SP_ABL != 3
     const char* const as = smem + la[slot];
     const char* const bs = smem + lb[slot];
     auto rd = [&](const char* ptr) __attribute__((always_inline)) -> u32x4 {
@@ -481,15 +457,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
         return u32x4{l2[0], l2[1], h2[0], h2[1]};
       }
     };
-#if SP_ABL == 5 || SP_ABL == 7          // timing only: a third / two thirds of the fragment reads
-    fa[0][0] = rd(as); fb[0][0] = rd(bs); fb[1][0] = rd(bs + 3 * FRAG); fa[1][0] = rd(as + 3 * FRAG);
-#if SP_ABL == 7
-    fa[0][1] = rd(as + FRAG); fb[0][1] = rd(bs + FRAG); fb[1][1] = rd(bs + 4 * FRAG); fa[1][1] = rd(as + 4 * FRAG);
-#else
-    fa[0][1] = fa[0][0] + 1u; fb[0][1] = fb[0][0] + 1u; fb[1][1] = fb[1][0] + 1u; fa[1][1] = fa[1][0] + 1u;
-#endif
-    fa[0][2] = fa[0][1] + 3u; fb[0][2] = fb[0][1] + 3u; fb[1][2] = fb[1][1] + 3u; fa[1][2] = fa[1][1] + 3u;
-#else
     // (in the order the products consume them: the first MFMA needs a[0][2] and b[0][0] only)
     fa[0][2] = rd(as + 2 * FRAG);
     fb[0][0] = rd(bs);
@@ -501,15 +468,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
     for (int q = 0; q < 3; ++q) fb[1][q] = rd(bs + (3 + q) * FRAG);
 #pragma unroll
     for (int q = 0; q < 3; ++q) fa[1][q] = rd(as + (3 + q) * FRAG);
-#endif
-#endif
   };
-#if SP_ABL == 3
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { fa[i][q] = u32x4{(unsigned)lane, 1u, 2u, 3u}; fb[i][q] = u32x4{4u, (unsigned)lane, 6u, 7u}; }
-#endif
   // the 12 MFMAs of tile row i; NEG: the A fragments negated (in place: they are dead afterwards)
   auto mfma_row = [&](auto i_tag, auto neg_tag) __attribute__((always_inline)) {
     constexpr int i = decltype(i_tag)::value;
@@ -521,37 +480,17 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       f32x16 c = acc[i][j];
-#if SP_ABL == 6
-      if (j == 0) asm volatile("" :: "v"(fa[i][0]), "v"(fa[i][1]), "v"(fa[i][2]), "v"(fb[i][0]), "v"(fb[i][1]), "v"(fb[i][2]));
-      const bf16x8 a0 = __builtin_bit_cast(bf16x8, sa[i][0]), a1 = __builtin_bit_cast(bf16x8, sa[i][1]),
-                   a2 = __builtin_bit_cast(bf16x8, sa[i][2]);
-      const bf16x8 b0 = __builtin_bit_cast(bf16x8, sb[j][0]), b1 = __builtin_bit_cast(bf16x8, sb[j][1]),
-                   b2 = __builtin_bit_cast(bf16x8, sb[j][2]);
-#else
       const bf16x8 a0 = __builtin_bit_cast(bf16x8, fa[i][0]), a1 = __builtin_bit_cast(bf16x8, fa[i][1]),
                    a2 = __builtin_bit_cast(bf16x8, fa[i][2]);
       const bf16x8 b0 = __builtin_bit_cast(bf16x8, fb[j][0]), b1 = __builtin_bit_cast(bf16x8, fb[j][1]),
                    b2 = __builtin_bit_cast(bf16x8, fb[j][2]);
-#endif
       // smallest terms first
-#if SP_ABL == 8                            // timing only: the same FLOPs as pairs of v_mfma_f32_16x16x32_bf16 (the shape the chip
-      {                                    // clocks higher on, profiles/r06_mfma_ceiling_bf16.txt) on the same fragment registers
-        f32x4 lo = {c[0], c[1], c[2], c[3]}, hi = {c[4], c[5], c[6], c[7]};
-#define SP_PAIR(a, b)                                                  \
-        lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, lo, 0, 0, 0); \
-        hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, hi, 0, 0, 0);
-        SP_PAIR(a2, b0) SP_PAIR(a0, b2) SP_PAIR(a1, b1) SP_PAIR(a1, b0) SP_PAIR(a0, b1) SP_PAIR(a0, b0)
-#undef SP_PAIR
-        c[0] = lo[0]; c[1] = lo[1]; c[2] = lo[2]; c[3] = lo[3]; c[4] = hi[0]; c[5] = hi[1]; c[6] = hi[2]; c[7] = hi[3];
-      }
-#else
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
-#endif
       acc[i][j] = c;
     }
   };
@@ -587,7 +526,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
     if constexpr (KIND <= 2) wait_two();
     else if constexpr (KIND == 3) wait_one();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (SP_ABL != 2) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     if constexpr (LATE && !(FIRST && S == 0)) {
       // the second half of the step before this one: the last step of the previous period — opposite sign — in phase 0
       if constexpr (S == 0) { mfma_row(I1{}, std::integral_constant<bool, !NEG>{}); flush(std::integral_constant<bool, !NEG>{}); }
@@ -595,17 +534,11 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
       __builtin_amdgcn_sched_barrier(0);
     }
     // Which goes first behind the barrier, this step's fragment reads or the LDS-DMA requests of step t + 3?  A wave's
-    // ds_reads BEHIND its own global_load_lds return 1000-1800 cycles later than in front of them (gemm_sp16_kernel's stamps).
+    // ds_reads BEHIND its own global_load_lds return 1000-1800 cycles later than in front of them (timestamps in gemm_sp16_kernel).
     // The weight gradient (24 transposing reads per step) gains 25-27 % from reading first (132 -> 168 and 176 -> 220 TFLOP/s
     // on the benchmark's 1x1 layers); the forward product, whose requests' lead is worth more than its 12 plain reads,
-    // loses 2-4 % (-DSP_READS_FIRST / -DSP_DMA_FIRST force one order for both)
-#if defined(SP_READS_FIRST)
-    constexpr bool READS_FIRST = true;
-#elif defined(SP_DMA_FIRST)
-    constexpr bool READS_FIRST = false;
-#else
+    // loses 2-4 % (measured by forcing one order for both)
     constexpr bool READS_FIRST = MODE == 1;
-#endif
     // (the requests BEHIND the first row of products instead: -1 ... -4 % in both modes)
     if constexpr (READS_FIRST) {
       read_frags(S);
@@ -615,9 +548,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
       if constexpr (KIND == 0 || KIND == 1) issue(t0 + S + 3, (S + 3) & 3, ((S + 3) & 1) != 0);
       read_frags(S);
     }
-#ifdef SP_FENCE_READS
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     mfma_row(I0{}, neg_tag);
     if constexpr (!LATE) {
       mfma_row(I1{}, neg_tag);
@@ -668,7 +598,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sp_kernel(const SpP p) {
   else k_loop(std::true_type{});
 
   if (clk_block) { atomicAdd(&g_sp_clk_ticks[0], clock64() - clk_c0); atomicAdd(&g_sp_clk_ticks[1], wall_clock64() - clk_w0); }
-  if (SP_ABL == 4) { if (tot[0][0][0] == 123.f) p.out[0] = tot[1][1][3] + tot[0][1][2] + tot[1][0][1]; return; }
   if constexpr (MODE == 1) {
     // combine: float atomics into out[n][c] — per accumulator register two 128-byte row segments, the full-rate shape
     float* const ob = p.out + batch * p.bs_out;
@@ -881,16 +810,11 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
     else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // the fragment reads in front of the LDS-DMA requests: a wave's ds_reads behind its own global_load_lds return late
-    // (gemm_sp16_kernel's stamps), and with a second workgroup on the CU the requests' lead matters less than in
-    // gemm_sp_kernel<0> (-DSP2_DMA_FIRST, the other order: -1 ... -7 % on the benchmark shapes)
-#ifdef SP2_DMA_FIRST
-    if constexpr (TAIL == 0) issue(t + 2, slot == 0 ? 2 : slot - 1, ODD);
-    read_frags(slot);
-#else
+    // (timestamps in gemm_sp16_kernel), and with a second workgroup on the CU the requests' lead matters less than in
+    // gemm_sp_kernel<0> (the other order: -1 ... -7 % on the benchmark shapes)
     read_frags(slot);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (TAIL == 0) issue(t + 2, slot == 0 ? 2 : slot - 1, ODD);
-#endif
     mfma_step(neg_tag, std::integral_constant<int, -1>{});
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -968,7 +892,8 @@ __global__ __launch_bounds__(256, 2) void gemm_sp2_kernel(const SpP p) {
 // are, a DOUBLE step (two ring stages, 32 k) is multiplied between barriers, and the ring is two double stages.
 // Registers: 64 + 64 accumulators, the A fragments of the double step (4 row groups x 3 pieces: 48) and two of the four
 // column groups of B at a time (2 x 12).  Waves 4-7 run half a double step late, as in gemm_sp_kernel.
-// What the stamps of the diagnostic build (-DSP16_STAMP, tools/exp/sp16_stamps.py) taught:
+// What the timestamps of a diagnostic build (waves 0 and 4 of block 0, around the segments of four double steps; last present
+// in commit 0b1de7a) taught:
 //   * a wave's ds_reads BEHIND its own global_load_lds return 1000-1800 cycles later than in front of them (18 reads: 1050
 //     behind three requests, 570 in front): every segment reads first and requests afterwards;
 //   * back-to-back 16 x 16 x 32 instructions hold the SIMD's vector issue half of the time: the partner wave's 18 ds_read_b128
@@ -984,21 +909,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sp16_kernel(const SpP p) {
   __shared__ __attribute__((aligned(16))) char smem[RING * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef SP16_STAMP
-  __shared__ unsigned long long stamp_lds[2][64];
-  int stamp_n = 0;
-  const bool stamp_wave = blockIdx.x == 0 && blockIdx.y == 0 && (w == 0 || w == 4);
-  auto stamp = [&](int d) __attribute__((always_inline)) {
-    if (stamp_wave && d >= 16 && d < 20) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      if (lane == 0) stamp_lds[w >> 2][stamp_n & 63] = t;
-      ++stamp_n;
-    }
-  };
-#define SP_STAMP(d) stamp(d)
-#else
-#define SP_STAMP(d)
-#endif
   const int wm = w >> 1, wn = w & 1;
   const int v = xcd_remap(blockIdx.x, p.nbm * p.nbn);
   const int tile_n = v % p.nbn, tile_m = v / p.nbn;
@@ -1032,18 +942,13 @@ __global__ __launch_bounds__(512, 1) void gemm_sp16_kernel(const SpP p) {
     ldst_b[q] = sub * STAGE + (A_FRAGS + idx) * FRAG;
   }
   const unsigned int lane16 = (unsigned int)lane * 16u;
-#ifndef SP16_ABL
-#define SP16_ABL 0
-#endif
   auto issue_a = [&](int d, int pair) __attribute__((always_inline)) {
-    if (SP16_ABL == 1 && d > 1) return;
     char* const dst = smem + pair * 2 * STAGE;
     const unsigned int voff = lane16 + (unsigned int)d * (2u * KSTEP);
 #pragma unroll
     for (int q = 0; q < 6; ++q) glds16(gsrc_a[q] + (size_t)voff, dst + ldst_a[q]);
   };
   auto issue_b = [&](int d, int pair) __attribute__((always_inline)) {
-    if (SP16_ABL == 1 && d > 1) return;
     char* const dst = smem + pair * 2 * STAGE;
     const unsigned int voff = lane16 + (unsigned int)d * (2u * KSTEP);
 #pragma unroll
@@ -1095,13 +1000,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sp16_kernel(const SpP p) {
   // instructions lie between two that accumulate into the same registers
   auto mfma_half = [&](auto half_tag, auto buf_tag) __attribute__((always_inline)) {
     constexpr int H = decltype(half_tag)::value, BUF = decltype(buf_tag)::value;
-#if SP16_ABL == 4                           // timing only: no products (the fragments still have to arrive)
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) asm volatile("" :: "v"(fb[BUF][jj][q]), "v"(fa[jj][q]), "v"(fa[2 + jj][q]));
-    return;
-#endif
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // smallest terms first
@@ -1147,27 +1045,20 @@ __global__ __launch_bounds__(512, 1) void gemm_sp16_kernel(const SpP p) {
     constexpr bool A1 = decltype(a1_tag)::value, A2 = decltype(a2_tag)::value;
     if constexpr (A1) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    SP_STAMP(d);                                                  // 0: at OPEN (after the wait for the loads)
-    if (SP16_ABL != 2) __builtin_amdgcn_s_barrier();
-    SP_STAMP(d);                                                  // 1: through OPEN
+    __builtin_amdgcn_s_barrier();
     // (an LDS-DMA instruction costs its wave 60-180 cycles of issue: the half that multiplies first requests afterwards,
     //  so that one wave of every SIMD feeds the matrix pipe while the other talks to memory)
+    // (the sched_barriers between the segments stand in PAIRS on purpose: with one in place of a pair the compiler allocates
+    //  the kernel's registers differently and reorders its ds_read_b128)
     if constexpr (!LATE) {
-#ifndef SP16_NO_PRIO
       __builtin_amdgcn_s_setprio(3);         // an early wave's READS go in front of the late half's products, its products behind
-#endif
       read_a(S);
       read_b(S, H0{}, H0{});
-#ifndef SP16_NO_PRIO
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(0);
-#endif
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 2: reads issued
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // reads issued
       if constexpr (A1) issue_b(d + 1, S ^ 1);
-#ifdef SP16_STAMP
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 3: B requested, fragments in registers
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // B requested
       if constexpr (NEG) negate_a();
       mfma_half(H0{}, H0{});
     } else {
@@ -1176,40 +1067,31 @@ __global__ __launch_bounds__(512, 1) void gemm_sp16_kernel(const SpP p) {
         if constexpr (S == 0) flush(std::integral_constant<bool, !NEG>{});       // (the previous period's last half)
         __builtin_amdgcn_sched_barrier(0);
       }
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 2: products issued
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // products issued
       read_a(S);
       read_b(S, H0{}, H0{});
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 3: reads issued
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // reads issued
       if constexpr (A1) issue_b(d + 1, S ^ 1);
       if constexpr (NEG) negate_a();
     }
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    SP_STAMP(d);                                                  // 4: at MID
-    if (SP16_ABL != 2) __builtin_amdgcn_s_barrier();
-    SP_STAMP(d);                                                  // 5: through MID
+    __builtin_amdgcn_s_barrier();
     if constexpr (!LATE) {
-#ifndef SP16_NO_PRIO
       __builtin_amdgcn_s_setprio(3);
-#endif
       read_b(S, H1{}, H1{});
-#ifndef SP16_NO_PRIO
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(0);
-#endif
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 6: reads issued
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // reads issued
       if constexpr (A2) issue_a(d + 2, S);
-#ifdef SP16_STAMP
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 7: A requested, fragments in registers
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // A requested
       mfma_half(H1{}, H1{});
       if constexpr (S == 1) flush(neg_tag);
     } else {
       mfma_half(H0{}, H0{});
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 6: products issued
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // products issued
       read_b(S, H1{}, H1{});
-      __builtin_amdgcn_sched_barrier(0); SP_STAMP(d); __builtin_amdgcn_sched_barrier(0);      // 7: reads issued
+      __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0);      // reads issued
       if constexpr (A2) issue_a(d + 2, S);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1251,18 +1133,13 @@ __global__ __launch_bounds__(512, 1) void gemm_sp16_kernel(const SpP p) {
   issue_a(1, 1);
   // The late half multiplies FIRST behind every barrier, from registers, while the early half reads; it has to be through
   // its products when the early half's fragments arrive, or the two blocks of products run side by side and the late
-  // half's reads behind them are covered by nothing: priority for its instructions (measured with the stamps of the
+  // half's reads behind them are covered by nothing: priority for its instructions (measured with the timestamps of the
   // diagnostic build: the late half's 48 products took 1650 cycles beside the early half's, its reads 600 more)
-#ifndef SP16_NO_PRIO
   if (w >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   if (w < 4) k_loop(std::false_type{});
   else k_loop(std::true_type{});
   __builtin_amdgcn_s_setprio(0);
 
-#ifdef SP16_STAMP
-  if (stamp_wave && lane < 64) g_sp16_stamps[w >> 2][lane] = lane < stamp_n ? stamp_lds[w >> 2][lane] : 0ull;
-#endif
   if (clk_block) { atomicAdd(&g_sp_clk_ticks[0], clock64() - clk_c0); atomicAdd(&g_sp_clk_ticks[1], wall_clock64() - clk_w0); }
   // ---- epilogue: through the LDS transpose (accumulator register r of lane l: row 4 (l / 16) + r, column l % 16 of its 16 x 16)
   __syncthreads();

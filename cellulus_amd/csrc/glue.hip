@@ -74,7 +74,6 @@ __global__ void maxpool_bwd_window_kernel(const float* __restrict__ x, const flo
                                           int cz, int cy, int cx, float* __restrict__ dxo, int D, int H, int W,
                                           int C4, int fz, int fy, int fx, Dec dcw, uint32_t total) {
   const int C = C4 * 4;
-  const int OD = D / fz, OH = H / fy, OW = W / fx;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     uint32_t win;
     int c4, wx, wy, wz, bi;

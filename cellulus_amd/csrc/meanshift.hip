@@ -231,11 +231,7 @@ __global__ __launch_bounds__(256, BLOCKS) void ms_scatter_kernel(TIn* __restrict
             val[c] = (double)e4[c][e] + (double)co[c];
             if (WB) e4[c][e] = (TIn)val[c];
           }
-#ifdef CLX_SCATTER_NOSTORE      // EXPERIMENT: the pass without its point stores
-          if (((gb >> e) & 1u) && val[0] == 1e300) {
-#else
           if ((gb >> e) & 1u) {
-#endif
 #pragma unroll
             for (int c = 0; c < ND; ++c) Xout[(long long)pos * ND + c] = val[c];
             if (index) index[pos] = (int)(i + e);
@@ -835,10 +831,7 @@ __device__ __forceinline__ void ms_search_2d_multi(const double (&x)[U][2], cons
       arg[u] = ms_ring_search<2>(x[u], cx[u], cy[u], 0, 2, cs, order, cell_start, h, nx, ny, 1);
 }
 
-#ifndef CLX_DENSE_WAVES
-#define CLX_DENSE_WAVES 1
-#endif
-constexpr int DENSE_WAVES = CLX_DENSE_WAVES;          // wave-tiles per block: 1 / 2 / 4 measured 111 / 115 / 116 us at 8192^2
+constexpr int DENSE_WAVES = 1;          // wave-tiles per block: 1 / 2 / 4 measured 111 / 115 / 116 us at 8192^2
 template <int ND, int PXL, int G, int U>
 __global__ __launch_bounds__(64 * DENSE_WAVES) void ms_assign_dense_kernel(
     const double* __restrict__ X, const double* __restrict__ cs, int ncenters, const int* __restrict__ order,

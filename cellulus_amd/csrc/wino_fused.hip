@@ -224,7 +224,6 @@ __global__ __launch_bounds__(512, 1) void wino_fused_kernel(const FusedP p) {
   // (buffer loads: a 32-bit lane offset beside a uniform descriptor and a uniform chunk offset — with plain pointers the
   //  compiler kept the offsets as 64-bit pairs, spilled them, and reloaded them at the top of every chunk behind a
   //  vmcnt(0); a piece outside the image (partial last tiles) gets an offset past the descriptor's range and reads zeros)
-  typedef int i32x4_ __attribute__((ext_vector_type(4)));
   constexpr uint32_t OOB = 0xffffff00u;
   const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)OOB, 0x00020000);
   const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wf), 0, (int)OOB, 0x00020000);
@@ -510,7 +509,6 @@ __global__ __launch_bounds__(512, 1) void wino_pre_kernel(const FusedP p) {
   }
   if (tb >= p.ntb || nb >= p.nnb) return;          // (padding of the grouped order; uniform per block)
   const int t0 = tb * FT;
-  typedef int i32x4_ __attribute__((ext_vector_type(4)));
   constexpr uint32_t OOB = 0xffffff00u;
   // (the slab of one tile block: nchunks * NXI KB, far below 4 GB; the whole Vf may exceed it)
   const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(

@@ -36,6 +36,36 @@ def test_library_exports_every_declared_symbol():
     assert _clx.load().clx_abi_version() == 13
 
 
+def test_kernel_sources_have_no_preprocessor_conditionals():
+    # one source, one library: no -D flag can turn a product kernel into a timing-only one
+    csrc = os.path.join(ROOT, "cellulus_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(names) >= 25
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b")
+    found = [f"{n}:{i}: {line.strip()}" for n in names
+             for i, line in enumerate(open(os.path.join(csrc, n), encoding="utf-8"), 1) if cond.match(line)]
+    assert not found, "\n".join(found)
+
+
+def test_compile_command_ignores_the_environment(monkeypatch):
+    from cellulus_amd import _build
+
+    cmds = []
+
+    def fake_run(cmd, **kwargs):
+        cmds.append(cmd)
+        return subprocess.CompletedProcess(cmd, 0, "", "")
+
+    monkeypatch.setattr(_build.subprocess, "run", fake_run)
+    monkeypatch.setenv("CLX_EXTRA_HIPCC_FLAGS", "-DX")
+    for name in ("meanshift.hip", "gemm_sp.hip"):
+        flags = _build.PER_FILE_FLAGS.get(name, [])
+        src, obj = os.path.join(_build.CSRC, name), os.path.join(_build.OBJ_DIR, name[:-4] + ".o")
+        assert _build._compile_one(("hipcc", src, obj, flags)) == obj
+        assert cmds.pop() == ["hipcc", *_build.COMMON_FLAGS, *flags, "-c", src, "-o", obj]
+    assert _build.PER_FILE_FLAGS["meanshift.hip"] and "gemm_sp.hip" not in _build.PER_FILE_FLAGS
+
+
 def test_argument_validation_without_gpu():
     """Validation happens before any launch, so it is testable on the CPU."""
     from cellulus_amd import _clx

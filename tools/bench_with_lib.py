@@ -1,4 +1,5 @@
-"""python tools/bench_with_lib.py <libclx variant> [bench.py arguments]: bench.py with a variant library (tools/build_variant.sh)."""
+"""python tools/bench_with_lib.py <libclx.so> [bench.py arguments]: bench.py on a library built from another checkout,
+to compare it with this one's."""
 import os, runpy, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cellulus_amd import _clx
