@@ -336,6 +336,7 @@ extern "C" int clx_gather_add_bwd(const float* dsel, const long long* coords, fl
   CLX_REQUIRE(dsel && coords && doffsets, "clx_gather_add_bwd: null pointer");
   CLX_REQUIRE(B > 0 && P >= 0 && (ND == 2 || ND == 3) && Z > 0 && Y > 0 && X > 0,
               "clx_gather_add_bwd: bad extents");
+  CLX_REQUIRE(ND == 3 || Z == 1, "clx_gather_add_bwd: Z must be 1 for 2-D");
   if (P == 0) return CLX_OK;
   const long long total = (long long)B * P;
   gather_add_bwd_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
@@ -367,6 +368,7 @@ extern "C" int clx_oce_pairs_fused(const float* offsets, const long long* anchor
   CLX_REQUIRE(offsets && anchor && reference && doffsets && sums, "clx_oce_pairs_fused: null pointer");
   CLX_REQUIRE(B > 0 && P >= 0 && (ND == 2 || ND == 3) && Z > 0 && Y > 0 && X > 0,
               "clx_oce_pairs_fused: bad extents");
+  CLX_REQUIRE(ND == 3 || Z == 1, "clx_oce_pairs_fused: Z must be 1 for 2-D");
   CLX_REQUIRE(temperature != 0.f, "clx_oce_pairs_fused: temperature must be non-zero");
   if (P == 0) return CLX_OK;
   const long long total = (long long)B * P, npix = (long long)Z * Y * X;

@@ -476,12 +476,12 @@ int clx_upsample_bwd(const float* dcat, int ld_cat, int coff, int LD, int LH,
  * indexes the LAST spatial axis.  Index rules of the reference's advanced indexing: -n..-1
  * wrap around, anything else outside [0, n) is an IndexError there; here such a row is never
  * dereferenced, its selection is NaN and *oob_count (device int, zeroed by the caller, may be
- * NULL) counts it so that the host can raise. */
+ * NULL) counts it so that the host can raise.  Z must be 1 when ND == 2. */
 int clx_gather_add_fwd(const float* offsets, const long long* coords, float* sel,
                        int B, int P, int ND, int Z, int Y, int X, int* oob_count,
                        clx_stream stream);
 /* doffsets[b][c][coord] += dsel[b][p][c]  (float atomics; zero doffsets first); out-of-range
- * rows are skipped and counted as above */
+ * rows are skipped and counted as above.  As for the forward call, Z must be 1 when ND == 2. */
 int clx_gather_add_bwd(const float* dsel, const long long* coords, float* doffsets,
                        int B, int P, int ND, int Z, int Y, int X, int* oob_count,
                        clx_stream stream);
@@ -499,7 +499,8 @@ int clx_oce_loss_fwd_bwd(const float* a, const float* r, float* da, double* sums
  * the caller). Equivalent to the three calls above composed as in
  * cellulus/train.py:170-178.  sums: FOUR doubles, zeroed by the caller: (loss, oce, reg) and
  * the number of pairs with an out-of-range coordinate (skipped, never dereferenced; the
- * reference raises IndexError there, so must the caller when sums[3] != 0). */
+ * reference raises IndexError there, so must the caller when sums[3] != 0).  A pair counts once, whether
+ * one of its coordinates is out of range or both.  Z must be 1 when ND == 2. */
 int clx_oce_pairs_fused(const float* offsets, const long long* anchor,
                         const long long* reference, float* doffsets, double* sums,
                         int B, int P, int ND, int Z, int Y, int X,
