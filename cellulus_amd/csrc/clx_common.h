@@ -58,6 +58,10 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// geometry of a convolution descriptor (conv_igemm.hip): nsrc, extents, kernel 1..3, padding < kernel, input >= kernel,
+// per source channels / ld / alignment / factors / crop / "covers the logical input", M < 2^31.  `who` prefixes the message.
+int clx_conv_validate(const clx_conv_desc* d, const char* who);
+
 // small-channel (first layer) convolution path, conv_smallc.hip
 bool clx_smallc_applicable(const clx_conv_desc* d);
 int clx_smallc_fwd(const clx_conv_desc* d, hipStream_t st);

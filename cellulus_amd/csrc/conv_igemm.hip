@@ -545,7 +545,8 @@ static const float* zero_buffer() {
   return cache[dev];
 }
 
-static int conv_validate(const clx_conv_desc* d, const char* who) {
+// the geometry of a descriptor, checked by clx_conv_fwd and clx_conv_wgrad alike before any dispatch
+int clx_conv_validate(const clx_conv_desc* d, const char* who) {
   CLX_REQUIRE(d != nullptr, "%s: null descriptor", who);
   CLX_REQUIRE(d->nsrc == 1 || d->nsrc == 2, "%s: nsrc must be 1 or 2", who);
   CLX_REQUIRE(d->B > 0 && d->ID > 0 && d->IH > 0 && d->IW > 0, "%s: bad extent", who);
@@ -601,7 +602,7 @@ static void fill_params(const clx_conv_desc* d, ConvP& p) {
 }
 
 extern "C" int clx_conv_fwd(const clx_conv_desc* d, clx_stream stream) {
-  int rc = conv_validate(d, "clx_conv_fwd");
+  int rc = clx_conv_validate(d, "clx_conv_fwd");
   if (rc) return rc;
   CLX_REQUIRE(d->wpack && d->out, "clx_conv_fwd: null wpack/out");
   CLX_REQUIRE(d->N > 0 && d->ld_out >= d->N, "clx_conv_fwd: bad N/ld_out");

@@ -490,7 +490,11 @@ int clx_wgrad_launch(const clx_conv_desc* d, const float* dy, int ld_dy, float* 
 extern "C" int clx_conv_wgrad(const clx_conv_desc* d, const float* dy, int ld_dy,
                               float* dwpack, float* dbias, clx_stream stream) {
   CLX_REQUIRE(d && dy && dwpack, "clx_conv_wgrad: null pointer");
-  CLX_REQUIRE(d->nsrc == 1 || d->nsrc == 2, "clx_conv_wgrad: nsrc must be 1 or 2");
+  // the geometry checks of clx_conv_fwd, for every algo: no route below sizes a grid or reads a source unchecked
+  {
+    const int rc = clx_conv_validate(d, "clx_conv_wgrad");
+    if (rc) return rc;
+  }
   CLX_REQUIRE(d->N > 0 && d->N % 4 == 0 && ld_dy % 4 == 0 && ld_dy >= d->N,
               "clx_conv_wgrad: N and ld_dy must be multiples of 4 (N=%d ld_dy=%d)", d->N, ld_dy);
   CLX_REQUIRE(((uintptr_t)dy & 15) == 0, "clx_conv_wgrad: dy must be 16-byte aligned");

@@ -365,7 +365,10 @@ int clx_chain64_bwd(const float* dp2, int ld_dp2, int N2, const float* y1, int l
  * wpack ignored): dwpack[tap][n][c] += sum_p dy[p][n] * in[p (+) tap][c],
  * dbias[n] += sum_p dy[p][n]  (dbias may be NULL).  Both outputs are
  * ACCUMULATED with float atomics (split-K): zero them first.
- * dy: [M][ld_dy] gradient w.r.t. the pre-activation output. */
+ * dy: [M][ld_dy] gradient w.r.t. the pre-activation output.
+ * Validates the descriptor like clx_conv_fwd (extents, kernel 1..3, padding < kernel, input >= kernel, every
+ * source's channels / ld / alignment / factors / crop and that it covers the logical input, M < 2^31) before any
+ * dispatch, whatever the algo: a descriptor clx_conv_fwd refuses is refused here with the same message. */
 int clx_conv_wgrad(const clx_conv_desc* d, const float* dy, int ld_dy,
                    float* dwpack, float* dbias, clx_stream stream);
 
