@@ -36,7 +36,6 @@ def pad4(c: int) -> int:
 WINO_MIN_CHANNELS = int(os.environ.get("CLX_WINOGRAD_MIN_CHANNELS", "64"))
 # per-layer algorithm code = clx_conv_algo: 0 direct, 1 Winograd F(2x2), 2 Winograd F(4x4)
 # (3 = F(4x4) with the transforms inside the product kernel, forward only: clx_conv_algo CLX_ALGO_WINOGRAD4_FUSED)
-WINO_TAPS = {1: 16, 2: 36, 3: 36}
 WINO_PACK_FWD = {1: 2, 2: 4, 3: 7}  # clx_pack_mode
 WINO_PACK_DGRAD = {1: 3, 2: 5}
 WINO_TILE = {1: 2, 2: 4, 3: 4}
@@ -52,8 +51,25 @@ def winograd_code() -> int:
 
 
 def wino_taps(code, kernel):
-    """packed-weight / weight-gradient planes of a Winograd layer: a^2 transform points x z taps."""
-    return WINO_TAPS[code] * kernel[0]
+    """packed-weight / weight-gradient planes of a Winograd layer: a^2 transform points x z taps, a = tile + k - 1
+    (F(2x2, 3x3): 16, F(4x4, 3x3): 36, the F(4x4, 2x2) of a sub-pixel layer's low-resolution half: 25)."""
+    return (WINO_TILE[code] + kernel[1] - 1) ** 2 * kernel[0]
+
+
+def packed_taps(code, kernel):
+    """planes of the packed weights (or of the packed weight gradient) of a layer that runs with algorithm `code`"""
+    return wino_taps(code, kernel) if code else kernel[0] * kernel[1] * kernel[2]
+
+
+def pack_job_elements(cout, cin, taps, cin_pad, cout_pad, mode):
+    """elements one packing writes (the arguments of clx_pack_weights behind the two pointers): clx_pack_weights_batch
+    sizes its grid by the biggest job of the table"""
+    if mode in (0, 1):
+        return (cout if mode == 0 else cin_pad) * taps * (cin_pad if mode == 0 else cout_pad)
+    if mode == 7:
+        return cout_pad * cin_pad
+    rows, cols = (cin_pad, cout_pad) if mode in (3, 5, 6) else (cout_pad, cin_pad)
+    return rows * (3 if taps == 27 else 2 if taps == 8 else 1) * cols
 
 
 def wino_min_channels(kernel):
@@ -336,6 +352,78 @@ def find_chain_pairs(topo, algo_fwd, batch):
     return pairs
 
 
+def conv_src(ptr, C, ld, shape, crop=(0, 0, 0), factor=(1, 1, 1)):
+    """clx_src: a stored tensor (C of its ld channels, extent `shape`) seen through crop and nearest upsampling"""
+    s = ClxSrc()
+    s.ptr, s.C, s.ld = ptr, C, ld
+    s.D, s.H, s.W = shape
+    s.oz, s.oy, s.ox = crop
+    s.fz, s.fy, s.fx = factor
+    return s
+
+
+def conv_desc(sources, B, in_shape, kernel, pad, N, precision, c_real=0):
+    """clx_conv_desc of a convolution over `sources`.  What is not named here is what a fresh structure holds, zero and
+    NULL: no bias, ReLU, mask or accumulation, the direct algorithm, no workspace — the caller sets what it uses."""
+    d = ClxConvDesc()
+    d.nsrc = len(sources)
+    for i, s in enumerate(sources):
+        d.src[i] = s
+    d.B = B
+    d.ID, d.IH, d.IW = in_shape
+    d.KD, d.KH, d.KW = kernel
+    d.PD, d.PH, d.PW = pad
+    d.N = N
+    d.precision = precision
+    d.c_real = c_real
+    return d
+
+
+@dataclass(eq=False)
+class SubpixelHalf:
+    """One of the two convolutions a sub-pixel layer runs as — 3x3 over the skip tensor, 2x2 over the low-resolution
+    tensor — as allocation, packing, the weight gradient and the sharing between plans see it: weights (rows, C, taps),
+    packed as (rows_pad, packed_taps, Cp)."""
+
+    rows: int                        # output channels of the weights ...
+    rows_pad: int                    # ... and of their packed form
+    C: int                           # input channels, and padded
+    Cp: int
+    kernel: Tuple[int, int, int]
+    wino: int = 0                    # algorithm code of the forward pass and the weight gradient ...
+    wino_dgrad: int = 0              # ... and of the data gradient
+    fused: bool = False              # forward pass in the one-launch form (wino_fused.hip)
+    w: torch.Tensor = None           # weights (written by clx_subpixel_split_weights)
+    wp_fwd: torch.Tensor = None      # packed for the forward pass / for the data gradient
+    wp_dgrad: torch.Tensor = None
+    dw: torch.Tensor = None          # packed weight gradient: a slice of the plan's dwpack
+    g: torch.Tensor = None           # weight gradient, unpacked (read by clx_subpixel_fold_grads)
+    vcache: torch.Tensor = None      # transformed input, kept by the forward pass for the weight gradient ...
+    v_fresh: bool = False            # ... and written by the last forward pass
+
+    @property
+    def taps(self):
+        return self.kernel[0] * self.kernel[1] * self.kernel[2]
+
+
+@dataclass(eq=False)
+class Subpixel:
+    """Geometry of the sub-pixel form of a convolution over cat(skip, nearest-upsample(low)) (_subpixel_geometry)."""
+
+    fac: Tuple[int, int, int]        # upsampling factor, P = its product: the phases
+    P: int
+    N: int                           # padded output channels of the layer; the low half computes P * N
+    zshape: Tuple[int, int, int]     # extent of the low half's output Z, stored in buf[zname]
+    zname: str
+    level: int
+    skip: SubpixelHalf
+    low: SubpixelHalf
+
+    @property
+    def halves(self):
+        return self.skip, self.low
+
+
 class UNetPlan:
     """Executes a Topology for a fixed batch size on one HIP device."""
 
@@ -389,9 +477,8 @@ class UNetPlan:
                     and (layer.kernel[0] == 1 or winograd_code() == 2)):
                 lib = _clx.load()
                 code = winograd_code()
-                d = self._desc(layer)
+                d = self._desc(layer, layer.cout)
                 d.algo = code
-                d.N = layer.cout
                 nf = int(lib.clx_conv_workspace_bytes(ctypes.byref(d), 0))
                 if nf:
                     a["fwd"], ws_bytes = code, max(ws_bytes, nf)
@@ -413,73 +500,65 @@ class UNetPlan:
         # sub-pixel form of the convolutions that read a nearest-upsampled tensor
         self.subpixel = {}
         for info in t.r_info:
-            sp = self._subpixel_geometry(info["conv0"])
-            if sp is not None:
-                self.subpixel[info["conv0"].name] = sp
-                n = self.B * sp["zshape"][0] * sp["zshape"][1] * sp["zshape"][2]
-                self.buf[sp["zname"]] = _clx.zeros((n, sp["P"] * sp["N"]), torch.float32, self.device)
-                # the 2x2 convolution over the low-res tensor as Winograd F(4x4, 2x2)
-                sp["wino"] = 0
-                sp["fused_z"] = sp["fused_skip"] = False    # forward halves in the one-launch form (wino_fused.hip)
-                if (winograd_enabled() and winograd_code() == 2 and sp["zk"] in ((1, 2, 2), (2, 2, 2))
-                        and min(sp["C1p"], sp["P"] * sp["N"]) >= wino_min_channels(sp["zk"])):
-                    lib = _clx.load()
-                    dz, _ds = self._sp_descs(info["conv0"], sp)
-                    dz.algo = 2
-                    need = [int(lib.clx_conv_workspace_bytes(ctypes.byref(dz), 0))]
-                    if self.keep:
-                        need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(dz), 1)))
-                        dl = self._sp_low_dgrad_desc(info["conv0"], sp, None)
-                        dl.algo = 2
-                        need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(dl), 0)))
-                    if all(need):
-                        sp["wino"] = 2
-                        ws_bytes = max([ws_bytes] + need)
-                        sp["fused_z"] = bool(self._fused_ok(sp["C1p"], sp["P"] * sp["N"])
-                                             and int(lib.clx_conv_fused_applicable(ctypes.byref(dz))))
-                        if sp["fused_z"]:
-                            ws_bytes = max(ws_bytes, int(lib.clx_conv_fused_workspace_bytes(ctypes.byref(dz))))
-                # ... and the 3x3 convolution over the skip tensor as F(4x4, 3x3), forward and weight
-                # gradient only: its data gradient has K = N (64 at the benchmark config), too short
-                # a contraction for the batched GEMMs to pay
-                sp["wino_skip"] = 0
-                conv0 = info["conv0"]
-                if (winograd_enabled() and winograd_code() == 2 and tuple(conv0.kernel) in ((1, 3, 3), (3, 3, 3))
-                        and sp["C0p"] >= wino_min_channels(conv0.kernel)
-                        and sp["N"] >= wino_min_channels(conv0.kernel) // 2):
-                    lib = _clx.load()
-                    _dz, ds = self._sp_descs(conv0, sp)
-                    ds.algo = 2
+            conv0 = info["conv0"]
+            sp = self._subpixel_geometry(conv0)
+            if sp is None:
+                continue
+            self.subpixel[conv0.name] = sp
+            skip, low = sp.halves
+            n = self.B * sp.zshape[0] * sp.zshape[1] * sp.zshape[2]
+            self.buf[sp.zname] = _clx.zeros((n, low.rows), torch.float32, self.device)
+            # the 2x2 convolution over the low-res tensor as Winograd F(4x4, 2x2)
+            if (winograd_enabled() and winograd_code() == 2 and low.kernel in ((1, 2, 2), (2, 2, 2))
+                    and min(low.Cp, low.rows) >= wino_min_channels(low.kernel)):
+                lib = _clx.load()
+                dz, _ds = self._sp_descs(conv0, sp)
+                dz.algo = 2
+                need = [int(lib.clx_conv_workspace_bytes(ctypes.byref(dz), 0))]
+                if self.keep:
+                    need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(dz), 1)))
+                    dl = self._sp_low_dgrad_desc(conv0, sp, None)
+                    dl.algo = 2
+                    need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(dl), 0)))
+                if all(need):
+                    low.wino = low.wino_dgrad = 2
+                    ws_bytes = max([ws_bytes] + need)
+                    low.fused = bool(self._fused_ok(low.Cp, low.rows)
+                                     and int(lib.clx_conv_fused_applicable(ctypes.byref(dz))))
+                    if low.fused:
+                        ws_bytes = max(ws_bytes, int(lib.clx_conv_fused_workspace_bytes(ctypes.byref(dz))))
+            # ... and the 3x3 convolution over the skip tensor as F(4x4, 3x3), forward and weight
+            # gradient only: its data gradient has K = N (64 at the benchmark config), too short
+            # a contraction for the batched GEMMs to pay
+            if (winograd_enabled() and winograd_code() == 2 and skip.kernel in ((1, 3, 3), (3, 3, 3))
+                    and skip.Cp >= wino_min_channels(skip.kernel)
+                    and sp.N >= wino_min_channels(skip.kernel) // 2):
+                lib = _clx.load()
+                _dz, ds = self._sp_descs(conv0, sp)
+                ds.algo = 2
+                need = [int(lib.clx_conv_workspace_bytes(ctypes.byref(ds), 0))]
+                if self.keep:
+                    ds.N = sp.N
+                    need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(ds), 1)))
+                if all(need):
+                    skip.wino = 2
+                    ws_bytes = max([ws_bytes] + need)
                     ds.N = conv0.cout
-                    need = [int(lib.clx_conv_workspace_bytes(ctypes.byref(ds), 0))]
-                    if self.keep:
-                        ds.N = sp["N"]
-                        need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(ds), 1)))
-                    if all(need):
-                        sp["wino_skip"] = 2
-                        ws_bytes = max([ws_bytes] + need)
-                        ds.N = conv0.cout
-                        sp["fused_skip"] = bool(self._fused_ok(sp["C0p"], conv0.cout) and conv0.cout == sp["N"]
-                                                and int(lib.clx_conv_fused_applicable(ctypes.byref(ds))))
-                # its data gradient contracts over z taps x output channels: long enough only in 3-D
-                sp["wino_skip_dgrad"] = 0
-                if sp["wino_skip"] and self.keep and sp["N"] * conv0.kernel[0] >= WINO_MIN_CHANNELS:
-                    dd = self._dgrad_desc(conv0, None)
-                    dd.N = sp["C0p"]
-                    dd.algo = 2
-                    need = int(_clx.load().clx_conv_workspace_bytes(ctypes.byref(dd), 0))
-                    if need:
-                        sp["wino_skip_dgrad"] = 2
-                        ws_bytes = max(ws_bytes, need)
-                ztaps = 25 * sp["zk"][0] if sp["wino"] else sp["ztaps"]
-                staps = 36 * info["conv0"].kernel[0] if sp["wino_skip"] else info["conv0"].taps
-                sp["w_skip"] = torch.empty(conv0.cout * sp["C0"] * conv0.taps, dtype=torch.float32, device=self.device)
-                sp["weff"] = torch.empty(sp["P"] * sp["N"] * sp["C1"] * sp["ztaps"], dtype=torch.float32,
-                                         device=self.device)
-                sp["wp_skip_fwd"] = torch.empty(sp["N"] * staps * sp["C0p"],
-                                                dtype=torch.float32, device=self.device)
-                sp["wp_z_fwd"] = torch.empty(sp["P"] * sp["N"] * ztaps * sp["C1p"],
-                                             dtype=torch.float32, device=self.device)
+                    skip.fused = bool(self._fused_ok(skip.Cp, conv0.cout) and conv0.cout == sp.N
+                                      and int(lib.clx_conv_fused_applicable(ctypes.byref(ds))))
+            # its data gradient contracts over z taps x output channels: long enough only in 3-D
+            if skip.wino and self.keep and sp.N * skip.kernel[0] >= WINO_MIN_CHANNELS:
+                dd = self._dgrad_desc(conv0, None)
+                dd.N = skip.Cp
+                dd.algo = 2
+                need = int(_clx.load().clx_conv_workspace_bytes(ctypes.byref(dd), 0))
+                if need:
+                    skip.wino_dgrad = 2
+                    ws_bytes = max(ws_bytes, need)
+            for h in sp.halves:
+                h.w = torch.empty(h.rows * h.C * h.taps, dtype=torch.float32, device=self.device)
+                h.wp_fwd = torch.empty(h.rows_pad * packed_taps(h.wino, h.kernel) * h.Cp, dtype=torch.float32,
+                                       device=self.device)
         if ws_bytes:
             self.workspace = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=self.device)
         self._decide_sp()
@@ -487,16 +566,16 @@ class UNetPlan:
         self.wpack_fwd = {}
         self.wpack_dgrad = {}
         for layer in t.convs:
-            code = self.algo[layer.name]["fwd"]
-            taps = wino_taps(code, layer.kernel) if code else layer.taps
             self.wpack_fwd[layer.name] = torch.empty(
-                pad4(layer.cout) * taps * layer.cin_pad, dtype=torch.float32, device=self.device)
+                pad4(layer.cout) * packed_taps(self.algo[layer.name]["fwd"], layer.kernel) * layer.cin_pad,
+                dtype=torch.float32, device=self.device)
             if self.sp_pass[layer.name][0]:
                 self._register_wplanes(self.wpack_fwd[layer.name], layer.cin_pad)
         for info in t.r_info:
             sp = self.subpixel.get(info["conv0"].name)
-            if sp and sp["wino"] and self._sp_covers(self._sp_descs(info["conv0"], sp)[0], 0, 3 if sp["fused_z"] else sp["wino"]):
-                self._register_wplanes(sp["wp_z_fwd"], sp["C1p"])
+            if sp and sp.low.wino and self._sp_covers(self._sp_descs(info["conv0"], sp)[0], 0,
+                                                      3 if sp.low.fused else sp.low.wino):
+                self._register_wplanes(sp.low.wp_fwd, sp.low.Cp)
         # scratch for the planes of a 1x1 layer's input (a training plan keeps one buffer per layer instead)
         rows_k = [(self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2], layer.cin_pad)
                   for layer in t.convs if self.sp_pass[layer.name][0] and not self.algo[layer.name]["fwd"]]
@@ -528,8 +607,8 @@ class UNetPlan:
         self.wpack_fwd, self.wpack_dgrad, self.dwpack = other.wpack_fwd, other.wpack_dgrad, other.dwpack
         self._wplanes = other._wplanes
         for name, sp in self.subpixel.items():
-            for key in ("w_skip", "weff", "wp_skip_fwd", "wp_z_fwd", "wp_skip_dgrad", "wp_z_dgrad", "dw_skip", "dw_z"):
-                sp[key] = other.subpixel[name][key]
+            for h, o in zip(sp.halves, other.subpixel[name].halves):
+                h.w, h.wp_fwd, h.wp_dgrad, h.dw = o.w, o.wp_fwd, o.wp_dgrad, o.dw
 
     def share_forward_from(self, other):
         """Forward-only version of share_from: this plan reads `other`'s packed weights and never packs."""
@@ -537,8 +616,8 @@ class UNetPlan:
         self.wpack_fwd = other.wpack_fwd
         self._wplanes = other._wplanes
         for name, sp in self.subpixel.items():
-            for key in ("w_skip", "weff", "wp_skip_fwd", "wp_z_fwd"):
-                sp[key] = other.subpixel[name][key]
+            for h, o in zip(sp.halves, other.subpixel[name].halves):
+                h.w, h.wp_fwd = o.w, o.wp_fwd
         self._packed_version = other._packed_version
 
     def _find_chains(self):
@@ -567,27 +646,18 @@ class UNetPlan:
             if sp is None:
                 self.gbuf["cat%d" % info["level"]] = _clx.zeros((n, layer.cin_pad), torch.float32, self.device)
             else:
-                self.gbuf["dskip%d" % info["level"]] = _clx.zeros((n, sp["C0p"]), torch.float32, self.device)
-                self.gbuf[sp["zname"]] = _clx.zeros(tuple(self.buf[sp["zname"]].shape), torch.float32, self.device)
-                sp["wp_skip_dgrad"] = torch.empty(sp["C0p"] * (36 * layer.kernel[0] if sp["wino_skip_dgrad"] else layer.taps)
-                                                  * sp["N"], dtype=torch.float32,
-                                                  device=self.device)
-                ztaps = 25 * sp["zk"][0] if sp["wino"] else sp["ztaps"]
-                sp["wp_z_dgrad"] = torch.empty(sp["C1p"] * ztaps * sp["P"] * sp["N"],
-                                               dtype=torch.float32, device=self.device)
-                sp["_dw_skip_n"] = (36 * layer.kernel[0] if sp["wino_skip"] else layer.taps) * sp["N"] * sp["C0p"]
-                sp["g_skip"] = torch.empty(layer.cout * sp["C0"] * layer.taps, dtype=torch.float32, device=self.device)
-                sp["g_z"] = torch.empty(sp["P"] * sp["N"] * sp["C1"] * sp["ztaps"], dtype=torch.float32,
-                                        device=self.device)
+                skip, low = sp.halves
+                self.gbuf["dskip%d" % info["level"]] = _clx.zeros((n, skip.Cp), torch.float32, self.device)
+                self.gbuf[sp.zname] = _clx.zeros(tuple(self.buf[sp.zname].shape), torch.float32, self.device)
                 dz, ds = self._sp_descs(layer, sp)
-                ds.N = layer.cout
-                if sp["wino_skip"] and not sp["fused_skip"] and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                    sp["vcache_skip"] = self._float_scratch(self._vcache_bytes(ds, sp["wino_skip"], 0))
-                sp["_dw_z_n"] = ztaps * sp["P"] * sp["N"] * sp["C1p"]
-                if sp["wino"] and not sp["fused_z"] and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                    sp["vcache"] = self._float_scratch(self._vcache_bytes(dz, sp["wino"], 0))
-                if sp["wino"] and self._sp_covers(self._sp_low_dgrad_desc(layer, sp, None), 0, sp["wino"]):
-                    self._register_wplanes(sp["wp_z_dgrad"], sp["P"] * sp["N"], dgrad=True)
+                for h, d in ((skip, ds), (low, dz)):
+                    h.wp_dgrad = torch.empty(h.Cp * packed_taps(h.wino_dgrad, h.kernel) * h.rows_pad, dtype=torch.float32,
+                                             device=self.device)
+                    h.g = torch.empty(h.rows * h.C * h.taps, dtype=torch.float32, device=self.device)
+                    if h.wino and not h.fused and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
+                        h.vcache = self._float_scratch(self._vcache_bytes(d, h.wino, 0))
+                if low.wino and self._sp_covers(self._sp_low_dgrad_desc(layer, sp, None), 0, low.wino):
+                    self._register_wplanes(low.wp_dgrad, low.rows, dgrad=True)
         # ReLU gates as bits: written by the epilogue that produces a layer's output, read by the data
         # gradient that passes through that ReLU — 1/32 of the float tensor it would otherwise read (the
         # 64-channel 1x1 layers of the 3-D network are HBM-bound).  Whole words per pixel (channels %
@@ -621,13 +691,12 @@ class UNetPlan:
             for layer in t.convs:
                 a = self.algo[layer.name]
                 if a["wgrad"] and a["wgrad"] == a["dgrad"] and layer.name not in self.subpixel and layer.name not in self.adjoint:
-                    d = self._desc(layer)
-                    d.N = pad4(layer.cout)
+                    d = self._desc(layer, pad4(layer.cout))
                     need = max(need, self._vcache_bytes(d, a["wgrad"], 1))
             for info in t.r_info:
                 sp = self.subpixel.get(info["conv0"].name)
-                if sp and sp["wino"]:
-                    need = max(need, self._vcache_bytes(self._sp_descs(info["conv0"], sp)[0], sp["wino"], 1))
+                if sp and sp.low.wino:
+                    need = max(need, self._vcache_bytes(self._sp_descs(info["conv0"], sp)[0], sp.low.wino, 1))
             if need:
                 self.dycache = self._float_scratch(need)
         # forward and weight gradient of a Winograd layer transform the same input: keep V
@@ -635,20 +704,17 @@ class UNetPlan:
         for layer in t.convs:
             a = self.algo[layer.name]
             if a["fwd"] and a["fwd"] == a["wgrad"] and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                d = self._desc(layer)
-                d.N = layer.cout
+                d = self._desc(layer, layer.cout)
                 self.vcache[layer.name] = self._float_scratch(self._vcache_bytes(d, a["fwd"], 0))
         total = 0
         self.dw_off = {}
         for layer in t.convs:
             self.dw_off[layer.name] = total
-            code = self.algo[layer.name]["wgrad"]
-            total += (wino_taps(code, layer.kernel) if code else layer.taps) * pad4(layer.cout) * layer.cin_pad
+            total += packed_taps(self.algo[layer.name]["wgrad"], layer.kernel) * pad4(layer.cout) * layer.cin_pad
             if layer.param_index > 0:  # first layer needs no data gradient
-                code = self.algo[layer.name]["dgrad"]
-                taps = wino_taps(code, layer.kernel) if code else layer.taps
                 self.wpack_dgrad[layer.name] = torch.empty(
-                    layer.cin_pad * taps * pad4(layer.cout), dtype=torch.float32, device=self.device)
+                    layer.cin_pad * packed_taps(self.algo[layer.name]["dgrad"], layer.kernel) * pad4(layer.cout),
+                    dtype=torch.float32, device=self.device)
                 if self.sp_pass[layer.name][1]:
                     self._register_wplanes(self.wpack_dgrad[layer.name], pad4(layer.cout), dgrad=True)
         # training: the planes of a split 1x1 layer's input stay for its weight gradient; one scratch for the planes of dY
@@ -673,10 +739,12 @@ class UNetPlan:
             if layer.name in self.xplanes and pad4(t.shapes[layer.sources[0].tensor][1]) == layer.cin_pad:
                 self._pointwise_reader[layer.sources[0].tensor] = layer
         # the sub-pixel layers' weight-gradient accumulators live behind the others: one fill zeroes all
-        sp_off = {}
-        for name, sp in self.subpixel.items():
-            sp_off[name] = (total, total + sp["_dw_skip_n"])
-            total += sp["_dw_skip_n"] + sp["_dw_z_n"]
+        sp_slices = []
+        for sp in self.subpixel.values():
+            for h in sp.halves:
+                n = packed_taps(h.wino, h.kernel) * h.rows_pad * h.Cp
+                sp_slices.append((h, total, n))
+                total += n
         self.dwpack = _clx.zeros(total, torch.float32, self.device)
         if self.deterministic:
             lib = _clx.load()
@@ -684,10 +752,11 @@ class UNetPlan:
             self._det_turns = _clx.zeros(1 << 20, torch.int32, self.device)     # 4 MB of turn counters
             self._det_colsum = torch.empty(int(lib.clx_colsum_scratch_bytes(width)) // 4, dtype=torch.float32,
                                            device=self.device)
-        for name, sp in self.subpixel.items():
-            a, b = sp_off[name]
-            sp["dw_skip"] = self.dwpack[a:b]
-            sp["dw_z"] = self.dwpack[b:b + sp["_dw_z_n"]]
+        for h, off, n in sp_slices:
+            h.dw = self.dwpack[off:off + n]
+        # tensor -> the convolution / the pooling that produces it (backward_steps routes gradients by them)
+        self._conv_by_out = {layer.out: layer for layer in t.convs}
+        self._pool_by_out = {p.out: p for p in t.pools}
         self._bwd_ready = True
 
     # --------------------------------------------------------------- sub-pixel
@@ -720,9 +789,12 @@ class UNetPlan:
             if zcrop[d] != 0 or zshape[d] + zk[d] - 1 != low_shape[d]:
                 return None
         level = [i["level"] for i in self.topo.r_info if i["conv0"] is layer][0]
-        return dict(fac=f, P=f[0] * f[1] * f[2], N=pad4(layer.cout), C0=skip_s.channels, C0p=pad4(skip_s.channels),
-                    C1=up_s.channels, C1p=pad4(up_s.channels), zshape=tuple(zshape), zk=tuple(zk),
-                    ztaps=zk[0] * zk[1] * zk[2], zname="Z%d" % level, level=level)
+        P, N = f[0] * f[1] * f[2], pad4(layer.cout)
+        return Subpixel(fac=f, P=P, N=N, zshape=tuple(zshape), zname="Z%d" % level, level=level,
+                        skip=SubpixelHalf(rows=layer.cout, rows_pad=N, C=skip_s.channels, Cp=pad4(skip_s.channels),
+                                          kernel=tuple(layer.kernel)),
+                        low=SubpixelHalf(rows=P * N, rows_pad=P * N, C=up_s.channels, Cp=pad4(up_s.channels),
+                                         kernel=tuple(zk)))
 
     @staticmethod
     def _phase_sum(w, axis, a):
@@ -741,7 +813,8 @@ class UNetPlan:
 
     def _phase_weights(self, layer, sp, w_up):
         """w_up (cout, C1, kd, kh, kw) -> phase-summed (P*N, C1, zkd, zkh, zkw); rows of padded
-        output channels are zero.  Tiny tensors: plain elementwise torch ops."""
+        output channels are zero.  Tiny tensors: plain elementwise torch ops.  (The statement of the algebra the tests
+        check clx_subpixel_split_weights against, not a launch path: `sp` is any mapping with fac, P, N, C1 and zk.)"""
         f, N, cout = sp["fac"], sp["N"], layer.cout
         out = w_up.new_zeros((sp["P"], N, sp["C1"]) + sp["zk"])
         for a in range(f[0]):
@@ -770,182 +843,114 @@ class UNetPlan:
         return out
 
     def _sp_descs(self, layer, sp):
-        """(Z-convolution descriptor over the low-res tensor, skip-convolution descriptor)."""
+        """(Z-convolution descriptor over the low-res tensor, skip-convolution descriptor with the forward pass's N =
+        cout: its weight gradient has N = pad4(cout))."""
         t = self.topo
         skip_s, up_s = layer.sources
-        dz = ClxConvDesc()
-        dz.nsrc = 1
         low_shape, low_c = t.shapes[up_s.tensor]
-        src = ClxSrc()
-        src.ptr = self.buf[up_s.tensor].data_ptr()
-        src.C = sp["C1p"]
-        src.ld = pad4(low_c)
-        src.D, src.H, src.W = low_shape
-        src.oz = src.oy = src.ox = 0
-        src.fz = src.fy = src.fx = 1
-        dz.src[0] = src
-        dz.B = self.B
-        dz.ID, dz.IH, dz.IW = low_shape
-        dz.KD, dz.KH, dz.KW = sp["zk"]
-        dz.PD = dz.PH = dz.PW = 0
-        dz.N = sp["P"] * sp["N"]
-        ds = ClxConvDesc()
-        ds.nsrc = 1
         sshape, sc = t.shapes[skip_s.tensor]
-        src2 = ClxSrc()
-        src2.ptr = self.buf[skip_s.tensor].data_ptr()
-        src2.C = sp["C0p"]
-        src2.ld = pad4(sc)
-        src2.D, src2.H, src2.W = sshape
-        src2.oz, src2.oy, src2.ox = skip_s.crop
-        src2.fz = src2.fy = src2.fx = 1
-        ds.src[0] = src2
-        ds.B = self.B
-        ds.ID, ds.IH, ds.IW = layer.in_shape
-        ds.KD, ds.KH, ds.KW = layer.kernel
-        ds.PD = ds.PH = ds.PW = 0
-        for d in (dz, ds):
-            d.precision = self.precision
-            d.algo = 0
-            d.accumulate = 0
-            d.workspace = None
-            d.workspace_bytes = 0
-            d.mask = None
-            d.ld_mask = 0
-            d.bias = None
-            d.relu = 0
+        dz = conv_desc([conv_src(self.buf[up_s.tensor].data_ptr(), sp.low.Cp, pad4(low_c), low_shape)], self.B, low_shape,
+                       sp.low.kernel, (0, 0, 0), sp.low.rows, self.precision)
+        ds = conv_desc([conv_src(self.buf[skip_s.tensor].data_ptr(), sp.skip.Cp, pad4(sc), sshape, crop=skip_s.crop)],
+                       self.B, layer.in_shape, layer.kernel, (0, 0, 0), layer.cout, self.precision)
         return dz, ds
 
-    @staticmethod
-    def _sp_pack_mode(sp, half):
-        """clx_pack_mode of a sub-pixel layer's forward weights: plain, F(4x4), or F(4x4) in the fused kernel's layout"""
-        if half == "skip":
-            return 7 if sp["fused_skip"] else 4 if sp["wino_skip"] else 0
-        return 7 if sp["fused_z"] else 4 if sp["wino"] else 0
-
-    def _sp_pack(self, layer, sp, w, need_dgrad, st):
-        # one launch: the skip half's weights and the phase-summed weights of the upsampled half
-        # (_phase_weights is the same algebra in torch ops, kept as the CPU-testable statement)
+    def _sp_split(self, layer, sp, w, st):
+        """one launch: the skip half's weights and the phase-summed weights of the upsampled half
+        (_phase_weights is the same algebra in torch ops, kept as the CPU-testable statement)"""
         wv = w.detach()
         if not wv.is_contiguous():
             wv = wv.contiguous()
-        w_skip, weff = sp["w_skip"], sp["weff"]
-        _clx.call("clx_subpixel_split_weights", _clx.ptr(wv), _clx.ptr(w_skip), _clx.ptr(weff), layer.cout,
-                  layer.cin, sp["C0"], sp["N"], *layer.kernel, *sp["fac"], st)
-        _clx.call("clx_pack_weights", _clx.ptr(w_skip), _clx.ptr(sp["wp_skip_fwd"]), layer.cout, sp["C0"],
-                  layer.taps, sp["C0p"], sp["N"], self._sp_pack_mode(sp, "skip"), st)
-        _clx.call("clx_pack_weights", _clx.ptr(weff), _clx.ptr(sp["wp_z_fwd"]), sp["P"] * sp["N"], sp["C1"],
-                  sp["ztaps"], sp["C1p"], sp["P"] * sp["N"], self._sp_pack_mode(sp, "z"), st)
-        if need_dgrad:
-            _clx.call("clx_pack_weights", _clx.ptr(w_skip), _clx.ptr(sp["wp_skip_dgrad"]), layer.cout, sp["C0"],
-                      layer.taps, sp["C0p"], sp["N"], 5 if sp["wino_skip_dgrad"] else 1, st)
-            _clx.call("clx_pack_weights", _clx.ptr(weff), _clx.ptr(sp["wp_z_dgrad"]), sp["P"] * sp["N"],
-                      sp["C1"], sp["ztaps"], sp["C1p"], sp["P"] * sp["N"], 5 if sp["wino"] else 1, st)
+        _clx.call("clx_subpixel_split_weights", _clx.ptr(wv), _clx.ptr(sp.skip.w), _clx.ptr(sp.low.w), layer.cout,
+                  layer.cin, sp.skip.C, sp.N, *layer.kernel, *sp.fac, st)
+
+    def _sp_half_forward(self, h, d):
+        """what the forward launches of both halves share: packed weights, algorithm, the transformed input kept"""
+        self._set_wpack(d, h.wp_fwd)
+        h.v_fresh = False
+        if h.fused:
+            self._use_workspace(d, 3)
+        elif h.wino:
+            self._use_workspace(d, h.wino)
+            if self.keep and h.vcache is not None:
+                d.vcache = h.vcache.data_ptr()
+                h.v_fresh = True
 
     def _sp_forward(self, layer, sp, bias, st):
         dz, ds = self._sp_descs(layer, sp)
-        zbuf = self.buf[sp["zname"]]
-        self._set_wpack(dz, sp["wp_z_fwd"])
+        zbuf = self.buf[sp.zname]
         dz.out = zbuf.data_ptr()
-        dz.ld_out = sp["P"] * sp["N"]
-        sp["_v_fresh"] = False
-        if sp["fused_z"]:
-            self._use_workspace(dz, 3)
-        elif sp["wino"]:
-            self._use_workspace(dz, sp["wino"])
-            if self.keep and "vcache" in sp:
-                dz.vcache = sp["vcache"].data_ptr()
-                sp["_v_fresh"] = True
+        dz.ld_out = sp.low.rows
+        self._sp_half_forward(sp.low, dz)
         _clx.call("clx_conv_fwd", ctypes.byref(dz), st)
         out = self.buf[layer.out]
-        zs = sp["zshape"]
-        _clx.call("clx_depth_to_space", _clx.ptr(zbuf), sp["P"] * sp["N"], _clx.ptr(out), sp["N"], self.B,
-                  zs[0], zs[1], zs[2], sp["N"], *sp["fac"], st)
-        ds.N = layer.cout
-        self._set_wpack(ds, sp["wp_skip_fwd"])
+        zs = sp.zshape
+        _clx.call("clx_depth_to_space", _clx.ptr(zbuf), sp.low.rows, _clx.ptr(out), sp.N, self.B,
+                  zs[0], zs[1], zs[2], sp.N, *sp.fac, st)
         ds.bias = bias.data_ptr() if bias is not None else None
         ds.relu = 1 if layer.relu else 0
         ds.accumulate = 1
         ds.out = out.data_ptr()
-        ds.ld_out = sp["N"]
+        ds.ld_out = sp.N
         if layer.relu and self.keep:
             self._set_gate_out(ds, layer.out)
-        sp["_vskip_fresh"] = False
-        if sp["fused_skip"]:
-            self._use_workspace(ds, 3)
-        elif sp["wino_skip"]:
-            self._use_workspace(ds, sp["wino_skip"])
-            if self.keep and "vcache_skip" in sp:
-                ds.vcache = sp["vcache_skip"].data_ptr()
-                sp["_vskip_fresh"] = True
+        self._sp_half_forward(sp.skip, ds)
         _clx.call("clx_conv_fwd", ctypes.byref(ds), st)
 
     def _sp_wgrad(self, layer, sp, dy, gw, gb, st):
         """weight/bias gradient of a sub-pixel layer (added into the layer's slices of self.dwpack); returns
         unpack(stream), which unpacks both halves and folds them into `gw`."""
         dz, ds = self._sp_descs(layer, sp)
-        zs, PN = sp["zshape"], sp["P"] * sp["N"]
+        skip, low = sp.halves
+        zs = sp.zshape
         # dZ = space_to_depth(dY)
-        dzbuf = self.gbuf[sp["zname"]]
-        _clx.call("clx_space_to_depth", _clx.ptr(dy), sp["N"], _clx.ptr(dzbuf), PN, self.B,
-                  zs[0], zs[1], zs[2], sp["N"], *sp["fac"], st)
-        # weight gradients (dw_skip / dw_z are slices of self.dwpack: zeroed with it)
-        ds.N = sp["N"]
-        if sp["wino_skip"]:
-            self._use_workspace(ds, sp["wino_skip"])
-            if sp.get("_vskip_fresh"):
-                ds.vcache = sp["vcache_skip"].data_ptr()
-                ds.vcache_valid = 1
-        self._wgrad(ds, dy, sp["N"], sp["dw_skip"], gb, layer.cout, st)
-        if sp["wino"]:
-            self._use_workspace(dz, sp["wino"])
-            if sp.get("_v_fresh"):
-                dz.vcache = sp["vcache"].data_ptr()
-                dz.vcache_valid = 1
-            if self.dycache is not None:
-                dz.dy_vcache = self.dycache.data_ptr()
-        self._wgrad(dz, dzbuf, PN, sp["dw_z"], None, 0, st)
-        g_skip, g_z = sp["g_skip"], sp["g_z"]
+        dzbuf = self.gbuf[sp.zname]
+        _clx.call("clx_space_to_depth", _clx.ptr(dy), sp.N, _clx.ptr(dzbuf), low.rows, self.B,
+                  zs[0], zs[1], zs[2], sp.N, *sp.fac, st)
+        # weight gradients (the halves' dw are slices of self.dwpack: zeroed with it)
+        ds.N = sp.N
+        if low.wino and self.dycache is not None:
+            dz.dy_vcache = self.dycache.data_ptr()
+        for h, d, dyh, ld_dy, gbh, nbias in ((skip, ds, dy, sp.N, gb, layer.cout), (low, dz, dzbuf, low.rows, None, 0)):
+            if h.wino:
+                self._use_workspace(d, h.wino)
+                if h.v_fresh:
+                    d.vcache = h.vcache.data_ptr()
+                    d.vcache_valid = 1
+            self._wgrad(d, dyh, ld_dy, h.dw, gbh, nbias, st)
 
         def unpack(st):
-            if sp["wino_skip"]:
-                _clx.call("clx_unpack_wgrad_wino", _clx.ptr(sp["dw_skip"]), _clx.ptr(g_skip), layer.cout, sp["C0"],
-                          sp["N"], sp["C0p"], 4, 3, layer.kernel[0], st)
-            else:
-                _clx.call("clx_unpack_wgrad", _clx.ptr(sp["dw_skip"]), _clx.ptr(g_skip), layer.cout, sp["C0"],
-                          layer.taps, sp["N"], sp["C0p"], st)
-            if sp["wino"]:
-                _clx.call("clx_unpack_wgrad_wino", _clx.ptr(sp["dw_z"]), _clx.ptr(g_z), PN, sp["C1"], PN, sp["C1p"],
-                          4, 2, sp["zk"][0], st)
-            else:
-                _clx.call("clx_unpack_wgrad", _clx.ptr(sp["dw_z"]), _clx.ptr(g_z), PN, sp["C1"], sp["ztaps"], PN,
-                          sp["C1p"], st)
+            for h in sp.halves:
+                if h.wino:
+                    _clx.call("clx_unpack_wgrad_wino", _clx.ptr(h.dw), _clx.ptr(h.g), h.rows, h.C, h.rows_pad, h.Cp,
+                              WINO_TILE[h.wino], h.kernel[1], h.kernel[0], st)
+                else:
+                    _clx.call("clx_unpack_wgrad", _clx.ptr(h.dw), _clx.ptr(h.g), h.rows, h.C, h.taps, h.rows_pad, h.Cp, st)
             # adjoint of the weight split (one launch; _fold_phase_grads states the same in torch ops)
-            _clx.call("clx_subpixel_fold_grads", _clx.ptr(g_skip), _clx.ptr(g_z), _clx.ptr(gw), layer.cout, layer.cin,
-                      sp["C0"], sp["N"], *layer.kernel, *sp["fac"], st)
+            _clx.call("clx_subpixel_fold_grads", _clx.ptr(skip.g), _clx.ptr(low.g), _clx.ptr(gw), layer.cout, layer.cin,
+                      skip.C, sp.N, *layer.kernel, *sp.fac, st)
         return unpack
 
     def _sp_dgrad(self, layer, sp, dy, st):
         """both data gradients of a sub-pixel layer (after _sp_wgrad: it reads the transformed dZ that call left
         in self.dycache); returns the skip gradient buffer (pre-gate, full skip-crop grid)."""
-        dzbuf = self.gbuf[sp["zname"]]
+        skip, low = sp.halves
+        dzbuf = self.gbuf[sp.zname]
         # data gradient of the skip branch (gated later, together with the max-pool gradient)
-        dskip = self.gbuf["dskip%d" % sp["level"]]
+        dskip = self.gbuf["dskip%d" % sp.level]
         dd = self._dgrad_desc(layer, dy)
-        dd.N = sp["C0p"]
-        self._set_wpack(dd, sp["wp_skip_dgrad"])
-        dd.mask = None
-        dd.ld_mask = 0
+        dd.N = skip.Cp
+        self._set_wpack(dd, skip.wp_dgrad)
         dd.out = dskip.data_ptr()
-        dd.ld_out = sp["C0p"]
-        if sp["wino_skip_dgrad"]:
-            self._use_workspace(dd, sp["wino_skip_dgrad"])
+        dd.ld_out = skip.Cp
+        if skip.wino_dgrad:
+            self._use_workspace(dd, skip.wino_dgrad)
         _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
         # data gradient of the low-res tensor straight from dZ (replaces upsample backward)
         dl = self._sp_low_dgrad_desc(layer, sp, dzbuf)
-        self._set_wpack(dl, sp["wp_z_dgrad"])
-        if sp["wino"]:
-            self._use_workspace(dl, sp["wino"])
+        self._set_wpack(dl, low.wp_dgrad)
+        if low.wino:
+            self._use_workspace(dl, low.wino)
             if self.dycache is not None:       # written by the weight-gradient call on dZ above
                 dl.vcache = self.dycache.data_ptr()
                 dl.vcache_valid = 1
@@ -954,68 +959,30 @@ class UNetPlan:
 
     def _sp_low_dgrad_desc(self, layer, sp, dzbuf):
         """dL/d(low-res tensor) as the transposed 2x2(x2) convolution of dZ, ReLU gate fused."""
-        t = self.topo
-        zs, PN = sp["zshape"], sp["P"] * sp["N"]
+        low = sp.low
         up_s = layer.sources[1]
-        low_shape, low_c = t.shapes[up_s.tensor]
-        dl = ClxConvDesc()
-        dl.nsrc = 1
-        src = ClxSrc()
-        src.ptr = dzbuf.data_ptr() if dzbuf is not None else 16      # geometry-only queries never dereference
-        src.C = PN
-        src.ld = PN
-        src.D, src.H, src.W = zs
-        src.oz = src.oy = src.ox = 0
-        src.fz = src.fy = src.fx = 1
-        dl.src[0] = src
-        dl.B = self.B
-        dl.ID, dl.IH, dl.IW = zs
-        dl.KD, dl.KH, dl.KW = sp["zk"]
-        dl.PD, dl.PH, dl.PW = (k - 1 for k in sp["zk"])
-        dl.N = sp["C1p"]
-        dl.bias = None
-        dl.relu = 0
-        dl.accumulate = 0
-        dl.algo = 0
-        dl.workspace = None
-        dl.workspace_bytes = 0
-        dl.precision = self.precision
+        low_shape, low_c = self.topo.shapes[up_s.tensor]
+        # (geometry-only queries never dereference)
+        dl = conv_desc([conv_src(dzbuf.data_ptr() if dzbuf is not None else 16, low.rows, low.rows, sp.zshape)], self.B,
+                       sp.zshape, low.kernel, tuple(k - 1 for k in low.kernel), low.Cp, self.precision)
+        dl.ld_out = pad4(low_c)
         if dzbuf is not None:
             self._set_mask(dl, up_s.tensor)                 # ReLU gate of the low-res tensor
+            dl.out = self.gbuf[up_s.tensor].data_ptr()
         else:                                               # geometry-only query
             dl.mask = self.buf[up_s.tensor].data_ptr()
             dl.ld_mask = pad4(low_c)
-        dl.out = self.gbuf[up_s.tensor].data_ptr() if dzbuf is not None else None
-        dl.ld_out = pad4(low_c)
         return dl
 
     # ------------------------------------------------------------- descriptors
-    def _desc(self, layer: ConvLayer):
-        d = ClxConvDesc()
-        d.nsrc = len(layer.sources)
+    def _desc(self, layer: ConvLayer, N):
+        """forward / weight-gradient descriptor of a plain layer with N output channels (cout / pad4(cout))"""
         t = self.topo
-        for i, s in enumerate(layer.sources):
-            shape, c = t.shapes[s.tensor]
-            src = ClxSrc()
-            src.ptr = self.buf[s.tensor].data_ptr()
-            src.C = pad4(s.channels)
-            src.ld = pad4(c)
-            src.D, src.H, src.W = shape
-            src.oz, src.oy, src.ox = s.crop
-            src.fz, src.fy, src.fx = s.factor
-            d.src[i] = src
-        d.B = self.B
-        d.ID, d.IH, d.IW = layer.in_shape
-        d.KD, d.KH, d.KW = layer.kernel
-        d.PD = d.PH = d.PW = 0
-        d.accumulate = 0
-        d.algo = 0
-        d.workspace = None
-        d.workspace_bytes = 0
-        d.precision = self.precision
+        srcs = [conv_src(self.buf[s.tensor].data_ptr(), pad4(s.channels), pad4(t.shapes[s.tensor][1]), t.shapes[s.tensor][0],
+                         s.crop, s.factor) for s in layer.sources]
         # a raw image with 1-3 channels is stored padded to 4: tell the first-layer kernels
-        d.c_real = layer.sources[0].channels if len(layer.sources) == 1 else 0
-        return d
+        return conv_desc(srcs, self.B, layer.in_shape, layer.kernel, (0, 0, 0), N, self.precision,
+                         c_real=layer.sources[0].channels if len(layer.sources) == 1 else 0)
 
     def _set_gate_out(self, d, name):
         """forward epilogue of the layer producing buffer `name`: also emit the ReLU gates as bits"""
@@ -1028,9 +995,8 @@ class UNetPlan:
         """data-gradient epilogue: gate by the ReLU of the layer that produced buffer `name`"""
         g = self.gate.get(name)
         if not relu:
-            d.mask, d.ld_mask = None, 0
-        elif g is not None:
-            d.mask, d.ld_mask = None, 0
+            return
+        if g is not None:
             d.mask_bits = g.data_ptr()
             d.ld_mask_bits = g.shape[1]
         else:
@@ -1067,8 +1033,7 @@ class UNetPlan:
                 self.sp_pass[layer.name] = (False, False, False)
                 continue
             a = self.algo[layer.name]
-            d = self._desc(layer)
-            d.N = layer.cout
+            d = self._desc(layer, layer.cout)
             fwd = self._sp_covers(d, 0, a["fwd"])
             d.N = pad4(layer.cout)
             wgrad = self._sp_covers(d, 1, a["wgrad"])
@@ -1108,29 +1073,10 @@ class UNetPlan:
 
     def _dgrad_desc(self, layer: ConvLayer, dy):
         """Data gradient as a convolution of dy (zero padding k-1, flipped transposed weights)."""
-        dd = ClxConvDesc()
-        dd.nsrc = 1
-        src = ClxSrc()
-        src.ptr = dy.data_ptr() if dy is not None else 16      # geometry-only queries never dereference
-        src.C = pad4(layer.cout)
-        src.ld = pad4(layer.cout)
-        src.D, src.H, src.W = layer.out_shape
-        src.oz = src.oy = src.ox = 0
-        src.fz = src.fy = src.fx = 1
-        dd.src[0] = src
-        dd.B = self.B
-        dd.ID, dd.IH, dd.IW = layer.out_shape
-        dd.KD, dd.KH, dd.KW = layer.kernel
-        dd.PD, dd.PH, dd.PW = (k - 1 for k in layer.kernel)
-        dd.N = layer.cin_pad
-        dd.bias = None
-        dd.relu = 0
-        dd.accumulate = 0
-        dd.algo = 0
-        dd.workspace = None
-        dd.workspace_bytes = 0
-        dd.precision = self.precision
-        return dd
+        n = pad4(layer.cout)
+        # (geometry-only queries never dereference)
+        return conv_desc([conv_src(dy.data_ptr() if dy is not None else 16, n, n, layer.out_shape)], self.B, layer.out_shape,
+                         layer.kernel, tuple(k - 1 for k in layer.kernel), layer.cin_pad, self.precision)
 
     def _expand_cin(self, layer, w):
         """torch weight (cout, cin, taps) -> (cout, cin_gapped, taps) when a concat source is padded."""
@@ -1224,109 +1170,92 @@ class UNetPlan:
                           layer.cin, 1, pad4(layer.cout), layer.cin_pad, st)
         return unpack
 
-    def _pack_layer(self, layer, w, need_dgrad, st):
-        wv = w.detach().reshape(layer.cout, layer.cin, layer.taps)
-        if not wv.is_contiguous():
-            wv = wv.contiguous()
-        wv, cin_eff = self._expand_cin(layer, wv)
-        algo = self.algo[layer.name]
-        _clx.call("clx_pack_weights", _clx.ptr(wv), _clx.ptr(self.wpack_fwd[layer.name]),
-                  layer.cout, cin_eff, layer.taps, layer.cin_pad, pad4(layer.cout),
-                  WINO_PACK_FWD.get(algo["fwd"], 0), st)
-        if need_dgrad and layer.name in self.wpack_dgrad:
-            _clx.call("clx_pack_weights", _clx.ptr(wv), _clx.ptr(self.wpack_dgrad[layer.name]),
-                      layer.cout, cin_eff, layer.taps, layer.cin_pad, pad4(layer.cout),
-                      6 if layer.name in self.adjoint else WINO_PACK_DGRAD.get(algo["dgrad"], 1), st)
+    def _pack_jobs(self, params, need_dgrad):
+        """The packings of a step, layer by layer in launch order: yields (layer, copy, jobs), jobs = the argument lists
+        (source, destination, cout, cin, taps, cin_pad, cout_pad, clx_pack_mode) of the layer's clx_pack_weights calls.
+        A sub-pixel layer packs its halves' weights (_sp_split writes them first).  copy: the parameter cannot be read
+        as it is — not contiguous, or a concatenation of odd channel counts — and _pack_one reads a copy instead."""
+        for layer in self.topo.convs:
+            w = params[2 * layer.param_index]
+            sp = self.subpixel.get(layer.name)
+            if sp is not None:
+                jobs = [(h.w, h.wp_fwd, h.rows, h.C, h.taps, h.Cp, h.rows_pad, 7 if h.fused else 4 if h.wino else 0)
+                        for h in sp.halves]
+                if need_dgrad:
+                    jobs += [(h.w, h.wp_dgrad, h.rows, h.C, h.taps, h.Cp, h.rows_pad, 5 if h.wino_dgrad else 1)
+                             for h in sp.halves]
+                yield layer, False, jobs
+                continue
+            algo = self.algo[layer.name]
+            dsts = [(self.wpack_fwd[layer.name], WINO_PACK_FWD.get(algo["fwd"], 0))]
+            if need_dgrad and layer.name in self.wpack_dgrad:
+                dsts.append((self.wpack_dgrad[layer.name],
+                             6 if layer.name in self.adjoint else WINO_PACK_DGRAD.get(algo["dgrad"], 1)))
+            gapped = len(layer.sources) > 1 and not all(s.channels % 4 == 0 for s in layer.sources[:-1])
+            yield layer, gapped or not w.is_contiguous(), [
+                (w, dst, layer.cout, layer.cin, layer.taps, layer.cin_pad, pad4(layer.cout), mode) for dst, mode in dsts]
+
+    def _pack_one(self, layer, copy, jobs, params, st):
+        """one layer's packings, a launch each"""
+        if copy:
+            wv = params[2 * layer.param_index].detach().reshape(layer.cout, layer.cin, layer.taps)
+            if not wv.is_contiguous():
+                wv = wv.contiguous()
+            wv, cin_eff = self._expand_cin(layer, wv)
+            jobs = [(wv, dst, cout, cin_eff) + tuple(rest) for _w, dst, cout, _cin, *rest in jobs]
+        for src, dst, *rest in jobs:
+            _clx.call("clx_pack_weights", _clx.ptr(src), _clx.ptr(dst), *rest, st)
 
     def _pack_batched(self, params, need_dgrad, st):
         """Every packing of the step in ONE launch (clx_pack_weights_batch): the job table — the arguments of
         the ~40 clx_pack_weights calls — is built once per plan and lives on the device; it is rebuilt when a
         parameter's storage moves.  The sub-pixel layers' weight split runs first (its outputs are sources of
-        jobs); layers whose weights need a gapped copy (odd channel counts in a concatenation) keep their calls."""
+        jobs); layers whose weights need a copy (_pack_jobs) keep their calls."""
         from .._clx import ClxPackJob
 
         sig = (bool(need_dgrad),) + tuple(params[2 * layer.param_index].data_ptr() for layer in self.topo.convs)
         cache = getattr(self, "_pack_table", None)
         if cache is None or cache["sig"] != sig:
-            jobs, singles = [], []
-
-            def job(src, dst, cout, cin, taps, cin_pad, cout_pad, mode):
-                jobs.append(ClxPackJob(src.data_ptr(), dst.data_ptr(), cout, cin, taps, cin_pad, cout_pad, mode))
-                if mode in (0, 1):
-                    return (cout if mode == 0 else cin_pad) * taps * (cin_pad if mode == 0 else cout_pad)
-                if mode == 7:
-                    return cout_pad * cin_pad
-                rows, cols = (cin_pad, cout_pad) if mode in (3, 5, 6) else (cout_pad, cin_pad)
-                return rows * (3 if taps == 27 else 2 if taps == 8 else 1) * cols
-
-            biggest = 1
-            for layer in self.topo.convs:
-                w = params[2 * layer.param_index]
-                if layer.name in self.subpixel:
-                    sp = self.subpixel[layer.name]
-                    PN = sp["P"] * sp["N"]
-                    biggest = max(biggest, job(sp["w_skip"], sp["wp_skip_fwd"], layer.cout, sp["C0"], layer.taps,
-                                               sp["C0p"], sp["N"], self._sp_pack_mode(sp, "skip")),
-                                  job(sp["weff"], sp["wp_z_fwd"], PN, sp["C1"], sp["ztaps"], sp["C1p"], PN,
-                                      self._sp_pack_mode(sp, "z")))
-                    if need_dgrad:
-                        biggest = max(biggest, job(sp["w_skip"], sp["wp_skip_dgrad"], layer.cout, sp["C0"], layer.taps,
-                                                   sp["C0p"], sp["N"], 5 if sp["wino_skip_dgrad"] else 1),
-                                      job(sp["weff"], sp["wp_z_dgrad"], PN, sp["C1"], sp["ztaps"], sp["C1p"], PN,
-                                          5 if sp["wino"] else 1))
+            table_jobs, singles, biggest = [], [], 1
+            for layer, copy, jobs in self._pack_jobs(params, need_dgrad):
+                if copy:
+                    singles.append((layer, copy, jobs))
                     continue
-                gapped = len(layer.sources) > 1 and not all(s.channels % 4 == 0 for s in layer.sources[:-1])
-                if gapped or not w.is_contiguous():
-                    singles.append(layer)
-                    continue
-                algo = self.algo[layer.name]
-                biggest = max(biggest, job(w, self.wpack_fwd[layer.name], layer.cout, layer.cin, layer.taps,
-                                           layer.cin_pad, pad4(layer.cout), WINO_PACK_FWD.get(algo["fwd"], 0)))
-                if need_dgrad and layer.name in self.wpack_dgrad:
-                    biggest = max(biggest, job(w, self.wpack_dgrad[layer.name], layer.cout, layer.cin, layer.taps,
-                                               layer.cin_pad, pad4(layer.cout),
-                                               6 if layer.name in self.adjoint else WINO_PACK_DGRAD.get(algo["dgrad"], 1)))
+                for src, dst, *rest in jobs:
+                    table_jobs.append(ClxPackJob(src.data_ptr(), dst.data_ptr(), *rest))
+                    biggest = max(biggest, pack_job_elements(*rest))
             table = None
-            if jobs:
-                arr = (ClxPackJob * len(jobs))(*jobs)
+            if table_jobs:
+                arr = (ClxPackJob * len(table_jobs))(*table_jobs)
                 host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
                 table = host.to(self.device)
-            cache = self._pack_table = dict(sig=sig, table=table, njobs=len(jobs), biggest=int(biggest), singles=singles)
+            cache = self._pack_table = dict(sig=sig, table=table, njobs=len(table_jobs), biggest=int(biggest),
+                                            singles=singles)
         for layer in self.topo.convs:
             if layer.name in self.subpixel:
-                sp = self.subpixel[layer.name]
-                wv = params[2 * layer.param_index].detach()
-                if not wv.is_contiguous():
-                    wv = wv.contiguous()
-                _clx.call("clx_subpixel_split_weights", _clx.ptr(wv), _clx.ptr(sp["w_skip"]), _clx.ptr(sp["weff"]),
-                          layer.cout, layer.cin, sp["C0"], sp["N"], *layer.kernel, *sp["fac"], st)
+                self._sp_split(layer, self.subpixel[layer.name], params[2 * layer.param_index], st)
         if cache["table"] is not None:
             _clx.call("clx_pack_weights_batch", _clx.ptr(cache["table"]), cache["njobs"], cache["biggest"], st)
-        for layer in cache["singles"]:
-            self._pack_layer(layer, params[2 * layer.param_index], need_dgrad, st)
-        self._split_wplanes(need_dgrad, st)
+        for layer, copy, jobs in cache["singles"]:
+            self._pack_one(layer, copy, jobs, params, st)
 
     def pack_weights(self, params, version, need_dgrad):
         """(Re)pack weights when the parameters changed (version = tuple of tensor versions)."""
         if need_dgrad and not self._bwd_ready:
             self._alloc_backward()
-        key = (version, need_dgrad)
         if self._packed_version is not None and self._packed_version[0] == version and \
                 (self._packed_version[1] or not need_dgrad):
             return
         st = _clx.stream_ptr(self.device)
         if os.environ.get("CLX_PACK_BATCH", "1") != "0":
             self._pack_batched(params, need_dgrad, st)
-            self._packed_version = key
-            return
-        for layer in self.topo.convs:
-            w = params[2 * layer.param_index]
-            if layer.name in self.subpixel:
-                self._sp_pack(layer, self.subpixel[layer.name], w, need_dgrad, st)
-                continue
-            self._pack_layer(layer, w, need_dgrad, st)
+        else:
+            for layer, copy, jobs in self._pack_jobs(params, need_dgrad):
+                if layer.name in self.subpixel:
+                    self._sp_split(layer, self.subpixel[layer.name], params[2 * layer.param_index], st)
+                self._pack_one(layer, copy, jobs, params, st)
         self._split_wplanes(need_dgrad, st)
-        self._packed_version = key
+        self._packed_version = (version, need_dgrad)
 
     # ----------------------------------------------------------------- forward
     # ------------------------------------------------- changed rows of noisy copies (csrc/sparse_rows.hip)
@@ -1418,14 +1347,11 @@ class UNetPlan:
     def _conv_forward(self, op, params, st, tiles=None):
         """one plain convolution layer of the forward pass (tiles = (int32 tensor, count): a Winograd layer computes the
         listed output tiles only)"""
-        d = self._desc(op)
-        d.N = op.cout
+        d = self._desc(op, op.cout)
         self._set_wpack(d, self.wpack_fwd[op.name])
         b = params[2 * op.param_index + 1]
         d.bias = b.data_ptr() if b is not None else None
         d.relu = 1 if op.relu else 0
-        d.mask = None
-        d.ld_mask = 0
         d.out = self.buf[op.out].data_ptr()
         d.ld_out = pad4(op.cout)
         if op.relu and self.keep:
@@ -1496,22 +1422,9 @@ class UNetPlan:
                 _clx.call("clx_gather_rows", _clx.ptr(src), width, _clx.ptr(rows), n, width, _clx.ptr(cur), width, st)
             for k, op in enumerate(tail):
                 y = self._compact(1 + k % 2, n, pad4(op.cout))
-                d = ClxConvDesc()
-                d.nsrc = 1
-                src_d = ClxSrc()
-                src_d.ptr = cur.data_ptr()
-                src_d.C = src_d.ld = cur.shape[1]
-                src_d.D, src_d.H, src_d.W = 1, 1, n
-                src_d.oz = src_d.oy = src_d.ox = 0
-                src_d.fz = src_d.fy = src_d.fx = 1
-                d.src[0] = src_d
-                d.B = 1
-                d.ID, d.IH, d.IW = 1, 1, n
-                d.KD = d.KH = d.KW = 1
-                d.PD = d.PH = d.PW = 0
-                d.N = op.cout
+                d = conv_desc([conv_src(cur.data_ptr(), cur.shape[1], cur.shape[1], (1, 1, n))], 1, (1, 1, n), (1, 1, 1),
+                              (0, 0, 0), op.cout, self.precision)
                 self._set_wpack(d, self.wpack_fwd[op.name])
-                d.precision = self.precision
                 if self.precision and self.aplanes is not None:       # (n <= the dense tensor's rows: the scratch fits)
                     d.aplanes = self.aplanes.data_ptr()
                 b = params[2 * op.param_index + 1]
@@ -1645,8 +1558,6 @@ class UNetPlan:
                   pad4(layer.cout), 1, st)
         dd = self._dgrad_desc(layer, dy)
         dd.wpack = wp.data_ptr()
-        dd.mask = None
-        dd.ld_mask = 0
         dd.out = px.data_ptr()
         dd.ld_out = layer.cin_pad
         _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
@@ -1668,10 +1579,7 @@ class UNetPlan:
         _clx.call("clx_planar_to_pixel", _clx.ptr(dout), _clx.ptr(self.gbuf["h1"]), self.B,
                   t.out_channels, npix_out, pad4(t.out_channels), st)
 
-        by_out = {layer.out: layer for layer in t.convs}
-        pool_by_out = {p.out: p for p in t.pools}
-        r_by_conv0 = {info["conv0"].name: info for info in t.r_info}
-        pending_skip = {}   # skip tensor name -> (cat gbuf name, conv0 layer)
+        pending_skip = {}   # skip tensor name -> (gradient buffer of its consumer's input, its row length, that layer)
         dy_planes_of = {}   # tensor name -> buffer that holds the P3 planes of its gradient (split precision)
 
         # reverse execution order; gbuf[x] holds dL/d(pre-activation of x)
@@ -1684,122 +1592,126 @@ class UNetPlan:
                 continue                                    # done with its successor
             if layer.name in self.chain_second:
                 a, b = self.chain_second[layer.name]
-                yield (b.param_index, a.param_index), self._chain_backward(a, b, by_out[a.sources[0].tensor], grads, st)
-                continue
-            if layer.name in self.subpixel:
+                yield (b.param_index, a.param_index), self._chain_backward(a, b, self._conv_by_out[a.sources[0].tensor],
+                                                                           grads, st)
+            elif layer.name in self.subpixel:
                 sp = self.subpixel[layer.name]
                 yield (layer.param_index,), self._sp_wgrad(layer, sp, dy, grads[2 * layer.param_index],
                                                            grads[2 * layer.param_index + 1], st)
                 dskip = self._sp_dgrad(layer, sp, dy, st)
-                pending_skip[layer.sources[0].tensor] = (dskip, sp["C0p"], layer)
-                continue
-            # ---- weight + bias gradient
-            d = self._desc(layer)
-            d.N = pad4(layer.cout)
-            gb = grads[2 * layer.param_index + 1]
-            off = self.dw_off[layer.name]
-            wino_w = self.algo[layer.name]["wgrad"]
-            wtaps = wino_taps(wino_w, layer.kernel) if wino_w else layer.taps
-            dwp = self.dwpack[off:off + wtaps * pad4(layer.cout) * layer.cin_pad]
-            adjoint = layer.name in self.adjoint
-            dual = (self.dycache is not None and wino_w and layer.param_index > 0
-                    and self.algo[layer.name]["dgrad"] == wino_w and not adjoint)
-            if wino_w:
-                self._use_workspace(d, wino_w)
-                if layer.name in self.vcache and layer.name in self._vcache_fresh:
-                    d.vcache = self.vcache[layer.name].data_ptr()
-                    d.vcache_valid = 1
-                if dual:
-                    d.dy_vcache = self.dycache.data_ptr()
-            # split precision, 1x1 layers: the planes of this layer's dY — written by the epilogue of the data gradient that
-            # produced dY (dy_planes_of, with the bias gradient as that epilogue's column sums), or split by the weight
-            # gradient below — serve the weight gradient and the data gradient
-            dy_planes = dy_planes_of.pop(layer.out, None)
-            dy_ready = dy_planes is not None
-            if dy_planes is None and self.dyplanes is not None:
-                dy_planes = self.dyplanes
-            if self.sp_pass[layer.name][2] and not wino_w:
-                d.aplanes = self.xplanes[layer.name].data_ptr()
-                d.aplanes_valid = 1 if layer.name in self._xplanes_fresh else 0
-                d.dyplanes = dy_planes.data_ptr()
-                d.dyplanes_valid = 1 if dy_ready else 0
-                if dy_ready:
-                    gb = None                       # (the bias gradient is in already)
-                dy_ready = True
-            elif dy_ready:
-                raise AssertionError("planes of dY were written for a layer whose weight gradient does not read them")
-            self._wgrad(d, dy, pad4(layer.cout), dwp, gb, layer.cout, st)
-            yield (layer.param_index,), self._unpack_step(layer, dwp, grads[2 * layer.param_index], wino_w)
-            # ---- data gradient
-            if layer.param_index == 0:
-                if dx is not None:
-                    self.first_dgrad(layer, dy, params[0], dx, st)
-                continue
-            dd = self._dgrad_desc(layer, dy)
-            self._set_wpack(dd, self.wpack_dgrad[layer.name])
-            dgrad_sp = self.sp_pass[layer.name][1] and not self.algo[layer.name]["dgrad"]
-            if dgrad_sp:
-                dd.aplanes = dy_planes.data_ptr()
-                dd.aplanes_valid = 1 if dy_ready else 0          # (left by the weight gradient above, or by the layer behind)
-            if self.algo[layer.name]["dgrad"]:
-                self._use_workspace(dd, self.algo[layer.name]["dgrad"])
-                if adjoint:                    # A dY A^T was left in the workspace by the weight-gradient call above
-                    dd.adjoint = 1
-                elif dual:                     # V of dY was written by the weight-gradient call above
-                    dd.vcache = self.dycache.data_ptr()
-                    dd.vcache_valid = 1
-            if len(layer.sources) == 2:
-                info = r_by_conv0[layer.name]
-                cat = self.gbuf["cat%d" % info["level"]]
-                dd.mask = None
-                dd.ld_mask = 0
-                dd.out = cat.data_ptr()
-                dd.ld_out = layer.cin_pad
-                _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
-                skip_s, up_s = layer.sources
-                # upsampled branch -> pre-activation gradient of the low-res tensor
-                ushape, uc = t.shapes[up_s.tensor]
-                LD, LH, LW = layer.in_shape
-                _clx.call("clx_upsample_bwd", _clx.ptr(cat), layer.cin_pad, pad4(skip_s.channels),
-                          LD, LH, LW, *up_s.crop, _clx.ptr(self.buf[up_s.tensor]),
-                          _clx.ptr(self.gbuf[up_s.tensor]), self.B, ushape[0], ushape[1], ushape[2],
-                          pad4(uc), *up_s.factor, st)
-                pending_skip[skip_s.tensor] = (cat, layer.cin_pad, layer)
+                pending_skip[layer.sources[0].tensor] = (dskip, sp.skip.Cp, layer)
             else:
-                s = layer.sources[0]
-                if s.tensor in pool_by_out:
-                    # input is a pooled tensor: dgrad -> gradient of the pool output (no gate),
-                    # then route through the max-pool, add the skip gradient, gate by ReLU.
-                    pool = pool_by_out[s.tensor]
-                    dd.mask = None
-                    dd.ld_mask = 0
-                    dd.out = self.gbuf[pool.out].data_ptr()
-                    dd.ld_out = pad4(pool.channels)
-                    _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
-                    cat, ld_cat, rl = pending_skip.pop(pool.src)
-                    skip_s = rl.sources[0]
-                    D, H, W = pool.in_shape
-                    SD, SH, SW = rl.in_shape
-                    _clx.call("clx_maxpool_bwd", _clx.ptr(self.buf[pool.src]), _clx.ptr(self.buf[pool.out]),
-                              _clx.ptr(self.gbuf[pool.out]), _clx.ptr(cat), ld_cat, SD, SH, SW,
-                              *skip_s.crop, _clx.ptr(self.gbuf[pool.src]), self.B, D, H, W,
-                              pad4(pool.channels), *pool.factor, st)
-                else:
-                    prev = by_out[s.tensor]
-                    self._set_mask(dd, prev.out, relu=prev.relu)
-                    dd.out = self.gbuf[prev.out].data_ptr()
-                    dd.ld_out = pad4(prev.cout)
-                    if (dgrad_sp and prev.name in self.xplanes and self.sp_pass[prev.name][2]
-                            and os.environ.get("CLX_SP_EPILOGUE_PLANES", "1") != "0"):
-                        # the epilogue writes the planes of prev's dY and adds prev's bias gradient (its column sums): prev
-                        # is a split 1x1 layer (xplanes: not one of a fused pair) whose weight gradient reads those planes
-                        other = self.dyplanes2 if dy_planes is self.dyplanes else self.dyplanes
-                        dd.out_planes = other.data_ptr()
-                        gbp = grads[2 * prev.param_index + 1]
-                        dd.out_colsum = gbp.data_ptr() if gbp is not None else None
-                        dy_planes_of[prev.out] = other
-                    _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
+                unpack, dy_planes, dy_ready = self._layer_wgrad(layer, dy, grads, dy_planes_of, st)
+                yield (layer.param_index,), unpack
+                if layer.param_index > 0:
+                    self._layer_dgrad(layer, dy, grads, dy_planes, dy_ready, dy_planes_of, pending_skip, st)
+                elif dx is not None:
+                    self.first_dgrad(layer, dy, params[0], dx, st)
         assert not pending_skip
+
+    def _dy_dual(self, layer):
+        """weight and data gradient of a Winograd layer from ONE transform of dY, kept in self.dycache?"""
+        a = self.algo[layer.name]
+        return bool(self.dycache is not None and a["wgrad"] and layer.param_index > 0 and a["dgrad"] == a["wgrad"]
+                    and layer.name not in self.adjoint)
+
+    def _layer_wgrad(self, layer, dy, grads, dy_planes_of, st):
+        """weight + bias gradient of a plain layer -> (unpack(stream), dy_planes, dy_ready): the buffer for the P3 planes
+        of dy (split precision) and whether it holds them now, for the layer's data gradient"""
+        d = self._desc(layer, pad4(layer.cout))
+        gb = grads[2 * layer.param_index + 1]
+        off = self.dw_off[layer.name]
+        wino_w = self.algo[layer.name]["wgrad"]
+        dwp = self.dwpack[off:off + packed_taps(wino_w, layer.kernel) * pad4(layer.cout) * layer.cin_pad]
+        if wino_w:
+            self._use_workspace(d, wino_w)
+            if layer.name in self.vcache and layer.name in self._vcache_fresh:
+                d.vcache = self.vcache[layer.name].data_ptr()
+                d.vcache_valid = 1
+            if self._dy_dual(layer):
+                d.dy_vcache = self.dycache.data_ptr()
+        # split precision, 1x1 layers: the planes of this layer's dY — written by the epilogue of the data gradient that
+        # produced dY (dy_planes_of, with the bias gradient as that epilogue's column sums), or split by the weight
+        # gradient below — serve the weight gradient and the data gradient
+        dy_planes = dy_planes_of.pop(layer.out, None)
+        dy_ready = dy_planes is not None
+        if dy_planes is None and self.dyplanes is not None:
+            dy_planes = self.dyplanes
+        if self.sp_pass[layer.name][2] and not wino_w:
+            d.aplanes = self.xplanes[layer.name].data_ptr()
+            d.aplanes_valid = 1 if layer.name in self._xplanes_fresh else 0
+            d.dyplanes = dy_planes.data_ptr()
+            d.dyplanes_valid = 1 if dy_ready else 0
+            if dy_ready:
+                gb = None                       # (the bias gradient is in already)
+            dy_ready = True
+        elif dy_ready:
+            raise AssertionError("planes of dY were written for a layer whose weight gradient does not read them")
+        self._wgrad(d, dy, pad4(layer.cout), dwp, gb, layer.cout, st)
+        return self._unpack_step(layer, dwp, grads[2 * layer.param_index], wino_w), dy_planes, dy_ready
+
+    def _layer_dgrad(self, layer, dy, grads, dy_planes, dy_ready, dy_planes_of, pending_skip, st):
+        """data gradient of a plain layer (after _layer_wgrad, which leaves it the transformed dY or its planes), routed
+        to what produced the layer's input: a concatenation, a pooling, or a convolution"""
+        t = self.topo
+        dd = self._dgrad_desc(layer, dy)
+        self._set_wpack(dd, self.wpack_dgrad[layer.name])
+        code = self.algo[layer.name]["dgrad"]
+        dgrad_sp = self.sp_pass[layer.name][1] and not code
+        if dgrad_sp:
+            dd.aplanes = dy_planes.data_ptr()
+            dd.aplanes_valid = 1 if dy_ready else 0          # (left by the weight gradient, or by the layer behind)
+        if code:
+            self._use_workspace(dd, code)
+            if layer.name in self.adjoint:      # A dY A^T was left in the workspace by the weight-gradient call
+                dd.adjoint = 1
+            elif self._dy_dual(layer):          # V of dY was written by the weight-gradient call
+                dd.vcache = self.dycache.data_ptr()
+                dd.vcache_valid = 1
+        s = layer.sources[0]
+        pool = self._pool_by_out.get(s.tensor)
+        if len(layer.sources) == 2:
+            level = [i["level"] for i in t.r_info if i["conv0"] is layer][0]
+            out, ld_out = self.gbuf["cat%d" % level], layer.cin_pad
+        elif pool is not None:
+            # input is a pooled tensor: dgrad -> gradient of the pool output (no gate),
+            # then route through the max-pool, add the skip gradient, gate by ReLU.
+            out, ld_out = self.gbuf[pool.out], pad4(pool.channels)
+        else:
+            prev = self._conv_by_out[s.tensor]
+            out, ld_out = self.gbuf[prev.out], pad4(prev.cout)
+            self._set_mask(dd, prev.out, relu=prev.relu)
+            if (dgrad_sp and prev.name in self.xplanes and self.sp_pass[prev.name][2]
+                    and os.environ.get("CLX_SP_EPILOGUE_PLANES", "1") != "0"):
+                # the epilogue writes the planes of prev's dY and adds prev's bias gradient (its column sums): prev
+                # is a split 1x1 layer (xplanes: not one of a fused pair) whose weight gradient reads those planes
+                other = self.dyplanes2 if dy_planes is self.dyplanes else self.dyplanes
+                dd.out_planes = other.data_ptr()
+                gbp = grads[2 * prev.param_index + 1]
+                dd.out_colsum = gbp.data_ptr() if gbp is not None else None
+                dy_planes_of[prev.out] = other
+        dd.out = out.data_ptr()
+        dd.ld_out = ld_out
+        _clx.call("clx_conv_fwd", ctypes.byref(dd), st)
+        if len(layer.sources) == 2:
+            skip_s, up_s = layer.sources
+            # upsampled branch -> pre-activation gradient of the low-res tensor
+            ushape, uc = t.shapes[up_s.tensor]
+            LD, LH, LW = layer.in_shape
+            _clx.call("clx_upsample_bwd", _clx.ptr(out), layer.cin_pad, pad4(skip_s.channels),
+                      LD, LH, LW, *up_s.crop, _clx.ptr(self.buf[up_s.tensor]),
+                      _clx.ptr(self.gbuf[up_s.tensor]), self.B, ushape[0], ushape[1], ushape[2],
+                      pad4(uc), *up_s.factor, st)
+            pending_skip[skip_s.tensor] = (out, layer.cin_pad, layer)
+        elif pool is not None:
+            cat, ld_cat, rl = pending_skip.pop(pool.src)
+            skip_s = rl.sources[0]
+            D, H, W = pool.in_shape
+            SD, SH, SW = rl.in_shape
+            _clx.call("clx_maxpool_bwd", _clx.ptr(self.buf[pool.src]), _clx.ptr(self.buf[pool.out]),
+                      _clx.ptr(out), _clx.ptr(cat), ld_cat, SD, SH, SW,
+                      *skip_s.crop, _clx.ptr(self.gbuf[pool.src]), self.B, D, H, W,
+                      pad4(pool.channels), *pool.factor, st)
 
 
 def _first_dgrad_kernel_wanted(layer):

@@ -707,9 +707,9 @@ def test_winograd_forward_backward_match_oracle(name, tile, device, monkeypatch)
     else:
         assert any(a["wgrad"] for a in plan.algo.values()) and any(a["dgrad"] for a in plan.algo.values())
     if tile == "4" and name != "2d_two_levels":      # the 2x2 low-res conv of the sub-pixel form: F(4x4, 2x2)
-        assert plan.subpixel and all(sp["wino"] == 2 and sp["wino_skip"] == 2 for sp in plan.subpixel.values())
+        assert plan.subpixel and all(sp.low.wino == 2 and sp.skip.wino == 2 for sp in plan.subpixel.values())
         if name.startswith("3d"):          # ... and, in 3-D, the skip half's data gradient
-            assert all(sp["wino_skip_dgrad"] == 2 for sp in plan.subpixel.values())
+            assert all(sp.skip.wino_dgrad == 2 for sp in plan.subpixel.values())
     for (n, po), (_, pm) in zip(oracle.named_parameters(), model.named_parameters()):
         g_ref, g = po.grad, pm.grad.cpu().double()
         l2 = ((g - g_ref).norm() / (g_ref.norm() + 1e-12)).item()
@@ -770,7 +770,7 @@ def test_subpixel_rewrite_is_selected_and_exact(device):
     plan = next(iter(model._plans.values()))
     assert len(plan.subpixel) == 1
     sp = next(iter(plan.subpixel.values()))
-    assert sp["P"] == 8 and sp["zk"] == (2, 2, 2)
+    assert sp.P == 8 and sp.low.kernel == (2, 2, 2)
     assert (got - ref).abs().max().item() < 1e-4
 
 

@@ -31,7 +31,7 @@ def child():
                          checksum=float(emb.double().abs().sum()))
         plan = next(iter(model._plans.values()))
         out[size]["algo_fwd"] = {n: a["fwd"] for n, a in plan.algo.items() if a["fwd"]}
-        out[size]["subpixel"] = {n: [sp["wino"], sp["wino_skip"], sp["fused_z"], sp["fused_skip"]] for n, sp in plan.subpixel.items()}
+        out[size]["subpixel"] = {n: [sp.low.wino, sp.skip.wino, sp.low.fused, sp.skip.fused] for n, sp in plan.subpixel.items()}
     print(json.dumps(out))
 
 
