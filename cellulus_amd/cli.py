@@ -1,4 +1,5 @@
-"""Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27)."""
+"""Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
+(``python -m cellulus_amd.measure <toml>``)."""
 
 import click
 import tomli
@@ -26,3 +27,11 @@ def infer(config_file):
     from .infer import infer as infer_experiment
 
     infer_experiment(ExperimentConfig(**_load(config_file)))
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
+def measure(config_file):
+    from .measure import measure as measure_experiment
+
+    measure_experiment(ExperimentConfig(**_load(config_file)).inference_config)

@@ -1,0 +1,270 @@
+"""Measure stage: the per-object table users take from ``skimage.measure.regionprops`` on the host —
+area, bounding box, centroid, covariance, equivalent diameter and mean / min / max intensity per raw
+channel — from integer sums gathered in one pass over the label map on the device
+(``csrc/measure.hip``: ``clx_region_moments``, ``clx_region_intensity``).  The sums are exact integers, so
+the only rounding in a column is its final division.
+
+    python -m cellulus_amd.measure experiment.toml
+
+writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt``.
+"""
+
+import math
+
+import numpy as np
+
+from . import _clx
+
+MAX_IDS = 1 << 24                       # clx_region_moments / clx_region_intensity: nid <= 2^24
+_SHIFT_MIN, _SHIFT_MAX = -1022, 1023    # 2.0 ** shift stays a normal float64: scaling by it is exact
+
+
+def intensity_shift(max_abs, npix):
+    """Binary scale for ``clx_region_intensity``: with ``q = rint(v * 2**shift)``, every ``|v| <= max_abs`` gives
+    ``|q| <= 2**(62 - L)``, ``L = npix.bit_length()``, so that a sum over up to ``npix`` pixels stays below ``2**62``.
+    ``shift = 62 - L - E`` with ``E`` the smallest integer such that ``max_abs <= 2**E`` (the ``frexp`` exponent, one
+    less for an exact power of two, whose ``q`` lands on the bound itself); the largest shift the kernel's per-pixel
+    bound admits.  0 for ``max_abs == 0``; clamped to [-1022, 1023] so that ``ldexp`` stays finite and exact."""
+    max_abs = float(max_abs)
+    if not (max_abs >= 0.0 and math.isfinite(max_abs)):
+        raise ValueError(f"intensity_shift: max_abs must be finite and >= 0, got {max_abs}")
+    if int(npix) < 1:
+        raise ValueError(f"intensity_shift: npix must be >= 1, got {npix}")
+    if max_abs == 0.0:
+        return 0
+    mant, exp = math.frexp(max_abs)
+    if mant == 0.5:
+        exp -= 1
+    return max(_SHIFT_MIN, min(_SHIFT_MAX, 62 - int(npix).bit_length() - exp))
+
+
+_AXES = ("z", "y", "x")
+_PAIRS = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))        # order of sum2: zz yy xx zy zx yx
+
+
+def _exact_div(num, den):
+    """Element-wise ``num / den`` of Python-int object arrays as float64: one correctly rounded division each."""
+    return np.array([n / d for n, d in zip(num, den)], dtype=np.float64)
+
+
+def shape_columns(label, area, bbox, sum1, sum2, nd):
+    """The geometric columns of ``region_table`` from integer moments.  label (n), area (n), bbox (n, 6) inclusive
+    ``zmin ymin xmin zmax ymax xmax``, sum1 (n, 3) ``Σz Σy Σx``, sum2 (n, 6) ``Σzz Σyy Σxx Σzy Σzx Σyx``; nd 2 or 3
+    (2-D: the z entries are ignored).  Covariance numerators ``area·Σab − Σa·Σb`` are exact Python integers."""
+    assert nd in (2, 3)
+    label = np.asarray(label)
+    n = len(label)
+    area_o = np.asarray(area).astype(object).reshape(n)
+    bbox = np.asarray(bbox).reshape(n, 6)
+    s1 = np.asarray(sum1).astype(object).reshape(n, 3)
+    s2 = np.asarray(sum2).astype(object).reshape(n, 6)
+    axes = range(3 - nd, 3)
+    cols = {"label": label.astype(np.int64), "area": np.asarray(area).astype(np.int64).reshape(n)}
+    for a in axes:
+        cols[f"bbox_min_{_AXES[a]}"] = bbox[:, a].astype(np.int64)
+    for a in axes:
+        cols[f"bbox_max_{_AXES[a]}"] = bbox[:, 3 + a].astype(np.int64) + 1          # exclusive, as in skimage
+    for a in axes:
+        cols[f"centroid_{_AXES[a]}"] = _exact_div(s1[:, a], area_o)
+    cov = np.zeros((n, 3, 3), dtype=np.float64)
+    area_sq = area_o * area_o
+    for k, (a, b) in enumerate(_PAIRS):
+        if a < 3 - nd:
+            continue
+        c = _exact_div(area_o * s2[:, k] - s1[:, a] * s1[:, b], area_sq)
+        cov[:, a, b] = cov[:, b, a] = c
+        cols[f"cov_{_AXES[a]}{_AXES[b]}"] = c
+    eig = np.linalg.eigvalsh(cov[:, 3 - nd:, 3 - nd:])[:, ::-1] if n else np.zeros((0, nd))
+    for i in range(nd):
+        cols[f"cov_eig_{i}"] = np.ascontiguousarray(eig[:, i])
+    a = cols["area"].astype(np.float64)
+    cols["equivalent_diameter"] = np.sqrt(4.0 * a / np.pi) if nd == 2 else np.cbrt(6.0 * a / np.pi)
+    return cols
+
+
+def _to_device_labels(labels, device):
+    import torch
+
+    if torch.is_tensor(labels):
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.dtype.is_complex:
+            raise TypeError(f"region_table: labels must be integers, got {labels.dtype}")
+        lab = labels.to(device)
+        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= MAX_IDS):
+            raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+        return lab.to(torch.int32).contiguous()
+    labels = np.ascontiguousarray(labels)
+    if labels.dtype.kind not in "ui":
+        raise TypeError(f"region_table: labels must be integers, got {labels.dtype}")
+    if labels.size and (int(labels.min()) < 0 or int(labels.max()) >= MAX_IDS):
+        raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+    return torch.from_numpy(labels.astype(np.int32)).to(device)
+
+
+def _to_device_raw(channel, device):
+    import torch
+
+    from .segment import _RAW_F32, _RAW_F64, _RAW_I32, _raw_to_device
+
+    if not torch.is_tensor(channel):
+        return _raw_to_device(channel, device)
+    if channel.dtype == torch.float32:
+        return channel.to(device).contiguous(), _RAW_F32
+    if channel.dtype == torch.float64:
+        return channel.to(device).contiguous(), _RAW_F64
+    if channel.dtype.is_floating_point or channel.dtype.is_complex or channel.dtype == torch.bool:
+        raise TypeError(f"region_table: unsupported raw dtype {channel.dtype}")
+    c = channel.to(device)
+    if c.numel() and (int(c.min()) < -2 ** 31 or int(c.max()) >= 2 ** 31):
+        raise ValueError("region_table: integer raw values must fit in int32")
+    return c.to(torch.int32).contiguous(), _RAW_I32
+
+
+def _intensity(lab, raw_d, raw_type, nid, shift):
+    """One clx_region_intensity call -> (isum int64 (nid), keys uint64 (nid, 2), bad)."""
+    import torch
+
+    dev = lab.device
+    isum = torch.empty(nid, dtype=torch.int64, device=dev)
+    vkey = torch.empty((nid, 2), dtype=torch.int64, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    _clx.call("clx_region_intensity", _clx.ptr(lab), _clx.ptr(raw_d), raw_type, lab.numel(), nid, int(shift),
+              _clx.ptr(isum), _clx.ptr(vkey), _clx.ptr(bad), _clx.stream_ptr(dev))
+    return isum.cpu().numpy(), vkey.cpu().numpy().view(np.uint64), int(bad.item())
+
+
+def _channel_columns(lab, raw_d, raw_type, nid, present, area, k):
+    from .segment import _RAW_I32, _decode_keys
+    from .utils.otsu import minmax_on_device
+
+    npix = lab.numel()
+    shift = 0
+    if raw_type != _RAW_I32:
+        lo, hi = minmax_on_device(raw_d.reshape(-1))
+        max_abs = max(abs(lo), abs(hi))
+        if not math.isfinite(max_abs):
+            # something outside the objects is not finite: take the maximum under the objects from the keys of a first
+            # call whose scale lets every finite value pass
+            _, keys, bad = _intensity(lab, raw_d, raw_type, nid, _SHIFT_MIN)
+            if bad & 2:
+                raise ValueError(f"region_table: raw channel {k} has non-finite values inside objects")
+            vals = _decode_keys(keys[present], raw_type).astype(np.float64)
+            max_abs = float(np.abs(vals).max()) if vals.size else 0.0
+        shift = intensity_shift(max_abs, npix)
+    isum, keys, bad = _intensity(lab, raw_d, raw_type, nid, shift)
+    if bad & 2:
+        raise ValueError(f"region_table: raw channel {k} has non-finite values inside objects")
+    if bad & 1:
+        raise ValueError("region_table: label ids changed under the measurement")
+    vals = _decode_keys(keys[present], raw_type)
+    mean = _exact_div(isum[present].astype(object), area[present].astype(object))
+    if shift:
+        mean = np.ldexp(mean, -shift)
+    return {f"intensity_mean_c{k}": mean, f"intensity_min_c{k}": vals[:, 0].copy(), f"intensity_max_c{k}": vals[:, 1].copy()}
+
+
+def region_table(labels, raw=None, device=None):
+    """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
+    ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
+    ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
+    float64 or integers that fit int32), ``intensity_mean_c{k}, intensity_min_c{k}, intensity_max_c{k}``.
+    Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
+    import torch
+
+    if torch.is_tensor(labels) and labels.is_cuda:
+        device = labels.device
+    elif device is None:
+        if not torch.cuda.is_available():
+            raise _clx.ClxError("measure needs a HIP device; cellulus_amd has no CPU path")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _clx.ClxError(f"measure needs a HIP device, got {device}; cellulus_amd has no CPU path")
+    nd = labels.ndim
+    if nd not in (2, 3):
+        raise ValueError(f"region_table: labels must be 2-D or 3-D, got {nd} dimensions")
+    spatial = tuple(labels.shape)
+    lab = _to_device_labels(labels, device)
+    _clx.require_device(lab, "labels")
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    nid = int(lab.max().item()) + 1 if lab.numel() else 1
+    if lab.numel() == 0 or nid == 1:
+        area = np.zeros(1, dtype=np.int64)
+        cols = shape_columns(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, 6), np.int32),
+                             np.zeros((0, 3), np.uint64), np.zeros((0, 6), np.uint64), nd)
+        present = np.zeros(0, dtype=np.int64)
+    else:
+        area_d = torch.empty(nid, dtype=torch.int64, device=device)
+        bbox_d = torch.empty((nid, 6), dtype=torch.int32, device=device)
+        sum1_d = torch.empty((nid, 3), dtype=torch.int64, device=device)
+        sum2_d = torch.empty((nid, 6), dtype=torch.int64, device=device)
+        bad_d = torch.empty(1, dtype=torch.int32, device=device)
+        _clx.call("clx_region_moments", _clx.ptr(lab), Z, Y, X, nid, _clx.ptr(area_d), _clx.ptr(bbox_d),
+                  _clx.ptr(sum1_d), _clx.ptr(sum2_d), _clx.ptr(bad_d), _clx.stream_ptr(device))
+        if int(bad_d.item()):
+            raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+        area = area_d.cpu().numpy()
+        area[0] = 0
+        present = np.flatnonzero(area > 0)
+        cols = shape_columns(present, area[present], bbox_d.cpu().numpy()[present],
+                             sum1_d.cpu().numpy().view(np.uint64)[present],
+                             sum2_d.cpu().numpy().view(np.uint64)[present], nd)
+    if raw is not None:
+        if tuple(raw.shape) == spatial:
+            raw = raw[None]
+        if tuple(raw.shape[1:]) != spatial:
+            raise ValueError(f"region_table: raw has shape {tuple(raw.shape)}, labels {spatial}")
+        for k in range(raw.shape[0]):
+            raw_d, raw_type = _to_device_raw(raw[k], device)
+            if len(present):
+                cols.update(_channel_columns(lab.reshape(-1), raw_d.reshape(-1), raw_type, nid, present, area, k))
+            else:
+                dt = raw_d.cpu().numpy().dtype
+                cols.update({f"intensity_mean_c{k}": np.zeros(0), f"intensity_min_c{k}": np.zeros(0, dt),
+                             f"intensity_max_c{k}": np.zeros(0, dt)})
+    return cols
+
+
+def _format(value):
+    return "%.17g" % value if isinstance(value, (float, np.floating)) else "%d" % value
+
+
+def measure(inference_config) -> None:
+    """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
+    every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
+    then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  Rank 0 works alone under torch.distributed."""
+    import torch
+
+    from . import parallel
+    from .datasets.meta_data import DatasetMetaData
+    from .train import _require_hip_device
+    from .utils import zarr_io
+
+    if parallel.rank() != 0:
+        return
+    dataset_config = inference_config.dataset_config
+    meta = DatasetMetaData.from_dataset_config(dataset_config)
+    device = _require_hip_device(inference_config.device)
+    if parallel.world_size() > 1:
+        device = torch.device("cuda", torch.cuda.current_device())
+    seg_config = inference_config.segmentation_dataset_config
+    ds_seg = zarr_io.open(seg_config.container_path, "r")[seg_config.dataset_name]
+    ds_raw = zarr_io.open(dataset_config.container_path, "r")[dataset_config.dataset_name]
+    for bandwidth in range(inference_config.num_bandwidths):
+        header, lines = None, []
+        for sample in range(meta.num_samples):
+            labels = ds_seg[sample, bandwidth].astype(np.int32)
+            table = region_table(labels, ds_raw[sample], device)
+            header = header or ["sample"] + list(table)
+            columns = list(table.values())
+            for i in range(len(table["label"])):
+                lines.append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
+        with open(f"measurements_bandwidth-{bandwidth}.csv", "w") as out:
+            out.write(",".join(header or ["sample"]) + "\n")
+            for line in lines:
+                out.write(line + "\n")
+
+
+if __name__ == "__main__":
+    from .cli import measure as _command
+
+    _command()

@@ -896,6 +896,37 @@ int clx_joint_histogram(const int32_t* pred, const int32_t* gt, long long n,
                         unsigned long long* joint, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* measure stage: the per-object table of skimage.measure.regionprops (area, */
+/* bbox, centroid, second moments, mean / min / max intensity) as integer    */
+/* sums taken in one pass over the label map — no host copy of the map       */
+/* ------------------------------------------------------------------------ */
+/* Geometry of every id in [1, nid) of a label map [Z][Y][X] (2-D: Z = 1); replaces the coordinate lists behind
+ * regionprops' area / bbox / centroid / inertia_tensor.  The entry point initialises ALL outputs itself (nothing
+ * depends on what the buffers held); row 0 (background) of every output is unspecified.
+ *   area [nid]     pixel count (0: id absent)
+ *   bbox [nid][6]  zmin,ymin,xmin,zmax,ymax,xmax, inclusive; max < 0: id absent (clx_inst_stats' convention)
+ *   sum1 [nid][3]  Σz, Σy, Σx          sum2 [nid][6]  Σzz, Σyy, Σxx, Σzy, Σzx, Σyx
+ *   bad  [1]       1: a label outside [0, nid) — never followed as an index, that pixel is skipped
+ * Integer accumulators only: the same map gives the same bits in every run.  Refused (CLX_ERR_ARG) before any launch:
+ * null pointers, nid outside [1, 2^24], Z*Y*X >= 2^32, (max(Z,Y,X) - 1)^2 * Z*Y*X >= 2^63 (the second moments would
+ * not fit in 64 bits). */
+int clx_region_moments(const int32_t* labels, int Z, int Y, int X, int nid,
+                       unsigned long long* area, int32_t* bbox, unsigned long long* sum1,
+                       unsigned long long* sum2, int32_t* bad, clx_stream stream);
+/* One raw channel (npix values of `raw_type`) over the same labels; replaces regionprops' mean / min / max_intensity.
+ * Outputs are initialised by the entry point, row 0 is unspecified.
+ *   isum [nid]     Σ q over the id's pixels.  CLX_RAW_I32: q = v, exact, `shift` ignored.  CLX_RAW_F32 / _F64:
+ *                  q = (long long) rint(ldexp((double) v, shift)); the caller picks `shift` so that the sum fits
+ *                  (cellulus_amd.measure.intensity_shift) and divides Σ q by 2^shift
+ *   vkey [nid][2]  min, max as clx_inst_stats' order-preserving keys ({~0, 0}: id absent)
+ *   bad  [1]       bit 0: a label outside [0, nid); bit 1: a value under an object id that is NaN, ±Inf or has
+ *                  |q| > 2^62 >> bit_length(npix) (a wrong `shift` cannot overflow silently).  Such pixels are skipped.
+ * Refused before any launch: null pointers, unknown raw_type, nid outside [1, 2^24], npix outside [1, 2^32). */
+int clx_region_intensity(const int32_t* labels, const void* raw, int raw_type, long long npix,
+                         int nid, int shift, long long* isum, unsigned long long* vkey,
+                         int32_t* bad, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
