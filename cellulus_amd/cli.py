@@ -1,5 +1,5 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
-(``python -m cellulus_amd.measure <toml>``)."""
+(``python -m cellulus_amd.measure <toml> [--contacts]``)."""
 
 import click
 import tomli
@@ -31,7 +31,8 @@ def infer(config_file):
 
 @click.command()
 @click.argument("config_file", type=click.Path(exists=True))
-def measure(config_file):
+@click.option("--contacts", is_flag=True, help="add the boundary columns and write contacts_bandwidth-<b>.csv")
+def measure(config_file, contacts):
     from .measure import measure as measure_experiment
 
-    measure_experiment(ExperimentConfig(**_load(config_file)).inference_config)
+    measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts)

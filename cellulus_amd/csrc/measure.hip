@@ -3,7 +3,9 @@
 // gathered in one pass over the label map on the device:
 //   clx_region_moments    pixel count, bounding box, Σ coordinate and Σ coordinate products per id
 //   clx_region_intensity  Σ quantised value and min / max (order-preserving keys) of one raw channel per id
-// Both kernels share one structure.  A lane reads 4 consecutive pixels; a lane whose pixels all carry one
+//   clx_region_contacts   faces between pixels of different ids, per id pair (a stencil; further down)
+//   clx_region_perimeter  border pixels of every object by neighbourhood class (2-D; further down)
+// The first two kernels share one structure.  A lane reads 4 consecutive pixels; a lane whose pixels all carry one
 // object id (and lie in one image row, for the moments) is "uniform".  A ballot over the wave cuts the 64 lanes
 // into runs of uniform lanes with the same id (and row); the first lane of a run owns it.  The geometric sums
 // of a run follow in closed form from its start and length, the intensities from a segmented wave reduction.
@@ -327,6 +329,278 @@ __global__ __launch_bounds__(BLOCK) void intensity_kernel(const int* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Contacts: every face (connectivity 1) between two pixels of different ids counts once for the pair (lo, hi); the
+// outside of the image is id 0.  A pixel owns its forward faces (+x, +y, +z; past the last column / row / slice the
+// neighbour is 0) and, in the first column / row / slice, the backward face to 0.  The output is a SET of pairs of
+// unknown size: an open-addressing table in global memory keyed by (lo << 32) | hi (never 0, as hi >= 1), filled through
+// a block-private table in LDS that is flushed once.  A lane whose pixels and forward neighbours all carry one id away
+// from the image edge has nothing to emit; a wave of such lanes skips the rest of the trip.
+
+constexpr int CSLOTS = 512;             // pairs a block keeps in LDS (power of two)
+constexpr int CPROBES = 8;
+constexpr unsigned int GPROBES = 4096;  // slots tried in the global table before the result is declared lost
+
+struct ContactsOut {
+  u64* keys;
+  u64* counts;
+  int* info;                            // [0] bit 0: label outside [0, nid); bit 2: a pair was not placed.  [1] occupied slots
+  unsigned int mask, probes;            // capacity - 1; min(capacity, GPROBES)
+};
+
+__device__ __forceinline__ u64 mix64(u64 k) {   // MurmurHash3's finaliser: ids of neighbours are close, their keys must not be
+  k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+  return k ^ (k >> 33);
+}
+
+// n faces of `key` into the global table.  Bounded: at most o.probes slots, all inside [0, capacity); a pair that finds
+// neither its key nor an empty slot sets bit 2 and is dropped (the caller discards the table).  A stale read of a key
+// can only show 0 for a claimed slot, which the compare-and-swap corrects; a claimed key never changes.
+__device__ void pair_to_global(const ContactsOut& o, u64 key, u64 n, u64 h) {
+  unsigned int s = (unsigned int)(h >> 32) & o.mask;
+  for (unsigned int i = 0; i < o.probes; ++i) {
+    u64 k = __hip_atomic_load(&o.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == 0) {
+      k = atomicCAS(&o.keys[s], 0ull, key);
+      if (k == 0) atomicAdd(o.info + 1, 1);
+    }
+    if (k == 0 || k == key) { atomicAdd(&o.counts[s], n); return; }
+    s = (s + 1) & o.mask;
+  }
+  atomicOr(o.info, 4);
+}
+
+__device__ void add_pair(u64* lkeys, u64* lcnt, const ContactsOut& o, u64 key, unsigned int n) {
+  const u64 h = mix64(key);
+  int s = (int)(h & (CSLOTS - 1));
+  for (int i = 0; i < CPROBES; ++i) {
+    u64 k = __hip_atomic_load(&lkeys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (k == 0) k = atomicCAS(&lkeys[s], 0ull, key);
+    if (k == 0 || k == key) { atomicAdd(&lcnt[s], (u64)n); return; }
+    s = (s + 1) & (CSLOTS - 1);
+  }
+  pair_to_global(o, key, n, h);
+}
+
+// a lane's faces in the order it meets them; equal pairs in a row (a horizontal edge gives four) become one add
+struct PairRun {
+  u64 key;
+  unsigned int n;
+};
+__device__ __forceinline__ void face(PairRun& r, u64* lkeys, u64* lcnt, const ContactsOut& o, int a, int b) {
+  if (a == b) return;
+  const u64 key = a < b ? ((u64)(unsigned int)a << 32) | (unsigned int)b : ((u64)(unsigned int)b << 32) | (unsigned int)a;
+  if (key == r.key) { ++r.n; return; }
+  if (r.n) add_pair(lkeys, lcnt, o, r.key, r.n);
+  r.key = key;
+  r.n = 1;
+}
+
+__global__ void contacts_init(ContactsOut o, long long capacity) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 2) o.info[i] = 0;
+  if (i >= capacity) return;
+  o.keys[i] = 0;
+  o.counts[i] = 0;
+}
+
+__global__ __launch_bounds__(BLOCK) void contacts_kernel(const int* __restrict__ lab, int vec, int vec_y, int vec_z, int zfaces,
+                                                         long long npix, int Z, int Y, int X, int nid, long long ntiles,
+                                                         long long tiles_per_block, ContactsOut o) {
+  __shared__ u64 lkeys[CSLOTS];
+  __shared__ u64 lcnt[CSLOTS];
+  for (int s = threadIdx.x; s < CSLOTS; s += BLOCK) { lkeys[s] = 0; lcnt[s] = 0; }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const long long plane = (long long)Y * X;
+  const long long t0 = (long long)blockIdx.x * tiles_per_block;
+  const long long t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
+  bool any_bad = false;
+  for (long long t = t0; t < t1; ++t) {
+    const long long p0 = t * TILE + (long long)threadIdx.x * PPL;
+    int l[PPL], d[PPL], u[PPL];                         // own pixels, one row down, one slice down (flat index + X, + Y*X)
+    load_labels(lab, vec != 0, p0, npix, l);
+    any_bad |= clamp_labels(l, nid);
+    load_labels(lab, vec_y != 0, p0 + X, npix, d);
+    clamp_labels(d, nid);
+    if (zfaces) {
+      load_labels(lab, vec_z != 0, p0 + plane, npix, u);
+      clamp_labels(u, nid);
+    } else {
+#pragma unroll
+      for (int k = 0; k < PPL; ++k) u[k] = l[k];
+    }
+    // the +x neighbour of the lane's last pixel: the next lane's first, or a load for the wave's last lane
+    int right = __shfl_down(l[0], 1);
+    if (lane == 63) {
+      right = p0 + PPL < npix ? lab[p0 + PPL] : 0;
+      if ((unsigned)right >= (unsigned)nid) right = 0;
+    }
+    // npix < 2^32: 32-bit divisions
+    const unsigned int pu = p0 < npix ? (unsigned int)p0 : 0u;
+    const unsigned int r = pu / (unsigned int)X;
+    int x = (int)(pu - r * (unsigned int)X);
+    int z = (int)(r / (unsigned int)Y);
+    int y = (int)(r - (unsigned int)z * (unsigned int)Y);
+
+    // away from every image edge the stored neighbours are the real ones: nothing to emit if they all equal l[0]
+    const bool interior = p0 + PPL <= npix && x > 0 && x + PPL < X && y > 0 && y + 1 < Y && (!zfaces || (z > 0 && z + 1 < Z));
+    int diff = right ^ l[0];
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) diff |= (l[k] ^ l[0]) | (d[k] ^ l[0]) | (u[k] ^ l[0]);
+    const bool noisy = p0 < npix && (!interior || diff != 0);
+    if (__ballot(noisy) == 0ull) continue;
+    if (!noisy) continue;
+
+    // per pixel: is it in the image, and on which edges
+    bool in[PPL], x_lo[PPL], x_hi[PPL], y_lo[PPL], y_hi[PPL], z_lo[PPL], z_hi[PPL];
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      in[k] = p0 + k < npix;
+      x_lo[k] = x == 0; x_hi[k] = x == X - 1;
+      y_lo[k] = y == 0; y_hi[k] = y == Y - 1;
+      z_lo[k] = z == 0; z_hi[k] = z == Z - 1;
+      if (++x == X) { x = 0; if (++y == Y) { y = 0; ++z; } }
+    }
+    PairRun run = {0ull, 0u};
+#pragma unroll
+    for (int k = 0; k < PPL; ++k)
+      if (in[k]) face(run, lkeys, lcnt, o, l[k], y_hi[k] ? 0 : d[k]);
+#pragma unroll
+    for (int k = 0; k < PPL; ++k)
+      if (in[k] && y_lo[k]) face(run, lkeys, lcnt, o, l[k], 0);
+    if (zfaces) {
+#pragma unroll
+      for (int k = 0; k < PPL; ++k)
+        if (in[k]) face(run, lkeys, lcnt, o, l[k], z_hi[k] ? 0 : u[k]);
+#pragma unroll
+      for (int k = 0; k < PPL; ++k)
+        if (in[k] && z_lo[k]) face(run, lkeys, lcnt, o, l[k], 0);
+    }
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      if (!in[k]) continue;
+      if (x_lo[k]) face(run, lkeys, lcnt, o, l[k], 0);
+      face(run, lkeys, lcnt, o, l[k], x_hi[k] ? 0 : (k < PPL - 1 ? l[(k + 1) & (PPL - 1)] : right));
+    }
+    if (run.n) add_pair(lkeys, lcnt, o, run.key, run.n);
+  }
+  if (any_bad) atomicOr(o.info, 1);
+  __syncthreads();
+
+  for (int s = threadIdx.x; s < CSLOTS; s += BLOCK)
+    if (lkeys[s]) pair_to_global(o, lkeys[s], lcnt[s], mix64(lkeys[s]));
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Perimeter (2-D): scikit-image's perimeter(mask, neighbourhood=4) restated on the full map.  A pixel of object i is a
+// border pixel if one of its 4 neighbours is not i (another object, background or the outside of the image); its code is
+// 1 + 2 n4 + 10 nd with n4 / nd the border pixels OF i among its 4 edge / 4 diagonal neighbours.  That is a 5 x 5
+// dependency: a block stages a PT x PT tile with a halo of 2 in LDS, derives the border flags of the tile plus a halo of
+// 1 (kept as the id itself, 0: no border pixel), then the codes of the tile, counted per id and weight class in the
+// id-keyed LDS table and flushed once per block.
+
+constexpr int PT = 32;                  // tile edge: PT * PT = TILE pixels, a lane takes 4 of a tile row
+constexpr int PH = PT + 4, PB = PT + 2;
+constexpr int NCLS = 4;                 // border pixels; codes of weight 1, sqrt 2, (1 + sqrt 2) / 2
+
+__device__ __forceinline__ int perimeter_class(int n4, int nd) {
+  if ((n4 == 2 || n4 == 3) && nd <= 2) return 1;        // codes 5 7 15 17 25 27
+  if ((n4 == 0 && nd == 2) || (n4 == 1 && nd == 3)) return 2;   // 21 33
+  if (n4 == 1 && (nd == 1 || nd == 2)) return 3;        // 13 23
+  return 0;
+}
+
+// `packed`: one byte per class, each at most PPL
+__device__ void add_classes(int* keys, unsigned int (*acc)[SLOTS], u64* classes, int label, unsigned int packed) {
+  const int s = find_slot(keys, label);
+#pragma unroll
+  for (int q = 0; q < NCLS; ++q) {
+    const unsigned int n = (packed >> (8 * q)) & 0xffu;
+    if (n == 0) continue;
+    if (s >= 0) atomicAdd(&acc[q][s], n);
+    else atomicAdd(classes + (size_t)label * NCLS + q, (u64)n);
+  }
+}
+
+__global__ void perimeter_init(u64* __restrict__ classes, int* __restrict__ bad, int nid) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) *bad = 0;
+  if (i >= nid) return;
+  for (int q = 0; q < NCLS; ++q) classes[(size_t)i * NCLS + q] = 0;
+}
+
+__global__ __launch_bounds__(BLOCK) void perimeter_kernel(const int* __restrict__ lab, int Y, int X, int nid, int tiles_x,
+                                                          long long ntiles, long long tiles_per_block, u64* __restrict__ classes,
+                                                          int* __restrict__ bad) {
+  __shared__ int keys[SLOTS];
+  __shared__ unsigned int acc[NCLS][SLOTS];             // a block's pixels are below 2^32
+  __shared__ int ls[PH][PH + 1];
+  __shared__ int bs[PB][PB + 1];
+  for (int s = threadIdx.x; s < SLOTS; s += BLOCK) {
+    keys[s] = 0;
+    for (int q = 0; q < NCLS; ++q) acc[q][s] = 0;
+  }
+
+  const long long t0 = (long long)blockIdx.x * tiles_per_block;
+  const long long t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
+  const int row = threadIdx.x >> 3, col = (threadIdx.x & 7) * PPL;
+  bool any_bad = false;
+  for (long long t = t0; t < t1; ++t) {
+    const int ty = (int)(t / tiles_x), tx = (int)(t - (long long)ty * tiles_x);
+    const long long y0 = (long long)ty * PT - 2, x0 = (long long)tx * PT - 2;
+    __syncthreads();                                    // the table is set up; the last trip's readers of ls / bs are done
+    for (int i = threadIdx.x; i < PH * PH; i += BLOCK) {
+      const int r = i / PH, c = i - r * PH;
+      const long long gy = y0 + r, gx = x0 + c;
+      int v = 0;
+      if (gy >= 0 && gy < Y && gx >= 0 && gx < X) {
+        v = lab[(size_t)gy * (size_t)X + (size_t)gx];
+        if ((unsigned)v >= (unsigned)nid) { v = 0; any_bad = true; }
+      }
+      ls[r][c] = v;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < PB * PB; i += BLOCK) {
+      const int r = i / PB, c = i - r * PB;             // (r + 1, c + 1) in ls
+      const int v = ls[r + 1][c + 1];
+      const bool border = v > 0 && (ls[r][c + 1] != v || ls[r + 2][c + 1] != v || ls[r + 1][c] != v || ls[r + 1][c + 2] != v);
+      bs[r][c] = border ? v : 0;
+    }
+    __syncthreads();
+    int cur = 0;
+    unsigned int packed = 0;
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      const int br = row + 1, bc = col + k + 1;         // the lane's pixel in bs
+      const int v = bs[br][bc];
+      if (v == 0) continue;
+      const int n4 = (bs[br - 1][bc] == v) + (bs[br + 1][bc] == v) + (bs[br][bc - 1] == v) + (bs[br][bc + 1] == v);
+      const int nd = (bs[br - 1][bc - 1] == v) + (bs[br - 1][bc + 1] == v) + (bs[br + 1][bc - 1] == v) + (bs[br + 1][bc + 1] == v);
+      if (v != cur) {
+        if (packed) add_classes(keys, acc, classes, cur, packed);
+        cur = v;
+        packed = 0;
+      }
+      const int cls = perimeter_class(n4, nd);
+      packed += 1u + (cls ? 1u << (8 * cls) : 0u);
+    }
+    if (packed) add_classes(keys, acc, classes, cur, packed);
+  }
+  if (any_bad) *bad = 1;
+  __syncthreads();
+
+  for (int s = threadIdx.x; s < SLOTS; s += BLOCK) {
+    const int label = keys[s];
+    if (label == 0) continue;
+#pragma unroll
+    for (int q = 0; q < NCLS; ++q)
+      if (acc[q][s]) atomicAdd(classes + (size_t)label * NCLS + q, (u64)acc[q][s]);
+  }
+}
+
 struct Tiling {
   long long ntiles, per_block;
   int grid;
@@ -389,5 +663,45 @@ extern "C" int clx_region_intensity(const int32_t* labels, const void* raw, int 
     intensity_kernel<int><<<t.grid, BLOCK, 0, st>>>(labels, (const int*)raw, vl, vr, npix, nid, shift, bound, t.ntiles,
                                                      t.per_block, isum, vkey, bad);
   CLX_CHECK_LAUNCH("clx_region_intensity");
+  return CLX_OK;
+}
+
+extern "C" int clx_region_contacts(const int32_t* labels, int nd, int Z, int Y, int X, int nid, int capacity,
+                                   unsigned long long* keys, unsigned long long* counts, int32_t* info, clx_stream stream) {
+  CLX_REQUIRE(labels && keys && counts && info, "clx_region_contacts: null pointer");
+  CLX_REQUIRE(nd == 2 || nd == 3, "clx_region_contacts: nd must be 2 or 3");
+  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_region_contacts: bad shape");
+  CLX_REQUIRE(nd == 3 || Z == 1, "clx_region_contacts: nd == 2 needs Z == 1");
+  CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_region_contacts: nid must lie in [1, 2^24]");
+  CLX_REQUIRE(capacity >= 1024 && capacity <= (1 << 28) && (capacity & (capacity - 1)) == 0,
+              "clx_region_contacts: capacity must be a power of two in [1024, 2^28]");
+  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
+  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_region_contacts: Z * Y * X must be below 2^32");
+  const long long npix = (long long)npix128;
+  hipStream_t st = (hipStream_t)stream;
+  const ContactsOut o = {keys, counts, info, (unsigned int)capacity - 1u,
+                         (unsigned int)capacity < GPROBES ? (unsigned int)capacity : GPROBES};
+  contacts_init<<<(capacity + 255) / 256, 256, 0, st>>>(o, capacity);
+  const Tiling t = tiling_for(npix);
+  const int vec = ((uintptr_t)labels & 15) == 0;
+  contacts_kernel<<<t.grid, BLOCK, 0, st>>>(labels, vec, vec && (X & 3) == 0, vec && (((long long)Y * X) & 3) == 0, nd == 3, npix,
+                                            Z, Y, X, nid, t.ntiles, t.per_block, o);
+  CLX_CHECK_LAUNCH("clx_region_contacts");
+  return CLX_OK;
+}
+
+extern "C" int clx_region_perimeter(const int32_t* labels, int Y, int X, int nid, unsigned long long* classes, int32_t* bad,
+                                    clx_stream stream) {
+  CLX_REQUIRE(labels && classes && bad, "clx_region_perimeter: null pointer");
+  CLX_REQUIRE(Y > 0 && X > 0, "clx_region_perimeter: bad shape");
+  CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_region_perimeter: nid must lie in [1, 2^24]");
+  CLX_REQUIRE((unsigned long long)Y * (unsigned long long)X < (1ull << 32), "clx_region_perimeter: Y * X must be below 2^32");
+  hipStream_t st = (hipStream_t)stream;
+  perimeter_init<<<(nid + 255) / 256, 256, 0, st>>>(classes, bad, nid);
+  const int tiles_x = (X + PT - 1) / PT;
+  const long long ntiles = (long long)((Y + PT - 1) / PT) * tiles_x;
+  const int grid = (int)(ntiles < MAX_GRID ? ntiles : MAX_GRID);
+  perimeter_kernel<<<grid, BLOCK, 0, st>>>(labels, Y, X, nid, tiles_x, ntiles, (ntiles + grid - 1) / grid, classes, bad);
+  CLX_CHECK_LAUNCH("clx_region_perimeter");
   return CLX_OK;
 }

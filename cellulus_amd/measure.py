@@ -2,11 +2,14 @@
 area, bounding box, centroid, covariance, equivalent diameter and mean / min / max intensity per raw
 channel — from integer sums gathered in one pass over the label map on the device
 (``csrc/measure.hip``: ``clx_region_moments``, ``clx_region_intensity``).  The sums are exact integers, so
-the only rounding in a column is its final division.
+the only rounding in a column is its final division.  On request also what an object's BOUNDARY gives: the faces it
+shares with every other object (``contact_pairs``: the region adjacency graph), with the background and the image edge,
+and in 2-D its border pixels and perimeter (``clx_region_contacts``, ``clx_region_perimeter``), all integer counts too.
 
-    python -m cellulus_amd.measure experiment.toml
+    python -m cellulus_amd.measure experiment.toml [--contacts]
 
-writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt``.
+writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
+the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it.
 """
 
 import math
@@ -16,6 +19,10 @@ import numpy as np
 from . import _clx
 
 MAX_IDS = 1 << 24                       # clx_region_moments / clx_region_intensity: nid <= 2^24
+MIN_CAPACITY, MAX_CAPACITY = 1 << 10, 1 << 28       # clx_region_contacts: slots of the pair table
+_INFO_BAD_LABEL, _INFO_FULL = 1, 4      # bits of clx_region_contacts' info[0]
+_SQRT2 = math.sqrt(2.0)
+PERIMETER_WEIGHTS = (0.0, 1.0, _SQRT2, (1.0 + _SQRT2) / 2.0)   # of clx_region_perimeter's classes; [0] counts border pixels
 _SHIFT_MIN, _SHIFT_MAX = -1022, 1023    # 2.0 ** shift stays a normal float64: scaling by it is exact
 
 
@@ -82,21 +89,75 @@ def shape_columns(label, area, bbox, sum1, sum2, nd):
     return cols
 
 
-def _to_device_labels(labels, device):
+def perimeter_from_classes(classes):
+    """``c1 + c2·√2 + c3·(1 + √2)/2`` per row of ``classes`` (n, 4) as float64: scikit-image's ``perimeter(mask,
+    neighbourhood=4)`` from ``clx_region_perimeter``'s integer counts (column 0, the border pixels, has no weight)."""
+    c = np.asarray(classes).reshape(-1, 4).astype(np.float64)
+    return c[:, 1] * PERIMETER_WEIGHTS[1] + c[:, 2] * PERIMETER_WEIGHTS[2] + c[:, 3] * PERIMETER_WEIGHTS[3]
+
+
+def boundary_columns(present, bbox, shape, a, b, faces, classes, nd):
+    """The boundary columns of ``region_table`` from integer counts.  present (n) ids ascending, bbox (n, 6) inclusive
+    ``zmin ymin xmin zmax ymax xmax``, shape the map's ``nd`` extents; a, b, faces: ``contact_pairs``' rows (a < b, a may
+    be 0; every non-zero id is in ``present``); classes (n, 4) ``clx_region_perimeter``'s rows of the present ids, or
+    None (3-D).  ``touches_border`` is host arithmetic on the bounding box."""
+    assert nd in (2, 3) and len(shape) == nd
+    present = np.asarray(present, dtype=np.int64)
+    n = len(present)
+    bbox = np.asarray(bbox).reshape(n, 6).astype(np.int64)
+    a, b, faces = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (a, b, faces))
+    row_a, row_b = np.searchsorted(present, a), np.searchsorted(present, b)       # a == 0 has no row
+    between = a > 0
+    boundary = np.zeros(n, dtype=np.int64)
+    contact = np.zeros(n, dtype=np.int64)
+    neighbours = np.zeros(n, dtype=np.int64)
+    np.add.at(boundary, row_b, faces)
+    np.add.at(boundary, row_a[between], faces[between])
+    for rows in (row_a[between], row_b[between]):
+        np.add.at(contact, rows, faces[between])
+        np.add.at(neighbours, rows, 1)
+    touches = np.zeros(n, dtype=bool)
+    for k, extent in zip(range(3 - nd, 3), shape):
+        touches |= (bbox[:, k] == 0) | (bbox[:, 3 + k] == int(extent) - 1)
+    cols = {"boundary_faces": boundary, "contact_faces": contact, "num_neighbours": neighbours,
+            "touches_border": touches.astype(np.int64)}
+    if nd == 2:
+        classes = np.asarray(classes).reshape(n, 4)
+        cols["border_pixels"] = classes[:, 0].astype(np.int64)
+        cols["perimeter"] = perimeter_from_classes(classes)
+    return cols
+
+
+def _resolve_device(labels, device):
+    import torch
+
+    if torch.is_tensor(labels) and labels.is_cuda:
+        device = labels.device
+    elif device is None:
+        if not torch.cuda.is_available():
+            raise _clx.ClxError("measure needs a HIP device; cellulus_amd has no CPU path")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _clx.ClxError(f"measure needs a HIP device, got {device}; cellulus_amd has no CPU path")
+    return device
+
+
+def _to_device_labels(labels, device, who="region_table"):
     import torch
 
     if torch.is_tensor(labels):
         if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.dtype.is_complex:
-            raise TypeError(f"region_table: labels must be integers, got {labels.dtype}")
+            raise TypeError(f"{who}: labels must be integers, got {labels.dtype}")
         lab = labels.to(device)
         if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= MAX_IDS):
-            raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+            raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
         return lab.to(torch.int32).contiguous()
     labels = np.ascontiguousarray(labels)
     if labels.dtype.kind not in "ui":
-        raise TypeError(f"region_table: labels must be integers, got {labels.dtype}")
+        raise TypeError(f"{who}: labels must be integers, got {labels.dtype}")
     if labels.size and (int(labels.min()) < 0 or int(labels.max()) >= MAX_IDS):
-        raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+        raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
     return torch.from_numpy(labels.astype(np.int32)).to(device)
 
 
@@ -162,36 +223,105 @@ def _channel_columns(lab, raw_d, raw_type, nid, present, area, k):
     return {f"intensity_mean_c{k}": mean, f"intensity_min_c{k}": vals[:, 0].copy(), f"intensity_max_c{k}": vals[:, 1].copy()}
 
 
-def region_table(labels, raw=None, device=None):
+def _labels_on_device(labels, device, who):
+    """-> (int32 device tensor, device, nd, spatial, nid) after the type and range checks every entry point shares;
+    `who` names the caller in their messages"""
+    device = _resolve_device(labels, device)
+    nd = labels.ndim
+    if nd not in (2, 3):
+        raise ValueError(f"{who}: labels must be 2-D or 3-D, got {nd} dimensions")
+    spatial = tuple(int(v) for v in labels.shape)
+    lab = _to_device_labels(labels, device, who)
+    _clx.require_device(lab, "labels")
+    nid = int(lab.max().item()) + 1 if lab.numel() else 1
+    return lab, device, nd, spatial, nid
+
+
+def _pair_capacity(objects):
+    """power of two, at least 8 x the object count (an object of a tissue has about six neighbours, so about four
+    pairs with the background's: the table stays below half full) and at least MIN_CAPACITY"""
+    return max(MIN_CAPACITY, 1 << max(0, 8 * int(objects) - 1).bit_length())
+
+
+def _contacts(lab, nd, spatial, nid, objects, who):
+    """clx_region_contacts, repeated with twice the table while it reports a pair it could not place
+    -> (a, b, faces) int64, sorted by (a, b).  `objects`: the object count or a bound on it, which sizes the first table"""
+    import torch
+
+    device = lab.device
+    Z, Y, X = (1,) * (3 - nd) + tuple(spatial)
+    capacity = _pair_capacity(objects)
+    while True:
+        if capacity > MAX_CAPACITY:
+            raise ValueError(f"{who}: more id pairs than a table of {MAX_CAPACITY} slots holds")
+        keys = torch.empty(capacity, dtype=torch.int64, device=device)
+        counts = torch.empty(capacity, dtype=torch.int64, device=device)
+        info = torch.empty(2, dtype=torch.int32, device=device)
+        _clx.call("clx_region_contacts", _clx.ptr(lab), nd, Z, Y, X, nid, capacity, _clx.ptr(keys), _clx.ptr(counts),
+                  _clx.ptr(info), _clx.stream_ptr(device))
+        flags, used = info.tolist()
+        if flags & _INFO_BAD_LABEL:
+            raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
+        if not flags & _INFO_FULL:
+            break
+        capacity *= 2
+    slot = torch.nonzero(keys).reshape(-1)
+    assert slot.numel() == used
+    k = keys[slot].cpu().numpy()
+    order = np.argsort(k, kind="stable")                     # keys are (a << 32) | b with a < 2^24: the (a, b) order
+    k = k[order]
+    return k >> 32, k & 0xFFFFFFFF, counts[slot].cpu().numpy()[order]
+
+
+def contact_pairs(labels, device=None):
+    """The faces between pixels of different ids of ``labels`` (2-D or 3-D integers, array or device tensor; the same
+    types and range as ``region_table``), connectivity 1, the outside of the image counting as id 0: ``(a, b, faces)``
+    int64 arrays, one row per pair with ``a < b``, sorted by ``(a, b)``.  Rows with ``a == 0`` are an object's faces to
+    the background and the image edge; the others are the region adjacency graph with the size of every contact.
+    Runs on a HIP device; there is no CPU path."""
+    lab, device, nd, spatial, nid = _labels_on_device(labels, device, "contact_pairs")
+    if nid == 1:                                             # no pixel, or background only: no object, no pair
+        return tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+    # the first table is sized without another pass over the map: neither the largest id nor the pixel count is below
+    # the object count
+    return _contacts(lab, nd, spatial, nid, min(nid - 1, lab.numel()), "contact_pairs")
+
+
+def _perimeter_classes(lab, Y, X, nid):
+    import torch
+
+    classes = torch.empty((nid, 4), dtype=torch.int64, device=lab.device)
+    bad = torch.empty(1, dtype=torch.int32, device=lab.device)
+    _clx.call("clx_region_perimeter", _clx.ptr(lab), Y, X, nid, _clx.ptr(classes), _clx.ptr(bad), _clx.stream_ptr(lab.device))
+    if int(bad.item()):
+        raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+    return classes.cpu().numpy()
+
+
+def region_table(labels, raw=None, device=None, boundary=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
     float64 or integers that fit int32), ``intensity_mean_c{k}, intensity_min_c{k}, intensity_max_c{k}``.
+    ``boundary=True`` appends ``boundary_faces`` (faces to anything that is not the object), ``contact_faces`` (to
+    other objects), ``num_neighbours`` (objects touched), ``touches_border`` (0 / 1: the bounding box reaches the image
+    edge) and in 2-D ``border_pixels`` and ``perimeter`` (scikit-image's 4-neighbourhood formula, restated).
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
+    return _region_table(labels, raw, device, boundary)[0]
+
+
+def _region_table(labels, raw, device, boundary):
+    """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     import torch
 
-    if torch.is_tensor(labels) and labels.is_cuda:
-        device = labels.device
-    elif device is None:
-        if not torch.cuda.is_available():
-            raise _clx.ClxError("measure needs a HIP device; cellulus_amd has no CPU path")
-        device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _clx.ClxError(f"measure needs a HIP device, got {device}; cellulus_amd has no CPU path")
-    nd = labels.ndim
-    if nd not in (2, 3):
-        raise ValueError(f"region_table: labels must be 2-D or 3-D, got {nd} dimensions")
-    spatial = tuple(labels.shape)
-    lab = _to_device_labels(labels, device)
-    _clx.require_device(lab, "labels")
+    lab, device, nd, spatial, nid = _labels_on_device(labels, device, "region_table")
     Z, Y, X = (1,) * (3 - nd) + spatial
-    nid = int(lab.max().item()) + 1 if lab.numel() else 1
     if lab.numel() == 0 or nid == 1:
         area = np.zeros(1, dtype=np.int64)
         cols = shape_columns(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, 6), np.int32),
                              np.zeros((0, 3), np.uint64), np.zeros((0, 6), np.uint64), nd)
         present = np.zeros(0, dtype=np.int64)
+        bbox = np.zeros((0, 6), dtype=np.int32)
     else:
         area_d = torch.empty(nid, dtype=torch.int64, device=device)
         bbox_d = torch.empty((nid, 6), dtype=torch.int32, device=device)
@@ -205,7 +335,8 @@ def region_table(labels, raw=None, device=None):
         area = area_d.cpu().numpy()
         area[0] = 0
         present = np.flatnonzero(area > 0)
-        cols = shape_columns(present, area[present], bbox_d.cpu().numpy()[present],
+        bbox = bbox_d.cpu().numpy()[present]
+        cols = shape_columns(present, area[present], bbox,
                              sum1_d.cpu().numpy().view(np.uint64)[present],
                              sum2_d.cpu().numpy().view(np.uint64)[present], nd)
     if raw is not None:
@@ -221,17 +352,29 @@ def region_table(labels, raw=None, device=None):
                 dt = raw_d.cpu().numpy().dtype
                 cols.update({f"intensity_mean_c{k}": np.zeros(0), f"intensity_min_c{k}": np.zeros(0, dt),
                              f"intensity_max_c{k}": np.zeros(0, dt)})
-    return cols
+    if not boundary:
+        return cols, None
+    if len(present):
+        pairs = _contacts(lab, nd, spatial, nid, len(present), "region_table")
+    else:
+        pairs = tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+    classes = None
+    if nd == 2:
+        classes = _perimeter_classes(lab, Y, X, nid)[present] if len(present) else np.zeros((0, 4), dtype=np.int64)
+    cols.update(boundary_columns(present, bbox, spatial, *pairs, classes, nd))
+    return cols, pairs
 
 
 def _format(value):
     return "%.17g" % value if isinstance(value, (float, np.floating)) else "%d" % value
 
 
-def measure(inference_config) -> None:
+def measure(inference_config, contacts=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
-    then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  Rank 0 works alone under torch.distributed."""
+    then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
+    and writes ``contacts_bandwidth-<b>.csv`` beside it: ``sample,label_a,label_b,faces``, one line per pair of
+    objects that touch.  Rank 0 works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -250,10 +393,12 @@ def measure(inference_config) -> None:
     ds_seg = zarr_io.open(seg_config.container_path, "r")[seg_config.dataset_name]
     ds_raw = zarr_io.open(dataset_config.container_path, "r")[dataset_config.dataset_name]
     for bandwidth in range(inference_config.num_bandwidths):
-        header, lines = None, []
+        header, lines, pair_lines = None, [], []
         for sample in range(meta.num_samples):
             labels = ds_seg[sample, bandwidth].astype(np.int32)
-            table = region_table(labels, ds_raw[sample], device)
+            table, pairs = _region_table(labels, ds_raw[sample], device, contacts)
+            if contacts:
+                pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)
             columns = list(table.values())
             for i in range(len(table["label"])):
@@ -262,6 +407,11 @@ def measure(inference_config) -> None:
             out.write(",".join(header or ["sample"]) + "\n")
             for line in lines:
                 out.write(line + "\n")
+        if contacts:
+            with open(f"contacts_bandwidth-{bandwidth}.csv", "w") as out:
+                out.write("sample,label_a,label_b,faces\n")
+                for line in pair_lines:
+                    out.write(line + "\n")
 
 
 if __name__ == "__main__":

@@ -925,6 +925,43 @@ int clx_region_moments(const int32_t* labels, int Z, int Y, int X, int nid,
 int clx_region_intensity(const int32_t* labels, const void* raw, int raw_type, long long npix,
                          int nid, int shift, long long* isum, unsigned long long* vkey,
                          int32_t* bad, clx_stream stream);
+/* Contacts: the faces between pixels of different ids, per id pair — the region adjacency / cell-contact graph, the
+ * boundary size of every object and its contact with the image edge, which no moment gives.  Label map [Z][Y][X].
+ *   face      between two pixels that are neighbours along one counted axis (connectivity 1): y and x for nd == 2
+ *             (Z must be 1), z, y and x for nd == 3 (Z == 1 allowed: its two z faces per pixel then go to id 0)
+ *   outside   the outside of the image is id 0 on both ends of every counted axis: a pixel in the first or last row,
+ *             column (or slice) has a face to id 0
+ *   pair      every face whose two ids differ counts once for (lo, hi), lo < hi; lo may be 0 (background or outside)
+ *   labels    a label outside [0, nid) is treated as 0, is never followed as an index and sets bit 0 of info[0]
+ * Output: an open-addressing table of `capacity` slots (a power of two in [1024, 2^28]).
+ *   keys   [capacity]  (lo << 32) | hi; 0: empty slot (hi >= 1, so no key is 0)
+ *   counts [capacity]  faces of that pair
+ *   info   [2]         [0] bit 0: a label outside [0, nid); bit 2: a pair could not be placed — the table is to be
+ *                      discarded and the call repeated with a larger capacity.  [1] occupied slots (<= capacity)
+ * The entry point initialises keys, counts and info itself.  Which slot a pair gets depends on which block claims first,
+ * so the slot order is unspecified; the SET of (key, count) is determined by the map: integer adds only.  Either the
+ * set is exact or bit 2 is set, nothing in between.  An insertion probes at most min(capacity, 4096) consecutive slots
+ * (modulo capacity) and then gives up with bit 2: it never spins, always terminates and writes only keys[0, capacity)
+ * and counts[0, capacity).  With a table a few times larger than the number of pairs bit 2 means "more pairs than
+ * slots" in practice, but a caller must not rely on that: repeat while it is set.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent,
+ * Z*Y*X >= 2^32, nid outside [1, 2^24], capacity not a power of two in [1024, 2^28]. */
+int clx_region_contacts(const int32_t* labels, int nd, int Z, int Y, int X, int nid, int capacity,
+                        unsigned long long* keys, unsigned long long* counts, int32_t* info,
+                        clx_stream stream);
+/* Perimeter, 2-D label map [Y][X]: scikit-image's perimeter(mask, neighbourhood=4) of every object's mask, restated on
+ * the full map (the formula is restated here, not compared with scikit-image by a fixture).  The outside of the image,
+ * the background and other objects all count as "not the object".
+ *   border pixel of i   a pixel of i with a 4-neighbour that is not i
+ *   code                1 + 2 n4 + 10 nd; n4 / nd: the border pixels of i among its 4 edge / 4 diagonal neighbours
+ *   classes [nid][4]    [0] border pixels; [1] codes 5 7 15 17 25 27 (weight 1); [2] codes 21 33 (weight sqrt 2);
+ *                       [3] codes 13 23 (weight (1 + sqrt 2) / 2).  perimeter = c1 + c2 sqrt 2 + c3 (1 + sqrt 2) / 2, formed
+ *                       by the caller; a one-pixel object has code 1 and perimeter 0
+ *   bad [1]             1: a label outside [0, nid) — never followed as an index, treated as background
+ * Outputs are initialised by the entry point; row 0 is unspecified.  Integer adds only: the same bits in every run.
+ * Refused before any launch: null pointers, a non-positive extent, nid outside [1, 2^24], Y*X >= 2^32. */
+int clx_region_perimeter(const int32_t* labels, int Y, int X, int nid, unsigned long long* classes,
+                         int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
