@@ -1,31 +1,28 @@
-"""Launch plan of the U-Net + head on libclx (forward, backward, inference).
-
-The topology is the one ``cellulus/models/unet.py:24-63`` requests from
-``funlib.learn.torch.models.UNet`` (valid convolutions ``[3,1,1,3]`` + ReLU per
-level, max-pool down, nearest ``constant_upsample`` up, centre-cropped skip
-concatenated *before* the upsampled tensor) followed by the 1x1 head.  funlib
-is not vendored in the reference; the restated rules (``crop_to_factor``,
-channel counts, module names) are documented in SURVEY.md §3.4.
+"""Launch plan of the U-Net + head on libclx (forward, backward, inference): UNetPlan executes a Topology
+(topology.py) for a fixed batch size on one HIP device.
 
 Everything device-side is channels-last f32 with channel counts padded to a
 multiple of 4; the padded channels stay zero for the life of a buffer.
+
+A plan is built in two phases: _decide chooses every layer's algorithm and every size from the topology, the switches
+and the library's geometry-only queries, then _alloc takes the device memory those decisions ask for.  The backward
+half does the same on the first training step (_decide_backward, _alloc_backward).
 """
 
 import ctypes
-import math
 import os
-from dataclasses import dataclass, field
-from typing import List, Tuple
 
 import torch
 
 from .. import _clx
-from .._clx import ClxConvDesc, ClxSrc
-
-
-def pad4(c: int) -> int:
-    return (c + 3) // 4 * 4
-
+# (every name this module defined before topology.py, descriptors.py, subpixel.py and dual.py were split from it can
+#  still be imported from here)
+from .descriptors import (DEFAULT_PRECISION, FUSED_MAX_CHANNELS, PRECISION_CODES, QUERY_PTR, WINO_PACK_DGRAD,  # noqa: F401
+                          WINO_PACK_FWD, WINO_TILE, conv_desc, conv_src, fused_pays, fused_wanted, pack_job_elements,
+                          packed_taps, precision_code, precision_name, wino_taps, winograd_code, winograd_enabled)
+from .subpixel import Subpixel, SubpixelHalf, fold_phase_grads, phase_weights, subpixel_geometry  # noqa: F401
+from .topology import (ConvLayer, PoolOp, Source, Topology, build_topology, find_chain_pairs, forward_flops, pad4,  # noqa: F401
+                       tensor_consumers)
 
 # Winograd is used for 3x3 layers whose channel counts (both sides) reach this value: below it the
 # extra HBM traffic of the transformed tensors and the short contraction (K = C per batched GEMM)
@@ -33,401 +30,22 @@ def pad4(c: int) -> int:
 # CLX_WINOGRAD=0 forces the direct implicit-GEMM kernels everywhere; CLX_WINOGRAD_TILE selects
 # F(2x2, 3x3) (2.25x fewer multiplications, error ~7e-7 of the output range on a 768-channel
 # layer) or F(4x4, 3x3) (4x fewer, ~5e-6; the direct kernel: ~4e-7).
+# (these two stay in this module, where the plan reads them: tests lower them here)
 WINO_MIN_CHANNELS = int(os.environ.get("CLX_WINOGRAD_MIN_CHANNELS", "64"))
-# per-layer algorithm code = clx_conv_algo: 0 direct, 1 Winograd F(2x2), 2 Winograd F(4x4)
-# (3 = F(4x4) with the transforms inside the product kernel, forward only: clx_conv_algo CLX_ALGO_WINOGRAD4_FUSED)
-WINO_PACK_FWD = {1: 2, 2: 4, 3: 7}  # clx_pack_mode
-WINO_PACK_DGRAD = {1: 3, 2: 5}
-WINO_TILE = {1: 2, 2: 4, 3: 4}
-
-
 # 3-D layers (F(4x4) in (y, x) per z plane, the z taps inside the batched GEMMs): K = 3 * C per GEMM, so
 # it pays from fewer channels than in 2-D
 WINO_MIN_CHANNELS_3D = int(os.environ.get("CLX_WINOGRAD_MIN_CHANNELS_3D", "64"))
-
-
-def winograd_code() -> int:
-    return 2 if os.environ.get("CLX_WINOGRAD_TILE", "4") == "4" else 1
-
-
-def wino_taps(code, kernel):
-    """packed-weight / weight-gradient planes of a Winograd layer: a^2 transform points x z taps, a = tile + k - 1
-    (F(2x2, 3x3): 16, F(4x4, 3x3): 36, the F(4x4, 2x2) of a sub-pixel layer's low-resolution half: 25)."""
-    return (WINO_TILE[code] + kernel[1] - 1) ** 2 * kernel[0]
-
-
-def packed_taps(code, kernel):
-    """planes of the packed weights (or of the packed weight gradient) of a layer that runs with algorithm `code`"""
-    return wino_taps(code, kernel) if code else kernel[0] * kernel[1] * kernel[2]
-
-
-def pack_job_elements(cout, cin, taps, cin_pad, cout_pad, mode):
-    """elements one packing writes (the arguments of clx_pack_weights behind the two pointers): clx_pack_weights_batch
-    sizes its grid by the biggest job of the table"""
-    if mode in (0, 1):
-        return (cout if mode == 0 else cin_pad) * taps * (cin_pad if mode == 0 else cout_pad)
-    if mode == 7:
-        return cout_pad * cin_pad
-    rows, cols = (cin_pad, cout_pad) if mode in (3, 5, 6) else (cout_pad, cin_pad)
-    return rows * (3 if taps == 27 else 2 if taps == 8 else 1) * cols
 
 
 def wino_min_channels(kernel):
     return WINO_MIN_CHANNELS_3D if kernel[0] > 1 else WINO_MIN_CHANNELS
 
 
-# The arithmetic of the plain products (1x1 layers, the transform-domain products of the 2-D Winograd layers; forward, data
-# gradient and weight gradient), clx_conv_precision:
-#   "f32x3bf16" (default since round 6): every float32 operand split EXACTLY into three bfloat16 pieces, six exact products
-#       per float32 product accumulated in float32 on the bf16 matrix cores (csrc/gemm_sp.hip; DESIGN.md 3.1h).  Results
-#       are float32; distance from the float64 oracle at a trained network's output scale 7.2e-5 (float32 MFMA: 7.3e-5).
-#   "f32": float32 MFMA everywhere (v_mfma_f32_32x32x2_f32), the only arithmetic of rounds 1-5; CLX_PRECISION=f32.
-#   "f32x3bf16g64" (opt-in, CLX_PRECISION=f32x3bf16g64): the arithmetic of "f32x3bf16" for channel counts that are multiples
-#       of 64 instead of 128, from 128 channels on (the 192 / 576-channel layers of the 64-feature-map networks).  Which layers that reaches is the library's answer
-#       (clx_conv_sp_covers; include/clx.h), as for the default: this module holds no copy of either rule.
-DEFAULT_PRECISION = "f32x3bf16"
-PRECISION_CODES = {"f32": 0, "f32x3bf16": 1, "f32x3bf16g64": 2}
-
-
-def precision_name() -> str:
-    name = os.environ.get("CLX_PRECISION", "") or DEFAULT_PRECISION
-    if name not in PRECISION_CODES:
-        raise ValueError(f"CLX_PRECISION must be 'f32', 'f32x3bf16' or 'f32x3bf16g64', got {name!r}")
-    return name
-
-
-def precision_code() -> int:
-    """clx_conv_precision: 0 = float32 MFMA, 1 = the three-way bfloat16 split (CLX_PREC_F32X3BF16), 2 = the same split
-    with the 64-channel granule (CLX_PREC_F32X3BF16_G64).  The run-to-run reproducible mode (CLX_DETERMINISTIC=1) exists
-    in float32 only and selects it."""
-    if os.environ.get("CLX_DETERMINISTIC", "0") == "1":
-        return 0
-    return PRECISION_CODES[precision_name()]
-
-
-def winograd_enabled() -> bool:
-    return os.environ.get("CLX_WINOGRAD", "1") != "0"
-
-
-# The fused forms keep the products' results on chip: 36 x 32 x 64 accumulators per workgroup, i.e. 10.7 FLOP per
-# byte of operands from L2 where the 128 x 128 tiles of the batched GEMMs have 32 — they top out near 110 TFLOP/s.  That
-# beats the three-launch form where ITS GEMMs are short (K = C <= 256: 78-90 TFLOP/s with the transforms) or narrow
-# (N = 64: HBM-bound on V and M), and loses at C = 768 (113 TFLOP/s with the transforms; tools/exp/fused_bench.py,
-# DESIGN.md 3.1g).
-FUSED_MAX_CHANNELS = int(os.environ.get("CLX_WINO_FUSED_MAX_CHANNELS", "256"))
-
-
-def fused_pays(cin_pad: int, cout: int) -> bool:
-    return cout <= 64 or cin_pad <= FUSED_MAX_CHANNELS
-
-
-def fused_wanted(keep_activations: bool) -> bool:
-    """2-D F(4x4) forward layers as ONE launch each (csrc/wino_fused.hip: the transformed tensors never reach HBM).
-    CLX_WINO_FUSED=0 keeps the three-launch form everywhere; the training plans (which keep the transformed input for
-    the weight gradient) take it with CLX_WINO_FUSED_TRAIN=1 only."""
-    if os.environ.get("CLX_WINO_FUSED", "1") == "0":
-        return False
-    return (not keep_activations) or os.environ.get("CLX_WINO_FUSED_TRAIN", "0") == "1"
-
-
-@dataclass
-class Source:
-    """One input of a convolution: a stored tensor seen through crop/upsample."""
-
-    tensor: str                      # buffer name
-    channels: int                    # real channels
-    crop: Tuple[int, int, int] = (0, 0, 0)
-    factor: Tuple[int, int, int] = (1, 1, 1)
-
-
-@dataclass
-class ConvLayer:
-    name: str                        # state_dict prefix, e.g. backbone.l_conv.0.conv_pass.0
-    sources: List[Source]
-    cout: int
-    kernel: Tuple[int, int, int]     # (kd, kh, kw), kd = 1 for 2-D
-    in_shape: Tuple[int, int, int]   # logical input extent (D, H, W)
-    out: str                         # output buffer name
-    relu: bool = True
-    param_index: int = -1            # index into the flat (weight, bias) list
-
-    @property
-    def cin(self):
-        return sum(s.channels for s in self.sources)
-
-    @property
-    def cin_pad(self):
-        return sum(pad4(s.channels) for s in self.sources)
-
-    @property
-    def taps(self):
-        return self.kernel[0] * self.kernel[1] * self.kernel[2]
-
-    @property
-    def out_shape(self):
-        return tuple(i - k + 1 for i, k in zip(self.in_shape, self.kernel))
-
-
-@dataclass
-class PoolOp:
-    src: str
-    out: str
-    channels: int
-    in_shape: Tuple[int, int, int]
-    factor: Tuple[int, int, int]
-
-
-@dataclass
-class Topology:
-    """Static description of the network for one input crop shape."""
-
-    nd: int
-    in_channels: int
-    out_channels: int
-    in_shape: Tuple[int, int, int]
-    convs: List[ConvLayer] = field(default_factory=list)
-    pools: List[PoolOp] = field(default_factory=list)
-    fwd_order: list = field(default_factory=list)      # ConvLayer | PoolOp in execution order
-    shapes: dict = field(default_factory=dict)         # buffer -> ((D,H,W), channels)
-    levels: int = 0
-    # per r-level: (conv0 layer, skip tensor, up tensor)
-    r_info: list = field(default_factory=list)
-    out_shape: Tuple[int, int, int] = (1, 1, 1)
-
-
-def build_topology(in_channels, out_channels, num_fmaps, fmap_inc_factor, features_in_last_layer,
-                   downsampling_factors, num_spatial_dims, spatial):
-    """Derives every layer's geometry for an input of spatial extent `spatial`."""
-    nd = num_spatial_dims
-    assert nd in (2, 3), "num_spatial_dims must be 2 or 3"
-    assert len(spatial) == nd
-    L = len(downsampling_factors)
-    factors = []
-    for f in downsampling_factors:
-        f = tuple(int(a) for a in f)
-        assert len(f) == nd, "downsampling factor rank must equal num_spatial_dims"
-        factors.append((1,) + f if nd == 2 else f)
-    shape = ((1,) + tuple(int(s) for s in spatial)) if nd == 2 else tuple(int(s) for s in spatial)
-    k3 = (1, 3, 3) if nd == 2 else (3, 3, 3)
-    k1 = (1, 1, 1)
-    pass_kernels = [k3, k1, k1, k3]
-    conv_crop = tuple(sum(k[d] - 1 for k in pass_kernels) for d in range(3))
-
-    topo = Topology(nd=nd, in_channels=in_channels, out_channels=out_channels, in_shape=shape, levels=L)
-    topo.shapes["raw"] = (shape, in_channels)
-
-    def add_pass(prefix, first_sources, first_in_shape, cout, out_prefix):
-        srcs, ishape = first_sources, first_in_shape
-        layers = []
-        for j, k in enumerate(pass_kernels):
-            name = f"{prefix}.conv_pass.{2 * j}"
-            out = f"{out_prefix}.{j}"
-            layer = ConvLayer(name=name, sources=srcs, cout=cout, kernel=k, in_shape=ishape, out=out)
-            for d in range(3):
-                if layer.out_shape[d] <= 0:
-                    raise ValueError(
-                        f"input extent {spatial} is too small for the U-Net (layer {name} would be empty)")
-            topo.convs.append(layer)
-            topo.fwd_order.append(layer)
-            topo.shapes[out] = (layer.out_shape, cout)
-            layers.append(layer)
-            srcs, ishape = [Source(out, cout)], layer.out_shape
-        return layers
-
-    # ---- left (contracting) path
-    left_out = []
-    cur, cur_c, cur_shape = "raw", in_channels, shape
-    for i in range(L + 1):
-        cout = num_fmaps * fmap_inc_factor ** i
-        layers = add_pass(f"backbone.l_conv.{i}", [Source(cur, cur_c)], cur_shape, cout, f"l{i}")
-        y, yshape = layers[-1].out, layers[-1].out_shape
-        left_out.append((y, cout, yshape))
-        if i < L:
-            f = factors[i]
-            for d in range(3):
-                if yshape[d] % f[d] != 0:
-                    raise RuntimeError(
-                        f"Can not downsample shape {yshape[3 - nd:]} with factor {f[3 - nd:]}, "
-                        f"mismatch in spatial dimension {d - (3 - nd)}")
-            pshape = tuple(s // ff for s, ff in zip(yshape, f))
-            pool = PoolOp(src=y, out=f"p{i}", channels=cout, in_shape=yshape, factor=f)
-            topo.pools.append(pool)
-            topo.fwd_order.append(pool)
-            topo.shapes[pool.out] = (pshape, cout)
-            cur, cur_c, cur_shape = pool.out, cout, pshape
-
-    # ---- right (expanding) path, bottom-up
-    crop_factors = []
-    prod = None
-    for f in factors[::-1]:
-        prod = tuple(f) if prod is None else tuple(a * b for a, b in zip(f, prod))
-        crop_factors.append(prod)
-    crop_factors = crop_factors[::-1]
-
-    below, below_c, below_shape = left_out[L]
-    topo.r_info = [None] * L
-    for i in range(L - 1, -1, -1):
-        f = factors[i]
-        up_shape = tuple(s * ff for s, ff in zip(below_shape, f))
-        # crop_to_factor: keep (size - conv_crop) a multiple of the cumulative factor
-        cf = crop_factors[i]
-        target = tuple(int(math.floor((s - c) / ff)) * ff + c for s, c, ff in zip(up_shape, conv_crop, cf))
-        for d in range(3):
-            if target[d] <= conv_crop[d] and up_shape[d] != target[d]:
-                raise RuntimeError(f"Feature map with shape {up_shape} is too small for cropping to factor")
-        up_crop = tuple((s - t) // 2 for s, t in zip(up_shape, target))
-        skip, skip_c, skip_shape = left_out[i]
-        for d in range(3):
-            if skip_shape[d] < target[d]:
-                raise RuntimeError("skip connection smaller than the upsampled feature map")
-        skip_crop = tuple((s - t) // 2 for s, t in zip(skip_shape, target))
-        cout = features_in_last_layer if i == 0 else num_fmaps * fmap_inc_factor ** i
-        srcs = [Source(skip, skip_c, crop=skip_crop),
-                Source(below, below_c, crop=up_crop, factor=f)]
-        layers = add_pass(f"backbone.r_conv.0.{i}", srcs, target, cout, f"r{i}")
-        topo.r_info[i] = dict(conv0=layers[0], skip=skip, up=below, level=i)
-        below, below_c, below_shape = layers[-1].out, cout, layers[-1].out_shape
-
-    # ---- head: 1x1 conv + ReLU + 1x1 conv (unet.py:52-63)
-    top, top_c, top_shape = below, below_c, below_shape
-    if L > 0 and top_c != features_in_last_layer:
-        raise AssertionError("internal: top level width mismatch")
-    h0 = ConvLayer(name="head.0", sources=[Source(top, top_c)], cout=features_in_last_layer,
-                   kernel=k1, in_shape=top_shape, out="h0", relu=True)
-    h1 = ConvLayer(name="head.2", sources=[Source("h0", features_in_last_layer)], cout=out_channels,
-                   kernel=k1, in_shape=top_shape, out="h1", relu=False)
-    if L == 0 and top_c != features_in_last_layer:
-        # funlib keeps num_fmaps at level 0 when there is no upsampling path; the
-        # reference head then expects features_in_last_layer inputs (a config error).
-        raise ValueError("with no downsampling, num_fmaps must equal features_in_last_layer")
-    for layer in (h0, h1):
-        topo.convs.append(layer)
-        topo.fwd_order.append(layer)
-        topo.shapes[layer.out] = (layer.out_shape, layer.cout)
-    topo.out_shape = top_shape
-    for idx, layer in enumerate(topo.convs):
-        layer.param_index = idx
-    return topo
-
-
-def tensor_consumers(topo):
-    """How many operations READ each stored tensor: every source of every convolution (skip connections and
-    upsampled tensors are sources of a level's first convolution) and every pooling."""
-    n = {}
-    for layer in topo.convs:
-        for src in layer.sources:
-            n[src.tensor] = n.get(src.tensor, 0) + 1
-    for pool in topo.pools:
-        n[pool.src] = n.get(pool.src, 0) + 1
-    return n
-
-
-def find_chain_pairs(topo, algo_fwd, batch):
-    """The (a, b) pairs of consecutive 64-channel 1x1 layers that may run as one launch each way.
-
-    The fused backward pass OVERWRITES the gradient of the pair's input and never writes the gradient of the
-    middle tensor (and neither tensor gets ReLU gate bits), so a pair qualifies only if the middle tensor is read
-    by `b` alone and the pair's input by `a` alone: a tensor that is also a skip connection, pooled, or read by a
-    second convolution keeps the layer-by-layer path, where gradients add up."""
-    produced_by_conv = {layer.out: layer for layer in topo.convs}
-    readers = tensor_consumers(topo)
-    one = (1, 1, 1)
-    plain = lambda s: tuple(s.crop) == (0, 0, 0) and tuple(s.factor) == (1, 1, 1)       # noqa: E731
-    pairs = []
-    i = 0
-    while i + 1 < len(topo.convs):
-        a, b = topo.convs[i], topo.convs[i + 1]
-        ok = (tuple(a.kernel) == one and tuple(b.kernel) == one and len(a.sources) == 1 and len(b.sources) == 1
-              and plain(a.sources[0]) and plain(b.sources[0]) and b.sources[0].tensor == a.out
-              and a.sources[0].tensor in produced_by_conv and a.sources[0].channels == 64 and a.cout == 64
-              and a.relu and (b.cout == 64 or b.cout <= 8)
-              and readers.get(a.out, 0) == 1 and readers.get(a.sources[0].tensor, 0) == 1
-              and not algo_fwd[a.name] and not algo_fwd[b.name]
-              and batch * a.in_shape[0] * a.in_shape[1] * a.in_shape[2] < (1 << 31) - 256)
-        if ok:
-            pairs.append((a, b))
-            i += 2
-        else:
-            i += 1
-    return pairs
-
-
-def conv_src(ptr, C, ld, shape, crop=(0, 0, 0), factor=(1, 1, 1)):
-    """clx_src: a stored tensor (C of its ld channels, extent `shape`) seen through crop and nearest upsampling"""
-    s = ClxSrc()
-    s.ptr, s.C, s.ld = ptr, C, ld
-    s.D, s.H, s.W = shape
-    s.oz, s.oy, s.ox = crop
-    s.fz, s.fy, s.fx = factor
-    return s
-
-
-def conv_desc(sources, B, in_shape, kernel, pad, N, precision, c_real=0):
-    """clx_conv_desc of a convolution over `sources`.  What is not named here is what a fresh structure holds, zero and
-    NULL: no bias, ReLU, mask or accumulation, the direct algorithm, no workspace — the caller sets what it uses."""
-    d = ClxConvDesc()
-    d.nsrc = len(sources)
-    for i, s in enumerate(sources):
-        d.src[i] = s
-    d.B = B
-    d.ID, d.IH, d.IW = in_shape
-    d.KD, d.KH, d.KW = kernel
-    d.PD, d.PH, d.PW = pad
-    d.N = N
-    d.precision = precision
-    d.c_real = c_real
-    return d
-
-
-@dataclass(eq=False)
-class SubpixelHalf:
-    """One of the two convolutions a sub-pixel layer runs as — 3x3 over the skip tensor, 2x2 over the low-resolution
-    tensor — as allocation, packing, the weight gradient and the sharing between plans see it: weights (rows, C, taps),
-    packed as (rows_pad, packed_taps, Cp)."""
-
-    rows: int                        # output channels of the weights ...
-    rows_pad: int                    # ... and of their packed form
-    C: int                           # input channels, and padded
-    Cp: int
-    kernel: Tuple[int, int, int]
-    wino: int = 0                    # algorithm code of the forward pass and the weight gradient ...
-    wino_dgrad: int = 0              # ... and of the data gradient
-    fused: bool = False              # forward pass in the one-launch form (wino_fused.hip)
-    w: torch.Tensor = None           # weights (written by clx_subpixel_split_weights)
-    wp_fwd: torch.Tensor = None      # packed for the forward pass / for the data gradient
-    wp_dgrad: torch.Tensor = None
-    dw: torch.Tensor = None          # packed weight gradient: a slice of the plan's dwpack
-    g: torch.Tensor = None           # weight gradient, unpacked (read by clx_subpixel_fold_grads)
-    vcache: torch.Tensor = None      # transformed input, kept by the forward pass for the weight gradient ...
-    v_fresh: bool = False            # ... and written by the last forward pass
-
-    @property
-    def taps(self):
-        return self.kernel[0] * self.kernel[1] * self.kernel[2]
-
-
-@dataclass(eq=False)
-class Subpixel:
-    """Geometry of the sub-pixel form of a convolution over cat(skip, nearest-upsample(low)) (_subpixel_geometry)."""
-
-    fac: Tuple[int, int, int]        # upsampling factor, P = its product: the phases
-    P: int
-    N: int                           # padded output channels of the layer; the low half computes P * N
-    zshape: Tuple[int, int, int]     # extent of the low half's output Z, stored in buf[zname]
-    zname: str
-    level: int
-    skip: SubpixelHalf
-    low: SubpixelHalf
-
-    @property
-    def halves(self):
-        return self.skip, self.low
-
-
 class UNetPlan:
     """Executes a Topology for a fixed batch size on one HIP device."""
 
-    def __init__(self, topo: Topology, batch: int, device: torch.device, keep_activations: bool):
+    def __init__(self, topo: Topology, batch: int, device: torch.device, keep_activations: bool, allocate=True):
+        """allocate=False: the decisions only — the plan owns no device memory and cannot run"""
         self.topo = topo
         self.B = int(batch)
         self.device = device
@@ -450,7 +68,17 @@ class UNetPlan:
         self._pointwise_reader = {}
         self.dx_bufs = {}           # the generic route of the input-image gradient (first_dgrad): scratch, made on first use
         self.buf = {}
-        self._alloc()
+        self.workspace = None
+        self.vcache = {}
+        self._vcache_fresh = set()
+        self._packed_version = None
+        self._bwd_ready = False
+        # tensor -> the convolution / the pooling that produces it (backward_steps routes gradients by them)
+        self._conv_by_out = {layer.out: layer for layer in topo.convs}
+        self._pool_by_out = {p.out: p for p in topo.pools}
+        self._decide()
+        if allocate:
+            self._alloc()
 
     def _fused_ok(self, cin_pad, cout):
         """the one-launch (float32) Winograd form for a 2-D layer cin_pad -> cout?  Where it pays (fused_pays) — in the
@@ -461,131 +89,95 @@ class UNetPlan:
         for <=, so the default precision runs every Winograd layer in three launches (-4 % on an inference tile)."""
         return bool(self.fused and not self.precision and fused_pays(cin_pad, cout))
 
-    # ------------------------------------------------------------------ memory
-    def _alloc(self):
+    # --------------------------------------------------------------- decisions
+    def _addr(self, name, query):
+        """the address of buffer `name` in a descriptor — of a geometry-only query, asked before the buffers exist: QUERY_PTR"""
+        return QUERY_PTR if query else self.buf[name].data_ptr()
+
+    def _takes(self, code, *passes):
+        """Can every pass of `passes` — (descriptor, which: 0 clx_conv_fwd, 1 clx_conv_wgrad) — run with algorithm `code`?
+        The library's answer is the workspace each needs (0: not applicable); taken, the plan's workspace covers them."""
+        lib = _clx.load()
+        need = []
+        for d, which in passes:
+            d.algo = code
+            need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(d), which)))
+        if not all(need):
+            return False
+        self.ws_bytes = max([self.ws_bytes] + need)
+        return True
+
+    def _fused_takes(self, d, cin_pad, cout):
+        """the one-launch form for the F(4x4) forward call `d`?  (_fused_ok, and the library's word on the geometry)"""
+        return bool(self._fused_ok(cin_pad, cout) and int(_clx.load().clx_conv_fused_applicable(ctypes.byref(d))))
+
+    def _decide(self):
+        """Phase one of construction: per layer the algorithm (direct implicit GEMM / Winograd) of forward, data gradient
+        and weight gradient, the sub-pixel records, the split-precision passes, the fused pairs and poolings, and the size
+        of the workspace — from the topology, the switches and the library's geometry-only queries.  Allocates nothing."""
         t = self.topo
-        for name, (shape, c) in t.shapes.items():
-            n = self.B * shape[0] * shape[1] * shape[2]
-            self.buf[name] = _clx.zeros((n, pad4(c)), torch.float32, self.device)
-        # per-layer algorithm (direct implicit GEMM / Winograd) for forward, dgrad and wgrad
+        lib = _clx.load()
+        code = winograd_code() if winograd_enabled() else 0
         self.algo = {}
-        self.workspace = None
-        ws_bytes = 0
+        self.ws_bytes = 0
         for layer in t.convs:
             a = dict(fwd=0, dgrad=0, wgrad=0)
-            if (winograd_enabled() and min(layer.cin_pad, layer.cout) >= wino_min_channels(layer.kernel)
-                    and (layer.kernel[0] == 1 or winograd_code() == 2)):
-                lib = _clx.load()
-                code = winograd_code()
-                d = self._desc(layer, layer.cout)
-                d.algo = code
-                nf = int(lib.clx_conv_workspace_bytes(ctypes.byref(d), 0))
-                if nf:
-                    a["fwd"], ws_bytes = code, max(ws_bytes, nf)
-                    if (code == 2 and self._fused_ok(layer.cin_pad, layer.cout) and layer.cout == pad4(layer.cout)
-                            and int(lib.clx_conv_fused_applicable(ctypes.byref(d)))):
+            if (code and min(layer.cin_pad, layer.cout) >= wino_min_channels(layer.kernel)
+                    and (layer.kernel[0] == 1 or code == 2)):
+                d = self._desc(layer, layer.cout, query=True)
+                if self._takes(code, (d, 0)):
+                    a["fwd"] = code
+                    if code == 2 and layer.cout == pad4(layer.cout) and self._fused_takes(d, layer.cin_pad, layer.cout):
                         a["fwd"] = 3
-                        ws_bytes = max(ws_bytes, int(lib.clx_conv_fused_workspace_bytes(ctypes.byref(d))))
+                        self.ws_bytes = max(self.ws_bytes, int(lib.clx_conv_fused_workspace_bytes(ctypes.byref(d))))
                 d.N = pad4(layer.cout)
-                nw = int(lib.clx_conv_workspace_bytes(ctypes.byref(d), 1))
-                if nw and self.keep:
-                    a["wgrad"], ws_bytes = code, max(ws_bytes, nw)
-                if self.keep and layer.param_index > 0:
-                    dd = self._dgrad_desc(layer, None)
-                    dd.algo = code
-                    nd_ = int(lib.clx_conv_workspace_bytes(ctypes.byref(dd), 0))
-                    if nd_:
-                        a["dgrad"], ws_bytes = code, max(ws_bytes, nd_)
+                if self.keep and self._takes(code, (d, 1)):
+                    a["wgrad"] = code
+                if self.keep and layer.param_index > 0 and self._takes(code, (self._dgrad_desc(layer, None), 0)):
+                    a["dgrad"] = code
             self.algo[layer.name] = a
         # sub-pixel form of the convolutions that read a nearest-upsampled tensor (DESIGN.md §3.1c)
         self.subpixel = {}
         for info in t.r_info:
             conv0 = info["conv0"]
-            sp = self._subpixel_geometry(conv0)
+            sp = subpixel_geometry(t, conv0)
             if sp is None:
                 continue
             self.subpixel[conv0.name] = sp
             skip, low = sp.halves
-            n = self.B * sp.zshape[0] * sp.zshape[1] * sp.zshape[2]
-            self.buf[sp.zname] = _clx.zeros((n, low.rows), torch.float32, self.device)
             # the 2x2 convolution over the low-res tensor as Winograd F(4x4, 2x2)
-            if (winograd_enabled() and winograd_code() == 2 and low.kernel in ((1, 2, 2), (2, 2, 2))
+            if (code == 2 and low.kernel in ((1, 2, 2), (2, 2, 2))
                     and min(low.Cp, low.rows) >= wino_min_channels(low.kernel)):
-                lib = _clx.load()
-                dz, _ds = self._sp_descs(conv0, sp)
-                dz.algo = 2
-                need = [int(lib.clx_conv_workspace_bytes(ctypes.byref(dz), 0))]
-                if self.keep:
-                    need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(dz), 1)))
-                    dl = self._sp_low_dgrad_desc(conv0, sp, None)
-                    dl.algo = 2
-                    need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(dl), 0)))
-                if all(need):
+                dz = self._sp_descs(conv0, sp, query=True)[0]
+                backward = [(dz, 1), (self._sp_low_dgrad_desc(conv0, sp, None), 0)] if self.keep else []
+                if self._takes(2, (dz, 0), *backward):
                     low.wino = low.wino_dgrad = 2
-                    ws_bytes = max([ws_bytes] + need)
-                    low.fused = bool(self._fused_ok(low.Cp, low.rows)
-                                     and int(lib.clx_conv_fused_applicable(ctypes.byref(dz))))
+                    low.fused = self._fused_takes(dz, low.Cp, low.rows)
                     if low.fused:
-                        ws_bytes = max(ws_bytes, int(lib.clx_conv_fused_workspace_bytes(ctypes.byref(dz))))
+                        self.ws_bytes = max(self.ws_bytes, int(lib.clx_conv_fused_workspace_bytes(ctypes.byref(dz))))
             # ... and the 3x3 convolution over the skip tensor as F(4x4, 3x3), forward and weight
             # gradient only: its data gradient has K = N (64 at the benchmark config), too short
             # a contraction for the batched GEMMs to pay
-            if (winograd_enabled() and winograd_code() == 2 and skip.kernel in ((1, 3, 3), (3, 3, 3))
-                    and skip.Cp >= wino_min_channels(skip.kernel)
+            if (code == 2 and skip.kernel in ((1, 3, 3), (3, 3, 3)) and skip.Cp >= wino_min_channels(skip.kernel)
                     and sp.N >= wino_min_channels(skip.kernel) // 2):
-                lib = _clx.load()
-                _dz, ds = self._sp_descs(conv0, sp)
-                ds.algo = 2
-                need = [int(lib.clx_conv_workspace_bytes(ctypes.byref(ds), 0))]
-                if self.keep:
-                    ds.N = sp.N
-                    need.append(int(lib.clx_conv_workspace_bytes(ctypes.byref(ds), 1)))
-                if all(need):
+                ds, dsw = (self._sp_descs(conv0, sp, query=True)[1] for _ in range(2))
+                dsw.N = sp.N
+                if self._takes(2, (ds, 0), *([(dsw, 1)] if self.keep else [])):
                     skip.wino = 2
-                    ws_bytes = max([ws_bytes] + need)
-                    ds.N = conv0.cout
-                    skip.fused = bool(self._fused_ok(skip.Cp, conv0.cout) and conv0.cout == sp.N
-                                      and int(lib.clx_conv_fused_applicable(ctypes.byref(ds))))
+                    skip.fused = conv0.cout == sp.N and self._fused_takes(ds, skip.Cp, conv0.cout)
             # its data gradient contracts over z taps x output channels: long enough only in 3-D
             if skip.wino and self.keep and sp.N * skip.kernel[0] >= WINO_MIN_CHANNELS:
                 dd = self._dgrad_desc(conv0, None)
                 dd.N = skip.Cp
-                dd.algo = 2
-                need = int(_clx.load().clx_conv_workspace_bytes(ctypes.byref(dd), 0))
-                if need:
+                if self._takes(2, (dd, 0)):
                     skip.wino_dgrad = 2
-                    ws_bytes = max(ws_bytes, need)
-            for h in sp.halves:
-                h.w = torch.empty(h.rows * h.C * h.taps, dtype=torch.float32, device=self.device)
-                h.wp_fwd = torch.empty(h.rows_pad * packed_taps(h.wino, h.kernel) * h.Cp, dtype=torch.float32,
-                                       device=self.device)
-        if ws_bytes:
-            self.workspace = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=self.device)
+            low.planes_fwd = bool(low.wino and self._sp_covers(self._sp_descs(conv0, sp, query=True)[0], 0,
+                                                               3 if low.fused else low.wino))
         self._decide_sp()
-        # packed weights (with their P3 planes where the split-precision products read them)
-        self.wpack_fwd = {}
-        self.wpack_dgrad = {}
-        for layer in t.convs:
-            self.wpack_fwd[layer.name] = torch.empty(
-                pad4(layer.cout) * packed_taps(self.algo[layer.name]["fwd"], layer.kernel) * layer.cin_pad,
-                dtype=torch.float32, device=self.device)
-            if self.sp_pass[layer.name][0]:
-                self._register_wplanes(self.wpack_fwd[layer.name], layer.cin_pad)
-        for info in t.r_info:
-            sp = self.subpixel.get(info["conv0"].name)
-            if sp and sp.low.wino and self._sp_covers(self._sp_descs(info["conv0"], sp)[0], 0,
-                                                      3 if sp.low.fused else sp.low.wino):
-                self._register_wplanes(sp.low.wp_fwd, sp.low.Cp)
         # scratch for the planes of a 1x1 layer's input (a training plan keeps one buffer per layer instead)
         rows_k = [(self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2], layer.cin_pad)
                   for layer in t.convs if self.sp_pass[layer.name][0] and not self.algo[layer.name]["fwd"]]
-        if rows_k:
-            self.aplanes = torch.empty(max(int(_clx.load().clx_planes_bytes(r, k)) for r, k in rows_k),
-                                       dtype=torch.uint8, device=self.device)
-        self._packed_version = None
-        self._bwd_ready = False
-        self.vcache = {}
-        self._vcache_fresh = set()
+        self.aplanes_bytes = max((int(lib.clx_planes_bytes(r, k)) for r, k in rows_k), default=0)
         self._find_chains()
         # 2 x 2 max-pooling written by the Winograd output transform of the layer that produces the pooled tensor (2-D:
         # a pooling window lies inside one output tile; clx_conv_desc.pool_out).  CLX_FUSED_POOL=0: the separate pass
@@ -598,6 +190,37 @@ class UNetPlan:
                         and tuple(pool.factor) == (1, 2, 2) and layer.cout % 4 == 0 and layer.name not in self.subpixel
                         and layer.out_shape[1] % 2 == 0 and layer.out_shape[2] % 2 == 0):
                     self.fused_pool[layer.name] = pool
+
+    # ------------------------------------------------------------------ memory
+    def _alloc(self):
+        """Phase two: the device memory of the forward pass, as _decide sized it."""
+        t = self.topo
+        for name, (shape, c) in t.shapes.items():
+            n = self.B * shape[0] * shape[1] * shape[2]
+            self.buf[name] = _clx.zeros((n, pad4(c)), torch.float32, self.device)
+        for sp in self.subpixel.values():
+            n = self.B * sp.zshape[0] * sp.zshape[1] * sp.zshape[2]
+            self.buf[sp.zname] = _clx.zeros((n, sp.low.rows), torch.float32, self.device)
+            for h in sp.halves:
+                h.w = torch.empty(h.rows * h.C * h.taps, dtype=torch.float32, device=self.device)
+                h.wp_fwd = torch.empty(h.rows_pad * packed_taps(h.wino, h.kernel) * h.Cp, dtype=torch.float32,
+                                       device=self.device)
+        if self.ws_bytes:
+            self.workspace = self._float_scratch(self.ws_bytes)
+        # packed weights (with their P3 planes where the split-precision products read them)
+        self.wpack_fwd = {}
+        self.wpack_dgrad = {}
+        for layer in t.convs:
+            self.wpack_fwd[layer.name] = torch.empty(
+                pad4(layer.cout) * packed_taps(self.algo[layer.name]["fwd"], layer.kernel) * layer.cin_pad,
+                dtype=torch.float32, device=self.device)
+            if self.sp_pass[layer.name][0]:
+                self._register_wplanes(self.wpack_fwd[layer.name], layer.cin_pad)
+        for sp in self.subpixel.values():
+            if sp.low.planes_fwd:
+                self._register_wplanes(sp.low.wp_fwd, sp.low.Cp)
+        if self.aplanes_bytes:
+            self.aplanes = torch.empty(self.aplanes_bytes, dtype=torch.uint8, device=self.device)
 
     def share_from(self, other):
         """Use `other`'s packed weights and gradient accumulators (same topology, batch size and switches): this
@@ -631,38 +254,29 @@ class UNetPlan:
             self.chains[a.name] = (a, b)
             self.chain_second[b.name] = (a, b)
 
-    def _alloc_backward(self):
+    def _subpixel_layers(self):
+        """(layer, its record) of every convolution that runs in the sub-pixel form"""
+        return [(info["conv0"], self.subpixel[info["conv0"].name]) for info in self.topo.r_info
+                if info["conv0"].name in self.subpixel]
+
+    def _decide_backward(self):
+        """Phase one of the backward half, taken with its allocation on the first training step (its switches are read
+        then): which tensors get ReLU gate bits, the adjoint data gradients, which transformed tensors and operand planes
+        are kept, and the size of each.  Allocates nothing."""
         t = self.topo
-        self.gbuf = {}
-        for name, (shape, c) in t.shapes.items():
-            if name == "raw":
-                continue
-            n = self.B * shape[0] * shape[1] * shape[2]
-            self.gbuf[name] = _clx.zeros((n, pad4(c)), torch.float32, self.device)
-        for info in t.r_info:
-            layer = info["conv0"]
-            n = self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2]
-            sp = self.subpixel.get(layer.name)
-            if sp is None:
-                self.gbuf["cat%d" % info["level"]] = _clx.zeros((n, layer.cin_pad), torch.float32, self.device)
-            else:
-                skip, low = sp.halves
-                self.gbuf["dskip%d" % info["level"]] = _clx.zeros((n, skip.Cp), torch.float32, self.device)
-                self.gbuf[sp.zname] = _clx.zeros(tuple(self.buf[sp.zname].shape), torch.float32, self.device)
-                dz, ds = self._sp_descs(layer, sp)
-                for h, d in ((skip, ds), (low, dz)):
-                    h.wp_dgrad = torch.empty(h.Cp * packed_taps(h.wino_dgrad, h.kernel) * h.rows_pad, dtype=torch.float32,
-                                             device=self.device)
-                    h.g = torch.empty(h.rows * h.C * h.taps, dtype=torch.float32, device=self.device)
-                    if h.wino and not h.fused and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                        h.vcache = self._float_scratch(self._vcache_bytes(d, h.wino, 0))
-                if low.wino and self._sp_covers(self._sp_low_dgrad_desc(layer, sp, None), 0, low.wino):
-                    self._register_wplanes(low.wp_dgrad, low.rows, dgrad=True)
+        lib = _clx.load()
+        keep_v = os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0"
+        for layer, sp in self._subpixel_layers():
+            dz, ds = self._sp_descs(layer, sp, query=True)
+            for h, d in ((sp.skip, ds), (sp.low, dz)):
+                h.vcache_bytes = self._vcache_bytes(d, h.wino, 0) if h.wino and not h.fused and keep_v else None
+            sp.low.planes_dgrad = bool(sp.low.wino
+                                       and self._sp_covers(self._sp_low_dgrad_desc(layer, sp, None), 0, sp.low.wino))
         # ReLU gates as bits: written by the epilogue that produces a layer's output, read by the data
         # gradient that passes through that ReLU — 1/32 of the float tensor it would otherwise read (the
         # 64-channel 1x1 layers of the 3-D network are HBM-bound).  Whole words per pixel (channels %
         # 32 == 0) and a producer that knows the bits (not the first-layer kernels); CLX_GATE_BITS=0 = off
-        self.gate = {}
+        self.gate_shape = {}
         # (the fused 1x1 pairs gate by the float tensors they read anyway: no bits for their input and middle)
         chain_gated = {a.out for a, _b in self.chains.values()} | {a.sources[0].tensor for a, _b in self.chains.values()}
         if os.environ.get("CLX_GATE_BITS", "1") != "0":
@@ -671,7 +285,7 @@ class UNetPlan:
                     continue
                 if layer.relu and layer.param_index > 0 and pad4(layer.cout) % 32 == 0:
                     n = self.B * layer.out_shape[0] * layer.out_shape[1] * layer.out_shape[2]
-                    self.gate[layer.out] = _clx.zeros((n, pad4(layer.cout) // 32), torch.int32, self.device)
+                    self.gate_shape[layer.out] = (n, pad4(layer.cout) // 32)
         # F(4x4, 3x3[x3]) layers whose weight AND data gradient are Winograd: the data gradient in its ADJOINT form,
         # dX = sum over tiles of B [U^T (A dY A^T)] B^T — its operand A dY A^T is what the weight gradient has just left
         # in the workspace, so dY is transformed once and the (K-1)-padded input transform of dY is never written
@@ -685,40 +299,32 @@ class UNetPlan:
                     self.adjoint.add(layer.name)
         # a Winograd layer's weight gradient and data gradient both transform dY: one pass produces both
         # (clx_conv_desc.dy_vcache); the buffer is shared by all layers (written and consumed back to back)
-        self.dycache = None
+        self.dycache_bytes = 0
         if os.environ.get("CLX_DY_DUAL", "1") != "0":
-            need = 0
             for layer in t.convs:
                 a = self.algo[layer.name]
                 if a["wgrad"] and a["wgrad"] == a["dgrad"] and layer.name not in self.subpixel and layer.name not in self.adjoint:
-                    d = self._desc(layer, pad4(layer.cout))
-                    need = max(need, self._vcache_bytes(d, a["wgrad"], 1))
-            for info in t.r_info:
-                sp = self.subpixel.get(info["conv0"].name)
-                if sp and sp.low.wino:
-                    need = max(need, self._vcache_bytes(self._sp_descs(info["conv0"], sp)[0], sp.low.wino, 1))
-            if need:
-                self.dycache = self._float_scratch(need)
+                    d = self._desc(layer, pad4(layer.cout), query=True)
+                    self.dycache_bytes = max(self.dycache_bytes, self._vcache_bytes(d, a["wgrad"], 1))
+            for layer, sp in self._subpixel_layers():
+                if sp.low.wino:
+                    dz = self._sp_descs(layer, sp, query=True)[0]
+                    self.dycache_bytes = max(self.dycache_bytes, self._vcache_bytes(dz, sp.low.wino, 1))
         # forward and weight gradient of a Winograd layer transform the same input: keep V
-        self.vcache = {}
+        self.vcache_bytes = {}
         for layer in t.convs:
             a = self.algo[layer.name]
-            if a["fwd"] and a["fwd"] == a["wgrad"] and os.environ.get("CLX_WINOGRAD_VCACHE", "1") != "0":
-                d = self._desc(layer, layer.cout)
-                self.vcache[layer.name] = self._float_scratch(self._vcache_bytes(d, a["fwd"], 0))
+            if a["fwd"] and a["fwd"] == a["wgrad"] and keep_v:
+                self.vcache_bytes[layer.name] = self._vcache_bytes(self._desc(layer, layer.cout, query=True), a["fwd"], 0)
+        # the packed weight gradients: one accumulator, a slice per layer
         total = 0
         self.dw_off = {}
         for layer in t.convs:
             self.dw_off[layer.name] = total
             total += packed_taps(self.algo[layer.name]["wgrad"], layer.kernel) * pad4(layer.cout) * layer.cin_pad
-            if layer.param_index > 0:  # first layer needs no data gradient
-                self.wpack_dgrad[layer.name] = torch.empty(
-                    layer.cin_pad * packed_taps(self.algo[layer.name]["dgrad"], layer.kernel) * pad4(layer.cout),
-                    dtype=torch.float32, device=self.device)
-                if self.sp_pass[layer.name][1]:
-                    self._register_wplanes(self.wpack_dgrad[layer.name], pad4(layer.cout), dgrad=True)
         # training: the planes of a split 1x1 layer's input stay for its weight gradient; one scratch for the planes of dY
-        need_dy = 0
+        self.xplanes_bytes = {}
+        self.dyplanes_bytes = 0
         for layer in t.convs:
             if layer.name in self.chains or layer.name in self.chain_second:
                 continue
@@ -726,132 +332,93 @@ class UNetPlan:
             fwd_sp, dgrad_sp, wgrad_sp = (on and not a[k] for on, k in zip(self.sp_pass[layer.name], ("fwd", "dgrad", "wgrad")))
             rows = self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2]
             if fwd_sp or wgrad_sp:
-                self.xplanes[layer.name] = self._planes_scratch(rows, layer.cin_pad)
+                self.xplanes_bytes[layer.name] = int(lib.clx_planes_bytes(rows, layer.cin_pad))
             if dgrad_sp or wgrad_sp:
-                need_dy = max(need_dy, int(_clx.load().clx_planes_bytes(rows, pad4(layer.cout))))
-        if need_dy:
-            # two of them: a data gradient reads the planes of its dY out of one while its epilogue writes the planes
-            # of the next layer's dY into the other
-            self.dyplanes = torch.empty(need_dy, dtype=torch.uint8, device=self.device)
-            self.dyplanes2 = torch.empty(need_dy, dtype=torch.uint8, device=self.device)
+                self.dyplanes_bytes = max(self.dyplanes_bytes, int(lib.clx_planes_bytes(rows, pad4(layer.cout))))
         # tensor -> the 1x1 layer that reads it as its one plain source and keeps planes of it
         for layer in t.convs:
-            if layer.name in self.xplanes and pad4(t.shapes[layer.sources[0].tensor][1]) == layer.cin_pad:
+            if layer.name in self.xplanes_bytes and pad4(t.shapes[layer.sources[0].tensor][1]) == layer.cin_pad:
                 self._pointwise_reader[layer.sources[0].tensor] = layer
         # the sub-pixel layers' weight-gradient accumulators live behind the others: one fill zeroes all
-        sp_slices = []
+        self.sp_dw_slices = []
         for sp in self.subpixel.values():
             for h in sp.halves:
                 n = packed_taps(h.wino, h.kernel) * h.rows_pad * h.Cp
-                sp_slices.append((h, total, n))
+                self.sp_dw_slices.append((h, total, n))
                 total += n
-        self.dwpack = _clx.zeros(total, torch.float32, self.device)
+        self.dwpack_numel = total
+
+    def _alloc_backward(self):
+        """Phase two of the backward half: its device memory, as _decide_backward sized it."""
+        self._decide_backward()
+        t = self.topo
+        self.gbuf = {}
+        for name, (shape, c) in t.shapes.items():
+            if name == "raw":
+                continue
+            n = self.B * shape[0] * shape[1] * shape[2]
+            self.gbuf[name] = _clx.zeros((n, pad4(c)), torch.float32, self.device)
+        for info in t.r_info:
+            layer = info["conv0"]
+            n = self.B * layer.in_shape[0] * layer.in_shape[1] * layer.in_shape[2]
+            sp = self.subpixel.get(layer.name)
+            if sp is None:
+                self.gbuf["cat%d" % info["level"]] = _clx.zeros((n, layer.cin_pad), torch.float32, self.device)
+                continue
+            self.gbuf["dskip%d" % info["level"]] = _clx.zeros((n, sp.skip.Cp), torch.float32, self.device)
+            self.gbuf[sp.zname] = _clx.zeros(tuple(self.buf[sp.zname].shape), torch.float32, self.device)
+            for h in sp.halves:
+                h.wp_dgrad = torch.empty(h.Cp * packed_taps(h.wino_dgrad, h.kernel) * h.rows_pad, dtype=torch.float32,
+                                         device=self.device)
+                h.g = torch.empty(h.rows * h.C * h.taps, dtype=torch.float32, device=self.device)
+                if h.vcache_bytes is not None:
+                    h.vcache = self._float_scratch(h.vcache_bytes)
+            if sp.low.planes_dgrad:
+                self._register_wplanes(sp.low.wp_dgrad, sp.low.rows, dgrad=True)
+        self.gate = {name: _clx.zeros(shape, torch.int32, self.device) for name, shape in self.gate_shape.items()}
+        self.dycache = self._float_scratch(self.dycache_bytes) if self.dycache_bytes else None
+        self.vcache = {name: self._float_scratch(n) for name, n in self.vcache_bytes.items()}
+        for layer in t.convs:
+            if layer.param_index > 0:  # first layer needs no data gradient
+                self.wpack_dgrad[layer.name] = torch.empty(
+                    layer.cin_pad * packed_taps(self.algo[layer.name]["dgrad"], layer.kernel) * pad4(layer.cout),
+                    dtype=torch.float32, device=self.device)
+                if self.sp_pass[layer.name][1]:
+                    self._register_wplanes(self.wpack_dgrad[layer.name], pad4(layer.cout), dgrad=True)
+        for name, n in self.xplanes_bytes.items():
+            self.xplanes[name] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        if self.dyplanes_bytes:
+            # two of them: a data gradient reads the planes of its dY out of one while its epilogue writes the planes
+            # of the next layer's dY into the other
+            self.dyplanes = torch.empty(self.dyplanes_bytes, dtype=torch.uint8, device=self.device)
+            self.dyplanes2 = torch.empty(self.dyplanes_bytes, dtype=torch.uint8, device=self.device)
+        self.dwpack = _clx.zeros(self.dwpack_numel, torch.float32, self.device)
         if self.deterministic:
-            lib = _clx.load()
             width = max(pad4(layer.cout) for layer in t.convs)
             self._det_turns = _clx.zeros(1 << 20, torch.int32, self.device)     # 4 MB of turn counters
-            self._det_colsum = torch.empty(int(lib.clx_colsum_scratch_bytes(width)) // 4, dtype=torch.float32,
+            self._det_colsum = torch.empty(int(_clx.load().clx_colsum_scratch_bytes(width)) // 4, dtype=torch.float32,
                                            device=self.device)
-        for h, off, n in sp_slices:
+        for h, off, n in self.sp_dw_slices:
             h.dw = self.dwpack[off:off + n]
-        # tensor -> the convolution / the pooling that produces it (backward_steps routes gradients by them)
-        self._conv_by_out = {layer.out: layer for layer in t.convs}
-        self._pool_by_out = {p.out: p for p in t.pools}
         self._bwd_ready = True
 
     # --------------------------------------------------------------- sub-pixel
-    def _subpixel_geometry(self, layer: ConvLayer):
-        """A convolution over cat(skip, nearest-upsample(low)) equals, exactly,
-             conv(skip) + depth_to_space( conv_{2^d taps}(low, phase-summed weights) )
-        because the k=3 taps of an output pixel with parity a fall on only two low-res rows.
-        Returns the geometry of that rewrite or None when it does not apply (odd crop, odd
-        output extent, cropped low-res grid, CLX_SUBPIXEL=0)."""
-        if os.environ.get("CLX_SUBPIXEL", "1") == "0" or len(layer.sources) != 2:
-            return None
-        skip_s, up_s = layer.sources
-        f, k, o = up_s.factor, layer.kernel, up_s.crop
-        if max(f) != 2 or min(f) < 1 or skip_s.factor != (1, 1, 1):
-            return None
-        low_shape, low_c = self.topo.shapes[up_s.tensor]
-        zshape, zk, zcrop = [], [], []
-        for d in range(3):
-            if f[d] == 2:
-                if k[d] != 3 or o[d] % 2 != 0 or layer.out_shape[d] % 2 != 0:
-                    return None
-                zshape.append(layer.out_shape[d] // 2)
-                zk.append(2)
-                zcrop.append(o[d] // 2)
-            else:
-                zshape.append(layer.out_shape[d])
-                zk.append(k[d])
-                zcrop.append(o[d])
-            # the Z convolution must read the WHOLE low-res grid (its dgrad writes all of it)
-            if zcrop[d] != 0 or zshape[d] + zk[d] - 1 != low_shape[d]:
-                return None
-        level = [i["level"] for i in self.topo.r_info if i["conv0"] is layer][0]
-        P, N = f[0] * f[1] * f[2], pad4(layer.cout)
-        return Subpixel(fac=f, P=P, N=N, zshape=tuple(zshape), zname="Z%d" % level, level=level,
-                        skip=SubpixelHalf(rows=layer.cout, rows_pad=N, C=skip_s.channels, Cp=pad4(skip_s.channels),
-                                          kernel=tuple(layer.kernel)),
-                        low=SubpixelHalf(rows=P * N, rows_pad=P * N, C=up_s.channels, Cp=pad4(up_s.channels),
-                                         kernel=tuple(zk)))
-
-    @staticmethod
-    def _phase_sum(w, axis, a):
-        """3 taps -> 2 taps along `axis` for output parity `a`: the taps that land on the same
-        low-res row are summed (a = 0: {0,1},{2};  a = 1: {0},{1,2}).  Elementwise torch ops."""
-        t0, t1, t2 = w.select(axis, 0), w.select(axis, 1), w.select(axis, 2)
-        pair = (t0 + t1, t2) if a == 0 else (t0, t1 + t2)
-        return torch.stack(pair, dim=axis)
-
-    @staticmethod
-    def _phase_spread(g, axis, a):
-        """adjoint of _phase_sum: 2 taps -> 3 taps."""
-        g0, g1 = g.select(axis, 0), g.select(axis, 1)
-        trip = (g0, g0, g1) if a == 0 else (g0, g1, g1)
-        return torch.stack(trip, dim=axis)
-
     def _phase_weights(self, layer, sp, w_up):
-        """w_up (cout, C1, kd, kh, kw) -> phase-summed (P*N, C1, zkd, zkh, zkw); rows of padded
-        output channels are zero.  Tiny tensors: plain elementwise torch ops.  (The statement of the algebra the tests
-        check clx_subpixel_split_weights against, not a launch path: `sp` is any mapping with fac, P, N, C1 and zk.)"""
-        f, N, cout = sp["fac"], sp["N"], layer.cout
-        out = w_up.new_zeros((sp["P"], N, sp["C1"]) + sp["zk"])
-        for a in range(f[0]):
-            for b in range(f[1]):
-                for c in range(f[2]):
-                    v = w_up
-                    for axis, (ff, par) in enumerate(zip(f, (a, b, c))):
-                        if ff == 2:
-                            v = self._phase_sum(v, 2 + axis, par)
-                    out[(a * f[1] + b) * f[2] + c, :cout] = v
-        return out.reshape((sp["P"] * N, sp["C1"]) + sp["zk"])
+        return phase_weights(layer, sp, w_up)
 
     def _fold_phase_grads(self, layer, sp, dweff):
-        """adjoint of _phase_weights: (P*N, C1, zk...) -> (cout, C1, kd, kh, kw)."""
-        f, N, cout = sp["fac"], sp["N"], layer.cout
-        g = dweff.reshape((sp["P"], N, sp["C1"]) + sp["zk"])
-        out = dweff.new_zeros((cout, sp["C1"]) + tuple(layer.kernel))
-        for a in range(f[0]):
-            for b in range(f[1]):
-                for c in range(f[2]):
-                    v = g[(a * f[1] + b) * f[2] + c, :cout]
-                    for axis, (ff, par) in enumerate(zip(f, (a, b, c))):
-                        if ff == 2:
-                            v = self._phase_spread(v, 2 + axis, par)
-                    out += v
-        return out
+        return fold_phase_grads(layer, sp, dweff)
 
-    def _sp_descs(self, layer, sp):
+    def _sp_descs(self, layer, sp, query=False):
         """(Z-convolution descriptor over the low-res tensor, skip-convolution descriptor with the forward pass's N =
-        cout: its weight gradient has N = pad4(cout))."""
+        cout: its weight gradient has N = pad4(cout)).  query: for a geometry-only query (_addr)."""
         t = self.topo
         skip_s, up_s = layer.sources
         low_shape, low_c = t.shapes[up_s.tensor]
         sshape, sc = t.shapes[skip_s.tensor]
-        dz = conv_desc([conv_src(self.buf[up_s.tensor].data_ptr(), sp.low.Cp, pad4(low_c), low_shape)], self.B, low_shape,
+        dz = conv_desc([conv_src(self._addr(up_s.tensor, query), sp.low.Cp, pad4(low_c), low_shape)], self.B, low_shape,
                        sp.low.kernel, (0, 0, 0), sp.low.rows, self.precision)
-        ds = conv_desc([conv_src(self.buf[skip_s.tensor].data_ptr(), sp.skip.Cp, pad4(sc), sshape, crop=skip_s.crop)],
+        ds = conv_desc([conv_src(self._addr(skip_s.tensor, query), sp.skip.Cp, pad4(sc), sshape, crop=skip_s.crop)],
                        self.B, layer.in_shape, layer.kernel, (0, 0, 0), layer.cout, self.precision)
         return dz, ds
 
@@ -963,22 +530,23 @@ class UNetPlan:
         up_s = layer.sources[1]
         low_shape, low_c = self.topo.shapes[up_s.tensor]
         # (geometry-only queries never dereference)
-        dl = conv_desc([conv_src(dzbuf.data_ptr() if dzbuf is not None else 16, low.rows, low.rows, sp.zshape)], self.B,
+        dl = conv_desc([conv_src(dzbuf.data_ptr() if dzbuf is not None else QUERY_PTR, low.rows, low.rows, sp.zshape)], self.B,
                        sp.zshape, low.kernel, tuple(k - 1 for k in low.kernel), low.Cp, self.precision)
         dl.ld_out = pad4(low_c)
         if dzbuf is not None:
             self._set_mask(dl, up_s.tensor)                 # ReLU gate of the low-res tensor
             dl.out = self.gbuf[up_s.tensor].data_ptr()
         else:                                               # geometry-only query
-            dl.mask = self.buf[up_s.tensor].data_ptr()
+            dl.mask = QUERY_PTR
             dl.ld_mask = pad4(low_c)
         return dl
 
     # ------------------------------------------------------------- descriptors
-    def _desc(self, layer: ConvLayer, N):
-        """forward / weight-gradient descriptor of a plain layer with N output channels (cout / pad4(cout))"""
+    def _desc(self, layer: ConvLayer, N, query=False):
+        """forward / weight-gradient descriptor of a plain layer with N output channels (cout / pad4(cout)); query: for a
+        geometry-only query (_addr)"""
         t = self.topo
-        srcs = [conv_src(self.buf[s.tensor].data_ptr(), pad4(s.channels), pad4(t.shapes[s.tensor][1]), t.shapes[s.tensor][0],
+        srcs = [conv_src(self._addr(s.tensor, query), pad4(s.channels), pad4(t.shapes[s.tensor][1]), t.shapes[s.tensor][0],
                          s.crop, s.factor) for s in layer.sources]
         # a raw image with 1-3 channels is stored padded to 4: tell the first-layer kernels
         return conv_desc(srcs, self.B, layer.in_shape, layer.kernel, (0, 0, 0), N, self.precision,
@@ -1033,7 +601,7 @@ class UNetPlan:
                 self.sp_pass[layer.name] = (False, False, False)
                 continue
             a = self.algo[layer.name]
-            d = self._desc(layer, layer.cout)
+            d = self._desc(layer, layer.cout, query=True)
             fwd = self._sp_covers(d, 0, a["fwd"])
             d.N = pad4(layer.cout)
             wgrad = self._sp_covers(d, 1, a["wgrad"])
@@ -1068,14 +636,11 @@ class UNetPlan:
     def _float_scratch(self, nbytes):
         return torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=self.device)
 
-    def _planes_scratch(self, rows, k):
-        return torch.empty(int(_clx.load().clx_planes_bytes(rows, k)), dtype=torch.uint8, device=self.device)
-
     def _dgrad_desc(self, layer: ConvLayer, dy):
         """Data gradient as a convolution of dy (zero padding k-1, flipped transposed weights)."""
         n = pad4(layer.cout)
         # (geometry-only queries never dereference)
-        return conv_desc([conv_src(dy.data_ptr() if dy is not None else 16, n, n, layer.out_shape)], self.B, layer.out_shape,
+        return conv_desc([conv_src(dy.data_ptr() if dy is not None else QUERY_PTR, n, n, layer.out_shape)], self.B, layer.out_shape,
                          layer.kernel, tuple(k - 1 for k in layer.kernel), layer.cin_pad, self.precision)
 
     def _expand_cin(self, layer, w):
@@ -1720,183 +1285,4 @@ def _first_dgrad_kernel_wanted(layer):
     return layer.cin <= 4 and os.environ.get("CLX_FIRST_DGRAD", "1") != "0"
 
 
-def forward_flops(topo, batch):
-    """2 M N K over the convolutions of one forward pass (direct form)."""
-    total = 0
-    for layer in topo.convs:
-        m = batch * layer.out_shape[0] * layer.out_shape[1] * layer.out_shape[2]
-        total += 2 * m * layer.cout * layer.cin * layer.taps
-    return total
-
-
-class _Rows:
-    """Read-only view of a per-tensor buffer dict of the two halves as full-batch tensors (rows are pixels,
-    batch-major: the halves concatenate)."""
-
-    def __init__(self, parts, attr):
-        self._parts, self._attr = parts, attr
-
-    def __getitem__(self, name):
-        return torch.cat([getattr(p, self._attr)[name] for p in self._parts], dim=0)
-
-    def __contains__(self, name):
-        return name in getattr(self._parts[0], self._attr)
-
-    def __bool__(self):
-        return bool(getattr(self._parts[0], self._attr))
-
-    def get(self, name, default=None):
-        return self[name] if name in self else default
-
-    def keys(self):
-        return getattr(self._parts[0], self._attr).keys()
-
-
-def dual_stream_wanted(topo, batch, keep_activations):
-    """Two half batches on two streams (DualPlan)?  Training plans with an even batch whose halves are big enough
-    to fill the device (CLX_STREAMS_MIN_GFLOP per half-batch forward pass, default 100: below that the step is
-    launch-bound and twice the launches cost more than the overlap returns); never in reproducible mode.
-    CLX_STREAMS=1 switches it off."""
-    if not keep_activations or batch < 2 or batch % 2 or os.environ.get("CLX_STREAMS", "2") == "1":
-        return False
-    if os.environ.get("CLX_DETERMINISTIC", "0") == "1":
-        return False
-    return forward_flops(topo, batch // 2) >= float(os.environ.get("CLX_STREAMS_MIN_GFLOP", "100")) * 1e9
-
-
-class DualPlan:
-    """A training batch as two half batches on two HIP streams.
-
-    A step is a strict chain of launches, each either bound by the matrix cores (the GEMMs) or by HBM (Winograd
-    transforms, pooling, fills, the first layer): on one stream the two kinds never overlap.  Two independent half
-    batches do — the transforms of one half run under the GEMMs of the other, and the partial last round of one
-    half's tiles is filled by the other's.  Both halves use ONE set of packed weights and add their weight and bias
-    gradients into ONE set of accumulators (the kernels add with atomics anyway); a layer's packed gradient is
-    unpacked on the caller's stream once both halves have passed that layer, which is also when on_layer_done
-    fires — the data-parallel buckets leave exactly as they do with one stream.
-    Same interface as UNetPlan (pack_weights / forward / backward); CLX_STREAMS=1 keeps one stream."""
-
-    def __init__(self, topo, batch, device, keep_activations):
-        assert batch % 2 == 0 and keep_activations
-        self.topo, self.B, self.device, self.keep = topo, int(batch), device, True
-        self.parts = [UNetPlan(topo, batch // 2, device, True) for _ in range(2)]
-        self.streams = [torch.cuda.Stream(device=device) for _ in range(2)]
-        self._events = [[], [], []]
-        self._shared = False
-        self.buf = _Rows(self.parts, "buf")
-
-    def __getattr__(self, name):            # algo, chains, subpixel, gate, ... : the halves agree
-        if name in ("parts", "streams"):
-            raise AttributeError(name)
-        if name == "gbuf":
-            return _Rows(self.parts, "gbuf")
-        return getattr(self.parts[0], name)
-
-    def pack_weights(self, params, version, need_dgrad):
-        a, b = self.parts
-        a.pack_weights(params, version, need_dgrad)
-        if need_dgrad and not self._shared:
-            b._alloc_backward()
-            b.share_from(a)
-            self._shared = True
-        b._packed_version = a._packed_version
-
-    def _fork(self):
-        main = torch.cuda.current_stream(self.device)
-        for s in self.streams:
-            s.wait_stream(main)
-        return main
-
-    def _join(self, main):
-        for s in self.streams:
-            main.wait_stream(s)
-
-    def forward(self, raw, params, out=None):
-        t = self.topo
-        assert self._shared, "pack_weights(need_dgrad=True) must run before forward"
-        raw = raw.contiguous()
-        if out is None:
-            out = torch.empty((self.B, t.out_channels) + tuple(t.out_shape[3 - t.nd:]), dtype=torch.float32,
-                              device=self.device)
-        h = self.B // 2
-        main = self._fork()
-        for i, (p, s) in enumerate(zip(self.parts, self.streams)):
-            with torch.cuda.stream(s):
-                p.forward(raw[i * h:(i + 1) * h], params, out=out[i * h:(i + 1) * h])
-        self._join(main)
-        return out
-
-    def _event(self, i, k):
-        ev = self._events[i]
-        while len(ev) <= k:
-            ev.append(torch.cuda.Event())
-        return ev[k]
-
-    def backward(self, dout, params, grads, on_layer_done=None, flat_grad=None, dx=None):
-        dout = dout.contiguous()
-        h = self.B // 2
-        self.parts[0].zero_gradients(grads, flat_grad)           # the one set of accumulators, on the caller's stream
-        main = self._fork()
-        # (dx is allocated on the caller's stream before the fork; each half writes its slice on its own stream and the
-        #  join orders both behind the caller)
-        dxs = [dx[:h], dx[h:]] if dx is not None else [None, None]
-        self._backward_halves([dout[:h], dout[h:]], params, grads, on_layer_done, main, dxs=dxs)
-        self._join(main)
-
-    def train_pass(self, raw, params, grads, flat_grad, loss_fn, after_loss=None, on_layer_done=None):
-        """UNetPlan.train_pass with each half's loss on its own stream (no join between the forward and the backward
-        pass); the accumulators are zeroed on the caller's stream while the halves run their forward passes."""
-        t = self.topo
-        assert self._shared, "pack_weights(need_dgrad=True) must run before train_pass"
-        raw = raw.contiguous()
-        out = torch.empty((self.B, t.out_channels) + tuple(t.out_shape[3 - t.nd:]), dtype=torch.float32,
-                          device=self.device)
-        h = self.B // 2
-        main = self._fork()
-        douts = []
-        # (starting the second half behind operation 0 .. 8 of the first — which gains 1.5-3 % on the inference chunks,
-        #  models/unet.py — LOSES 0.3-3 % here, round 4: the step ends at a join and the delay is not recovered)
-        for i, (p, s) in enumerate(zip(self.parts, self.streams)):
-            with torch.cuda.stream(s):
-                o = p.forward(raw[i * h:(i + 1) * h], params, out=out[i * h:(i + 1) * h])
-                douts.append(loss_fn(o, i * h, (i + 1) * h))
-                self._event(i, 0).record(s)
-        self.parts[0].zero_gradients(grads, flat_grad)
-        zeroed = self._event(2, 0)
-        zeroed.record(main)
-        for i, s in enumerate(self.streams):
-            main.wait_event(self._event(i, 0))
-            s.wait_event(zeroed)
-        if after_loss is not None:
-            after_loss()
-        self._backward_halves(douts, params, grads, on_layer_done, main)
-        self._join(main)
-        return out
-
-    def _backward_halves(self, douts, params, grads, on_layer_done, main, dxs=(None, None)):
-        st_main = _clx.stream_ptr(self.device)
-        gens = []
-        for p, s, d, dx in zip(self.parts, self.streams, douts, dxs):
-            with torch.cuda.stream(s):
-                gens.append(p.backward_steps(d, params, grads, dx=dx))
-        k = 1
-        while True:
-            items = []
-            for i, (g, s) in enumerate(zip(gens, self.streams)):
-                with torch.cuda.stream(s):
-                    item = next(g, None)
-                    if item is not None:
-                        self._event(i, k).record(s)
-                items.append(item)
-            if items[0] is None:
-                assert items[1] is None
-                break
-            assert items[1] is not None and items[0][0] == items[1][0]
-            for i in range(2):
-                main.wait_event(self._event(i, k))
-            done, unpack = items[0]                  # (the halves share the accumulators: either closure does)
-            unpack(st_main)
-            if on_layer_done is not None:
-                for idx in done:
-                    on_layer_done(idx)
-            k += 1
+from .dual import DualPlan, dual_stream_wanted  # noqa: E402,F401  (dual.py imports UNetPlan from this module)

@@ -18,8 +18,10 @@ import torch.nn as nn
 import ctypes
 
 from .. import _clx, parallel
-from .._clx import ClxConvDesc, ClxSrc
-from .plan import DualPlan, UNetPlan, build_topology, dual_stream_wanted, forward_flops, pad4
+from .descriptors import conv_desc, conv_src
+from .plan import UNetPlan
+from .dual import DualPlan, dual_stream_wanted      # (after .plan, which dual.py imports)
+from .topology import build_topology, forward_flops, pad4
 
 
 class _ConvPass(nn.Module):
@@ -93,23 +95,8 @@ class _UNetFunction(torch.autograd.Function):
 
 
 def _pointwise_desc(x, B, shape3, cin_p, n):
-    """clx_conv_desc of a 1x1(x1) convolution over a pixel-major (M, cin_p) tensor."""
-    d = ClxConvDesc()
-    d.nsrc = 1
-    src = ClxSrc()
-    src.ptr = x.data_ptr()
-    src.C = cin_p
-    src.ld = cin_p
-    src.D, src.H, src.W = shape3
-    src.oz = src.oy = src.ox = 0
-    src.fz = src.fy = src.fx = 1
-    d.src[0] = src
-    d.B = B
-    d.ID, d.IH, d.IW = shape3
-    d.KD = d.KH = d.KW = 1
-    d.PD = d.PH = d.PW = 0
-    d.N = n
-    return d
+    """clx_conv_desc of a 1x1(x1) convolution over a pixel-major (M, cin_p) tensor, in float32."""
+    return conv_desc([conv_src(x.data_ptr(), cin_p, cin_p, shape3)], B, shape3, (1, 1, 1), (0, 0, 0), n, 0)
 
 
 class _HeadFunction(torch.autograd.Function):

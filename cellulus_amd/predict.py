@@ -26,7 +26,7 @@ from . import _clx, parallel
 from .configs.inference_config import InferenceConfig
 from .datasets.meta_data import DatasetMetaData
 from .datasets.zarr_dataset import default_normalization_factor
-from .models.plan import build_topology
+from .models.topology import build_topology
 from .utils import zarr_io
 
 

@@ -179,7 +179,7 @@ def train(experiment_config):
     # the pair sampler draws coordinates for an output of extent crop_size - 16 (zarr_dataset.py:94): a
     # network whose output is smaller (deeper, other factors) makes the reference fail in its first
     # iteration with an IndexError out of select_and_add_coordinates — say so before any work is done
-    from .models.plan import build_topology
+    from .models.topology import build_topology
 
     topo = build_topology(model.in_channels, model.out_channels, model.num_fmaps, model.fmap_inc_factor,
                           model.features_in_last_layer, model.downsampling_factors, model.num_spatial_dims,
