@@ -203,6 +203,7 @@ PROTOTYPES = {
     "clx_region_intensity": (_I, [_P, _P, _I, _LL, _I, _I, _P, _P, _P, _P]),
     "clx_region_contacts": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "clx_region_perimeter": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "clx_region_topology": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "clx_lz4_decompress": (_LL, [_P, _LL, _P, _LL]),
     "clx_blosclz_decompress": (_LL, [_P, _LL, _P, _LL]),
     "clx_blosc_compress_bound": (_LL, [_LL]),

@@ -1,5 +1,5 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
-(``python -m cellulus_amd.measure <toml> [--contacts]``)."""
+(``python -m cellulus_amd.measure <toml> [--contacts] [--topology]``)."""
 
 import click
 import tomli
@@ -32,7 +32,8 @@ def infer(config_file):
 @click.command()
 @click.argument("config_file", type=click.Path(exists=True))
 @click.option("--contacts", is_flag=True, help="add the boundary columns and write contacts_bandwidth-<b>.csv")
-def measure(config_file, contacts):
+@click.option("--topology", is_flag=True, help="add the Euler numbers and the Crofton perimeter (2-D) / surface area and sphericity (3-D)")
+def measure(config_file, contacts, topology):
     from .measure import measure as measure_experiment
 
-    measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts)
+    measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology)

@@ -5,11 +5,14 @@ channel — from integer sums gathered in one pass over the label map on the dev
 the only rounding in a column is its final division.  On request also what an object's BOUNDARY gives: the faces it
 shares with every other object (``contact_pairs``: the region adjacency graph), with the background and the image edge,
 and in 2-D its border pixels and perimeter (``clx_region_contacts``, ``clx_region_perimeter``), all integer counts too.
+Also on request its TOPOLOGY and smooth boundary measure: the Euler numbers (holes, cavities, tunnels, pieces), the Crofton
+perimeter in 2-D, surface area and sphericity in 3-D, from integer sums over the 2 x 2 (x 2) windows of the map
+(``clx_region_topology``).
 
-    python -m cellulus_amd.measure experiment.toml [--contacts]
+    python -m cellulus_amd.measure experiment.toml [--contacts] [--topology]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
-the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it.
+the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns.
 """
 
 import math
@@ -24,6 +27,15 @@ _INFO_BAD_LABEL, _INFO_FULL = 1, 4      # bits of clx_region_contacts' info[0]
 _SQRT2 = math.sqrt(2.0)
 PERIMETER_WEIGHTS = (0.0, 1.0, _SQRT2, (1.0 + _SQRT2) / 2.0)   # of clx_region_perimeter's classes; [0] counts border pixels
 _SHIFT_MIN, _SHIFT_MAX = -1022, 1023    # 2.0 ** shift stays a normal float64: scaling by it is exact
+# Weights of the 13 line directions of the 26-neighbourhood in the Crofton surface estimate (``topology_columns``): the
+# 26 unit vectors towards a voxel's neighbours cut the sphere into their Voronoi cells (a point belongs to the direction
+# it is nearest to); a weight is the area of a direction's cell over 4 pi, the two antipodes of a line pooled, so that
+# 3 w1 + 6 w2 + 4 w3 = 1 for the 3 axial, 6 face-diagonal and 4 space-diagonal lines.  The cells are spherical polygons
+# (an octagon, a rectangle, a hexagon) whose corners are the points at equal distance from three neighbouring directions,
+# the permutations of (0.28174743, 0.36718039, 0.88645189) with signs; their areas follow from the spherical excess.
+# Computed that way in float64; tests/test_cpu_topology.py recomputes them with scipy.spatial.SphericalVoronoi.
+SURFACE_WEIGHTS = (0.09155578240952184, 0.07396125575215028, 0.07039127956463334)
+_SQRT3 = math.sqrt(3.0)
 
 
 def intensity_shift(max_abs, npix):
@@ -125,6 +137,36 @@ def boundary_columns(present, bbox, shape, a, b, faces, classes, nd):
         classes = np.asarray(classes).reshape(n, 4)
         cols["border_pixels"] = classes[:, 0].astype(np.int64)
         cols["perimeter"] = perimeter_from_classes(classes)
+    return cols
+
+
+def topology_columns(area, counts, nd):
+    """The topology columns of ``region_table`` from integer counts.  area (n) pixel counts, counts (n, 5)
+    ``clx_region_topology``'s rows ``T1 T2 T3 E_hi E_lo`` of the same objects; nd 2 or 3.  ``euler_number`` (8- / 26-
+    connectivity, scikit-image's default) and ``euler_number_conn1`` (4- / 6-connectivity) are ``E / 2**nd``; with
+    ``N1 = T1 / 2**(nd-1)``, ``N2 = T2 / 2**(nd-2)``, ``N3 = T3`` the boundary pairs along the axial, face-diagonal and
+    space-diagonal directions, ``perimeter_crofton = (π/8)·(N1 + N2/√2)`` (2-D, four directions) and ``surface_area =
+    4·(w1·N1/2 + w2·N2/(2√2) + w3·N3/(2√3))``, ``sphericity = π^(1/3)·(6·area)^(2/3) / surface_area`` (3-D).  The
+    divisions by powers of two are exact integer divisions."""
+    assert nd in (2, 3)
+    area = [int(v) for v in np.asarray(area).reshape(-1)]
+    rows = [[int(v) for v in r] for r in np.asarray(counts).reshape(-1, 5)]
+    assert len(area) == len(rows)
+    cell = 1 << nd
+    for r in rows:
+        assert r[0] % (cell // 2) == 0 and r[1] % (cell // 4) == 0 and r[3] % cell == 0 and r[4] % cell == 0, r
+    cols = {"euler_number": np.array([r[3] // cell for r in rows], dtype=np.int64),
+            "euler_number_conn1": np.array([r[4] // cell for r in rows], dtype=np.int64)}
+    n1 = np.array([r[0] // (cell // 2) for r in rows], dtype=np.float64)
+    n2 = np.array([r[1] // (cell // 4) for r in rows], dtype=np.float64)
+    n3 = np.array([r[2] for r in rows], dtype=np.float64)
+    if nd == 2:
+        cols["perimeter_crofton"] = (math.pi / 8.0) * (n1 + n2 / _SQRT2)
+    else:
+        w1, w2, w3 = SURFACE_WEIGHTS
+        surface = 4.0 * (w1 * n1 / 2.0 + w2 * n2 / (2.0 * _SQRT2) + w3 * n3 / (2.0 * _SQRT3))
+        cols["surface_area"] = surface
+        cols["sphericity"] = math.pi ** (1.0 / 3.0) * (6.0 * np.array(area, dtype=np.float64)) ** (2.0 / 3.0) / surface
     return cols
 
 
@@ -298,7 +340,18 @@ def _perimeter_classes(lab, Y, X, nid):
     return classes.cpu().numpy()
 
 
-def region_table(labels, raw=None, device=None, boundary=False):
+def _topology_counts(lab, nd, Z, Y, X, nid):
+    import torch
+
+    counts = torch.empty((nid, 5), dtype=torch.int64, device=lab.device)
+    bad = torch.empty(1, dtype=torch.int32, device=lab.device)
+    _clx.call("clx_region_topology", _clx.ptr(lab), nd, Z, Y, X, nid, _clx.ptr(counts), _clx.ptr(bad), _clx.stream_ptr(lab.device))
+    if int(bad.item()):
+        raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+    return counts.cpu().numpy()
+
+
+def region_table(labels, raw=None, device=None, boundary=False, topology=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -306,11 +359,14 @@ def region_table(labels, raw=None, device=None, boundary=False):
     ``boundary=True`` appends ``boundary_faces`` (faces to anything that is not the object), ``contact_faces`` (to
     other objects), ``num_neighbours`` (objects touched), ``touches_border`` (0 / 1: the bounding box reaches the image
     edge) and in 2-D ``border_pixels`` and ``perimeter`` (scikit-image's 4-neighbourhood formula, restated).
+    ``topology=True`` appends, after those, ``euler_number`` (8- / 26-connectivity, as scikit-image's), ``euler_number_conn1``
+    (4- / 6-connectivity) and in 2-D ``perimeter_crofton`` (four directions), in 3-D ``surface_area`` (Crofton, 13
+    directions) and ``sphericity`` (``topology_columns``).
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
-    return _region_table(labels, raw, device, boundary)[0]
+    return _region_table(labels, raw, device, boundary, topology)[0]
 
 
-def _region_table(labels, raw, device, boundary):
+def _region_table(labels, raw, device, boundary, topology=False):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     import torch
 
@@ -352,16 +408,19 @@ def _region_table(labels, raw, device, boundary):
                 dt = raw_d.cpu().numpy().dtype
                 cols.update({f"intensity_mean_c{k}": np.zeros(0), f"intensity_min_c{k}": np.zeros(0, dt),
                              f"intensity_max_c{k}": np.zeros(0, dt)})
-    if not boundary:
-        return cols, None
-    if len(present):
-        pairs = _contacts(lab, nd, spatial, nid, len(present), "region_table")
-    else:
-        pairs = tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
-    classes = None
-    if nd == 2:
-        classes = _perimeter_classes(lab, Y, X, nid)[present] if len(present) else np.zeros((0, 4), dtype=np.int64)
-    cols.update(boundary_columns(present, bbox, spatial, *pairs, classes, nd))
+    pairs = None
+    if boundary:
+        if len(present):
+            pairs = _contacts(lab, nd, spatial, nid, len(present), "region_table")
+        else:
+            pairs = tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+        classes = None
+        if nd == 2:
+            classes = _perimeter_classes(lab, Y, X, nid)[present] if len(present) else np.zeros((0, 4), dtype=np.int64)
+        cols.update(boundary_columns(present, bbox, spatial, *pairs, classes, nd))
+    if topology:
+        counts = _topology_counts(lab, nd, Z, Y, X, nid)[present] if len(present) else np.zeros((0, 5), dtype=np.int64)
+        cols.update(topology_columns(area[present], counts, nd))
     return cols, pairs
 
 
@@ -369,12 +428,12 @@ def _format(value):
     return "%.17g" % value if isinstance(value, (float, np.floating)) else "%d" % value
 
 
-def measure(inference_config, contacts=False) -> None:
+def measure(inference_config, contacts=False, topology=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
     and writes ``contacts_bandwidth-<b>.csv`` beside it: ``sample,label_a,label_b,faces``, one line per pair of
-    objects that touch.  Rank 0 works alone under torch.distributed."""
+    objects that touch.  ``topology=True`` adds the topology columns.  Rank 0 works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -396,7 +455,7 @@ def measure(inference_config, contacts=False) -> None:
         header, lines, pair_lines = None, [], []
         for sample in range(meta.num_samples):
             labels = ds_seg[sample, bandwidth].astype(np.int32)
-            table, pairs = _region_table(labels, ds_raw[sample], device, contacts)
+            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

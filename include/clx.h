@@ -962,6 +962,30 @@ int clx_region_contacts(const int32_t* labels, int nd, int Z, int Y, int X, int 
  * Refused before any launch: null pointers, a non-positive extent, nid outside [1, 2^24], Y*X >= 2^32. */
 int clx_region_perimeter(const int32_t* labels, int Y, int X, int nid, unsigned long long* classes,
                          int32_t* bad, clx_stream stream);
+/* Topology: per object the sums over all 2 x 2 (nd == 2) / 2 x 2 x 2 (nd == 3) windows of the label map [Z][Y][X], from
+ * which the caller forms the Euler numbers, the Crofton perimeter (2-D) and the surface area (3-D) of every object
+ * (cellulus_amd.measure.topology_columns).  The map is padded with id 0 on both ends of every counted axis: y and x for
+ * nd == 2 (Z must be 1), z, y and x for nd == 3 (Z == 1 allowed).
+ *   window    the 2^nd voxels of the padded map around one lattice vertex: (Y+1)(X+1) resp. (Z+1)(Y+1)(X+1) of them
+ *   bits      for an id i > 0: bit b_v = [voxel v of the window == i]; other objects, background and outside are "not i".
+ *             A window with no bit or with every bit set adds nothing to i
+ *   d-cell    through the vertex: a choice of d of the nd axes and a side along each (C(nd,d) 2^d of them); its voxels
+ *             are the 2^(nd-d) window voxels on the chosen sides
+ *   counts [nid][5], summed over all windows:
+ *     [0] T1    voxel pairs of the window that differ in exactly one coordinate and have different bits
+ *     [1] T2    the same for pairs that differ in exactly two coordinates
+ *     [2] T3    the same for pairs that differ in three coordinates (0 for nd == 2)
+ *     [3] E_hi  sum over d of (-1)^d 2^(nd-d) #{d-cells that touch at least one set voxel}
+ *     [4] E_lo  sum over d of (-1)^(nd-d) 2^(nd-d) #{d-cells all of whose voxels are set}
+ *   so that T1 = 2^(nd-1) (faces between i and not-i), T2 = 2^(nd-2) (face-diagonal neighbour pairs i / not-i), T3 = space-
+ *   diagonal pairs, E_hi = 2^nd (Euler number under 8- / 26-connectivity), E_lo = 2^nd (Euler number under 4- / 6-
+ *   connectivity); in 2-D E_hi / E_lo = Q1 - Q3 -/+ 2 QD, Gray's bit quads.  E_hi and E_lo may be negative.
+ *   bad [1]   1: a label outside [0, nid) -- never followed as an index, treated as 0
+ * Outputs are initialised by the entry point; row 0 is unspecified.  Integer adds only: the same bits in every run.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent,
+ * Z*Y*X >= 2^32, nid outside [1, 2^24]. */
+int clx_region_topology(const int32_t* labels, int nd, int Z, int Y, int X, int nid,
+                        long long* counts, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
