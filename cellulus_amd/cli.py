@@ -1,5 +1,5 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
-(``python -m cellulus_amd.measure <toml> [--contacts] [--topology]``)."""
+(``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull]``)."""
 
 import click
 import tomli
@@ -33,7 +33,8 @@ def infer(config_file):
 @click.argument("config_file", type=click.Path(exists=True))
 @click.option("--contacts", is_flag=True, help="add the boundary columns and write contacts_bandwidth-<b>.csv")
 @click.option("--topology", is_flag=True, help="add the Euler numbers and the Crofton perimeter (2-D) / surface area and sphericity (3-D)")
-def measure(config_file, contacts, topology):
+@click.option("--hull", is_flag=True, help="add the convex hull columns: convex area, solidity, maximum / minimum Feret diameter")
+def measure(config_file, contacts, topology, hull):
     from .measure import measure as measure_experiment
 
-    measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology)
+    measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology, hull=hull)

@@ -7,12 +7,15 @@ shares with every other object (``contact_pairs``: the region adjacency graph), 
 and in 2-D its border pixels and perimeter (``clx_region_contacts``, ``clx_region_perimeter``), all integer counts too.
 Also on request its TOPOLOGY and smooth boundary measure: the Euler numbers (holes, cavities, tunnels, pieces), the Crofton
 perimeter in 2-D, surface area and sphericity in 3-D, from integer sums over the 2 x 2 (x 2) windows of the map
-(``clx_region_topology``).
+(``clx_region_topology``).  And its CONVEX HULL: convex area, solidity and the maximum / minimum Feret diameter from the hull
+of the pixels' corner points, exact integers again (``clx_region_hull``; the definitions are the project's own, not
+scikit-image's rasterised ones: ``hull_columns``).
 
-    python -m cellulus_amd.measure experiment.toml [--contacts] [--topology]
+    python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
-the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns.
+the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns,
+``--hull`` the convex hull columns.
 """
 
 import math
@@ -168,6 +171,44 @@ def topology_columns(area, counts, nd):
         cols["surface_area"] = surface
         cols["sphericity"] = math.pi ** (1.0 / 3.0) * (6.0 * np.array(area, dtype=np.float64)) ** (2.0 / 3.0) / surface
     return cols
+
+
+def _sqrt_ratio(num, den):
+    """``sqrt(num / den)`` of Python ints (``num >= 0``, ``den > 0``) as a float64, correctly rounded: the integer square
+    root of the ratio scaled to more than 60 bits, a sticky bit for what it drops, one int -> float conversion"""
+    num, den = int(num), int(den)
+    assert num >= 0 and den > 0
+    if num == 0:
+        return 0.0
+    k = max(0, (124 + den.bit_length() - num.bit_length()) // 2)
+    scaled = num << (2 * k)
+    q = scaled // den
+    s = math.isqrt(q)
+    sticky = int(s * s != q or q * den != scaled)
+    return math.ldexp(float(2 * s + sticky), -(k + 1))
+
+
+def hull_columns(area, hull, nd):
+    """The convex hull columns of ``region_table`` from integers.  area (n) pixel counts, hull (n, 5)
+    ``clx_region_hull``'s rows ``A2 NV F2 C L2`` of the same objects; nd 2 or 3.  The object is the union of its pixels as
+    closed unit squares (cubes), its hull that of the pixels' corner points: NOT scikit-image's definitions, which count
+    the pixels of the rasterised ``convex_hull_image`` and take the Feret diameter from a contour.  2-D: ``area_convex =
+    A2 / 2``, ``solidity = area / area_convex`` (at most 1), ``feret_diameter_max = sqrt(F2)``, ``feret_diameter_min =
+    C / sqrt(L2)`` (the minimum caliper width, ImageJ's MinFeret) and ``hull_vertices = NV`` (int64); a one-pixel object
+    has 1, 1.0, sqrt 2, 1.0, 4.  3-D: ``feret_diameter_max`` only; convex volume and solidity in 3-D are not computed.
+    Every float is one correctly rounded operation on exact integers."""
+    assert nd in (2, 3)
+    area = [int(v) for v in np.asarray(area).reshape(-1)]
+    rows = [[int(v) for v in r] for r in np.asarray(hull).reshape(-1, 5)]
+    assert len(area) == len(rows)
+    feret_max = np.array([_sqrt_ratio(r[2], 1) for r in rows], dtype=np.float64)
+    if nd == 3:
+        return {"feret_diameter_max": feret_max}
+    return {"area_convex": np.array([r[0] / 2 for r in rows], dtype=np.float64),
+            "solidity": np.array([2 * a / r[0] for a, r in zip(area, rows)], dtype=np.float64),
+            "feret_diameter_max": feret_max,
+            "feret_diameter_min": np.array([_sqrt_ratio(r[3] * r[3], r[4]) for r in rows], dtype=np.float64),
+            "hull_vertices": np.array([r[1] for r in rows], dtype=np.int64)}
 
 
 def _resolve_device(labels, device):
@@ -351,7 +392,35 @@ def _topology_counts(lab, nd, Z, Y, X, nid):
     return counts.cpu().numpy()
 
 
-def region_table(labels, raw=None, device=None, boundary=False, topology=False):
+def _hull_rows(lab, nd, Z, Y, X, nid, bbox_d, bbox, present):
+    """one clx_region_hull call on clx_region_moments' bounding boxes (bbox_d on the device, bbox: its host copy)
+    -> hull int64 (nid, 5)"""
+    import torch
+
+    device = lab.device
+    box = bbox[present].astype(np.int64)
+    nrows = np.zeros(nid, dtype=np.int64)
+    nrows[present] = (box[:, 3] - box[:, 0] + 1) * (box[:, 4] - box[:, 1] + 1)
+    row_base = np.cumsum(nrows) - nrows                      # exclusive; absent ids have no rows
+    rows = int(nrows.sum())
+    nbytes = int(_clx.load().clx_region_hull_workspace(rows))
+    if nbytes == 0:
+        raise ValueError("region_table: too many bounding-box rows for clx_region_hull")
+    workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    row_base_d = torch.from_numpy(row_base).to(device)
+    hull = torch.empty((nid, 5), dtype=torch.int64, device=device)
+    bad = torch.empty(1, dtype=torch.int32, device=device)
+    _clx.call("clx_region_hull", _clx.ptr(lab), nd, Z, Y, X, nid, _clx.ptr(bbox_d), _clx.ptr(row_base_d), rows,
+              _clx.ptr(workspace), nbytes, _clx.ptr(hull), _clx.ptr(bad), _clx.stream_ptr(device))
+    flags = int(bad.item())
+    if flags & 1:
+        raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+    if flags & 2:
+        raise ValueError("region_table: label ids changed under the measurement")
+    return hull.cpu().numpy()
+
+
+def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -362,11 +431,14 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False):
     ``topology=True`` appends, after those, ``euler_number`` (8- / 26-connectivity, as scikit-image's), ``euler_number_conn1``
     (4- / 6-connectivity) and in 2-D ``perimeter_crofton`` (four directions), in 3-D ``surface_area`` (Crofton, 13
     directions) and ``sphericity`` (``topology_columns``).
+    ``hull=True`` appends, after those, in 2-D ``area_convex``, ``solidity``, ``feret_diameter_max``, ``feret_diameter_min``
+    and ``hull_vertices``, in 3-D ``feret_diameter_max``: the hull of the pixels' corner points, which is not
+    scikit-image's rasterised definition (``hull_columns``).
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
-    return _region_table(labels, raw, device, boundary, topology)[0]
+    return _region_table(labels, raw, device, boundary, topology, hull)[0]
 
 
-def _region_table(labels, raw, device, boundary, topology=False):
+def _region_table(labels, raw, device, boundary, topology=False, hull=False):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     import torch
 
@@ -378,6 +450,7 @@ def _region_table(labels, raw, device, boundary, topology=False):
                              np.zeros((0, 3), np.uint64), np.zeros((0, 6), np.uint64), nd)
         present = np.zeros(0, dtype=np.int64)
         bbox = np.zeros((0, 6), dtype=np.int32)
+        bbox_d = bbox_all = None
     else:
         area_d = torch.empty(nid, dtype=torch.int64, device=device)
         bbox_d = torch.empty((nid, 6), dtype=torch.int32, device=device)
@@ -391,7 +464,8 @@ def _region_table(labels, raw, device, boundary, topology=False):
         area = area_d.cpu().numpy()
         area[0] = 0
         present = np.flatnonzero(area > 0)
-        bbox = bbox_d.cpu().numpy()[present]
+        bbox_all = bbox_d.cpu().numpy()
+        bbox = bbox_all[present]
         cols = shape_columns(present, area[present], bbox,
                              sum1_d.cpu().numpy().view(np.uint64)[present],
                              sum2_d.cpu().numpy().view(np.uint64)[present], nd)
@@ -421,6 +495,9 @@ def _region_table(labels, raw, device, boundary, topology=False):
     if topology:
         counts = _topology_counts(lab, nd, Z, Y, X, nid)[present] if len(present) else np.zeros((0, 5), dtype=np.int64)
         cols.update(topology_columns(area[present], counts, nd))
+    if hull:
+        ints = _hull_rows(lab, nd, Z, Y, X, nid, bbox_d, bbox_all, present)[present] if len(present) else np.zeros((0, 5), dtype=np.int64)
+        cols.update(hull_columns(area[present], ints, nd))
     return cols, pairs
 
 
@@ -428,12 +505,13 @@ def _format(value):
     return "%.17g" % value if isinstance(value, (float, np.floating)) else "%d" % value
 
 
-def measure(inference_config, contacts=False, topology=False) -> None:
+def measure(inference_config, contacts=False, topology=False, hull=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
     and writes ``contacts_bandwidth-<b>.csv`` beside it: ``sample,label_a,label_b,faces``, one line per pair of
-    objects that touch.  ``topology=True`` adds the topology columns.  Rank 0 works alone under torch.distributed."""
+    objects that touch.  ``topology=True`` adds the topology columns, ``hull=True`` the convex hull columns.  Rank 0 works
+    alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -455,7 +533,7 @@ def measure(inference_config, contacts=False, topology=False) -> None:
         header, lines, pair_lines = None, [], []
         for sample in range(meta.num_samples):
             labels = ds_seg[sample, bandwidth].astype(np.int32)
-            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology)
+            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

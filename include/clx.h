@@ -986,6 +986,39 @@ int clx_region_perimeter(const int32_t* labels, int Y, int X, int nid, unsigned 
  * Z*Y*X >= 2^32, nid outside [1, 2^24]. */
 int clx_region_topology(const int32_t* labels, int nd, int Z, int Y, int X, int nid,
                         long long* counts, int32_t* bad, clx_stream stream);
+/* Convex hull: per object the integers behind area_convex, solidity and the maximum / minimum Feret diameter
+ * (cellulus_amd.measure.hull_columns forms the columns).  Label map [Z][Y][X]; nd == 2 needs Z == 1.
+ * Definitions -- NOT scikit-image's, which counts the pixels of the rasterised convex_hull_image and takes the Feret
+ * diameter from a contour; no fixture compares with it:
+ *   object    the union of its pixels as closed unit squares (3-D: unit cubes): pixel (y, x) has the corners
+ *             (y .. y+1, x .. x+1), and the hull of the object is the hull of its pixels' corner lattice points.  Everything
+ *             stays an integer and solidity = area / area_convex <= 1.  One pixel: area_convex 1, Feret max sqrt 2, min 1
+ *   hull [nid][5], nd == 2:
+ *     [0] A2  twice the area of the hull polygon (shoelace formula)
+ *     [1] NV  its strict vertices (no collinear point counts)
+ *     [2] F2  the largest squared distance between two vertices: feret_diameter_max = sqrt(F2)
+ *     [3] C, [4] L2  the minimum caliper width as an exact rational, C / sqrt(L2): for every hull edge e = b - a,
+ *             c_e = max over the vertices v of |cross(e, v - a)| and l_e = |e|^2; the edge with the smallest c_e^2 / l_e
+ *             is reported (compared exactly, c_a^2 l_b against c_b^2 l_a as 128-bit products), ties towards the smaller l_e
+ *   hull [nid][5], nd == 3: F2 only, the largest squared distance between two corner points of the object's voxels;
+ *             A2 = NV = C = L2 = 0.  Convex volume and solidity in 3-D are not computed.
+ *   bbox      [nid][6] clx_region_moments' output, left on the device
+ *   row_base  [nid] exclusive prefix sum over the ids of (zmax - zmin + 1) (ymax - ymin + 1), 0 rows for an absent id; `rows`
+ *             is the total.  Row (z, y) of object i is row_base[i] + (z - zmin) (ymax - ymin + 1) + (y - ymin)
+ *   workspace at least clx_region_hull_workspace(rows) bytes (a host-only function; 0: rows out of range), 8-byte aligned
+ *   bad [1]   bit 0: a label outside [0, nid) -- never followed as an index, treated as background
+ *             bit 1: a pixel that the bbox / row_base of its id does not contain (a stale or wrong box); it is skipped.
+ *             Boxes and row_base are checked against the image and `rows` before use: no index outside the workspace
+ *             is ever formed, whatever they hold; an id whose box fails that check gets a row of zeros
+ * The entry point initialises hull, bad and the workspace itself.  Row 0 and the rows of absent ids are zero.  Integer
+ * operations only: the same map gives the same bits in every run.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent, an
+ * extent >= 2^30, Z*Y*X >= 2^32, nid outside [1, 2^24], nd == 2 with (Y+1)(X+1) > 2^31 (C^2 must fit 64 bits), rows outside
+ * [0, (nid - 1) Z Y], workspace_bytes below clx_region_hull_workspace(rows), a workspace that is not 8-byte aligned. */
+size_t clx_region_hull_workspace(long long rows);
+int clx_region_hull(const int32_t* labels, int nd, int Z, int Y, int X, int nid, const int32_t* bbox,
+                    const long long* row_base, long long rows, void* workspace, size_t workspace_bytes,
+                    long long* hull, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
