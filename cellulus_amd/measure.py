@@ -9,13 +9,15 @@ Also on request its TOPOLOGY and smooth boundary measure: the Euler numbers (hol
 perimeter in 2-D, surface area and sphericity in 3-D, from integer sums over the 2 x 2 (x 2) windows of the map
 (``clx_region_topology``).  And its CONVEX HULL: convex area, solidity and the maximum / minimum Feret diameter from the hull
 of the pixels' corner points, exact integers again (``clx_region_hull``; the definitions are the project's own, not
-scikit-image's rasterised ones: ``hull_columns``).
+scikit-image's rasterised ones: ``hull_columns``).  And its THICKNESS: the largest inscribed circle / ball and where it sits,
+from the label-aware distance map (``label_distance_sq``: for every object pixel the squared distance to the nearest pixel
+of another value; ``clx_label_distance_sq``, ``clx_region_inscribed``, ``inscribed_columns``).
 
-    python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull]
+    python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull] [--inscribed]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
 the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns,
-``--hull`` the convex hull columns.
+``--hull`` the convex hull columns, ``--inscribed`` the inscribed circle / ball columns.
 """
 
 import math
@@ -39,6 +41,8 @@ _SHIFT_MIN, _SHIFT_MAX = -1022, 1023    # 2.0 ** shift stays a normal float64: s
 # Computed that way in float64; tests/test_cpu_topology.py recomputes them with scipy.spatial.SphericalVoronoi.
 SURFACE_WEIGHTS = (0.09155578240952184, 0.07396125575215028, 0.07039127956463334)
 _SQRT3 = math.sqrt(3.0)
+DIST_INF = 1 << 30                      # CLX_DIST_INF: a pixel of clx_label_distance_sq's map that has no candidate
+_BAD_LABEL, _BAD_DISTANCE = 1, 2        # bits of clx_region_inscribed's bad[0]
 
 
 def intensity_shift(max_abs, npix):
@@ -209,6 +213,28 @@ def hull_columns(area, hull, nd):
             "feret_diameter_max": feret_max,
             "feret_diameter_min": np.array([_sqrt_ratio(r[3] * r[3], r[4]) for r in rows], dtype=np.float64),
             "hull_vertices": np.array([r[1] for r in rows], dtype=np.int64)}
+
+
+def inscribed_columns(area, rows, shape, nd):
+    """The inscribed circle / ball columns of ``region_table`` from integers.  area (n) pixel counts, rows (n, 3)
+    ``clx_region_inscribed``'s rows ``D2, index, Σd²`` of the same objects, shape the map's ``nd`` extents; nd 2 or 3.
+    ``inscribed_radius = sqrt(D2)``: the largest distance from a pixel centre of the object to the nearest pixel centre
+    that is not the object's (scipy's ``distance_transform_edt(labels == i).max()``; a one-pixel object with anything
+    beside it has 1.0), ``inscribed_centre_z/_y/_x`` (2-D: y and x; int64) the first pixel in raster order that attains
+    it, ``distance_sq_mean = Σd² / area``.  Radius and mean are ``inf`` where ``D2 == DIST_INF``: the object fills a
+    map that has no edge to measure to.  Every float is one correctly rounded operation on exact integers."""
+    assert nd in (2, 3) and len(shape) == nd
+    area = [int(v) for v in np.asarray(area).reshape(-1)]
+    rows = [[int(v) for v in r] for r in np.asarray(rows).reshape(-1, 3)]
+    assert len(area) == len(rows)
+    inf = [r[0] >= DIST_INF for r in rows]
+    cols = {"inscribed_radius": np.array([math.inf if i else _sqrt_ratio(r[0], 1) for r, i in zip(rows, inf)], dtype=np.float64)}
+    index = np.array([r[1] for r in rows], dtype=np.int64)
+    centre = np.unravel_index(index, tuple(int(v) for v in shape)) if len(rows) else (np.zeros(0, dtype=np.int64),) * nd
+    for axis, c in zip(_AXES[3 - nd:], centre):
+        cols[f"inscribed_centre_{axis}"] = np.asarray(c, dtype=np.int64)
+    cols["distance_sq_mean"] = np.array([math.inf if i else r[2] / a for r, a, i in zip(rows, area, inf)], dtype=np.float64)
+    return cols
 
 
 def _resolve_device(labels, device):
@@ -420,7 +446,59 @@ def _hull_rows(lab, nd, Z, Y, X, nid, bbox_d, bbox, present):
     return hull.cpu().numpy()
 
 
-def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False):
+def _distance_map(lab, nd, Z, Y, X, edge):
+    """one clx_label_distance_sq call -> int32 device tensor, flat"""
+    import torch
+
+    device = lab.device
+    npix = lab.numel()
+    nbytes = int(_clx.load().clx_label_distance_workspace(npix))
+    if nbytes == 0:
+        raise ValueError("label_distance_sq: the map must have fewer than 2^32 pixels")
+    dist = torch.empty(npix, dtype=torch.int32, device=device)
+    workspace = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=device)
+    _clx.call("clx_label_distance_sq", _clx.ptr(lab), nd, Z, Y, X, int(bool(edge)), _clx.ptr(dist), _clx.ptr(workspace), nbytes,
+              _clx.stream_ptr(device))
+    return dist
+
+
+def label_distance_sq(labels, edge=False, device=None):
+    """For every pixel of ``labels`` (2-D or 3-D integers, array or device tensor; the same types and range as
+    ``region_table``) that belongs to an object the squared Euclidean distance, an exact integer, to the nearest pixel that
+    carries ANOTHER value, another object or the background alike; 0 on background.  Inside object ``i`` this is
+    ``scipy.ndimage.distance_transform_edt(labels == i) ** 2``, for every ``i`` at once: the input of a seeded watershed,
+    of skeletons, of an erosion that does not merge neighbours.  ``edge=False``: only pixels of the map count (scipy's
+    convention; a map that is one object everywhere has no candidate and gives ``DIST_INF``).  ``edge=True``: the map
+    counts as padded with one layer of background.  Returns the int32 DEVICE tensor in the shape of ``labels``.
+    Runs on a HIP device; there is no CPU path."""
+    import torch
+
+    lab, device, nd, spatial, _ = _labels_on_device(labels, device, "label_distance_sq")
+    if lab.numel() == 0:
+        return torch.empty(spatial, dtype=torch.int32, device=device)
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    return _distance_map(lab, nd, Z, Y, X, edge).reshape(spatial)
+
+
+def _inscribed_rows(lab, nd, Z, Y, X, nid, edge):
+    """clx_label_distance_sq, then clx_region_inscribed on its map -> int64 (nid, 3)"""
+    import torch
+
+    device = lab.device
+    dist = _distance_map(lab, nd, Z, Y, X, edge)
+    out = torch.empty((nid, 3), dtype=torch.int64, device=device)
+    bad = torch.empty(1, dtype=torch.int32, device=device)
+    _clx.call("clx_region_inscribed", _clx.ptr(lab), _clx.ptr(dist), lab.numel(), nid, _clx.ptr(out), _clx.ptr(bad),
+              _clx.stream_ptr(device))
+    flags = int(bad.item())
+    if flags & _BAD_LABEL:
+        raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+    if flags & _BAD_DISTANCE:
+        raise ValueError("region_table: the distance map changed under the measurement")
+    return out.cpu().numpy()
+
+
+def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -434,11 +512,15 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False, 
     ``hull=True`` appends, after those, in 2-D ``area_convex``, ``solidity``, ``feret_diameter_max``, ``feret_diameter_min``
     and ``hull_vertices``, in 3-D ``feret_diameter_max``: the hull of the pixels' corner points, which is not
     scikit-image's rasterised definition (``hull_columns``).
+    ``inscribed=True`` appends, after those, ``inscribed_radius`` (the radius of the largest circle / ball inside the
+    object: the maximum of ``label_distance_sq`` over its pixels, square-rooted), ``inscribed_centre_*`` (where it sits) and
+    ``distance_sq_mean`` (``inscribed_columns``); ``edge`` is ``label_distance_sq``'s: whether the image edge counts as
+    background.
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
-    return _region_table(labels, raw, device, boundary, topology, hull)[0]
+    return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge)[0]
 
 
-def _region_table(labels, raw, device, boundary, topology=False, hull=False):
+def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     import torch
 
@@ -498,6 +580,9 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False):
     if hull:
         ints = _hull_rows(lab, nd, Z, Y, X, nid, bbox_d, bbox_all, present)[present] if len(present) else np.zeros((0, 5), dtype=np.int64)
         cols.update(hull_columns(area[present], ints, nd))
+    if inscribed:
+        ints = _inscribed_rows(lab.reshape(-1), nd, Z, Y, X, nid, edge)[present] if len(present) else np.zeros((0, 3), dtype=np.int64)
+        cols.update(inscribed_columns(area[present], ints, spatial, nd))
     return cols, pairs
 
 
@@ -505,13 +590,14 @@ def _format(value):
     return "%.17g" % value if isinstance(value, (float, np.floating)) else "%d" % value
 
 
-def measure(inference_config, contacts=False, topology=False, hull=False) -> None:
+def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
     and writes ``contacts_bandwidth-<b>.csv`` beside it: ``sample,label_a,label_b,faces``, one line per pair of
-    objects that touch.  ``topology=True`` adds the topology columns, ``hull=True`` the convex hull columns.  Rank 0 works
-    alone under torch.distributed."""
+    objects that touch.  ``topology=True`` adds the topology columns, ``hull=True`` the convex hull columns,
+    ``inscribed=True`` the inscribed circle / ball columns (``edge=False``: distances to pixels of the map only).  Rank 0
+    works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -533,7 +619,7 @@ def measure(inference_config, contacts=False, topology=False, hull=False) -> Non
         header, lines, pair_lines = None, [], []
         for sample in range(meta.num_samples):
             labels = ds_seg[sample, bandwidth].astype(np.int32)
-            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull)
+            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

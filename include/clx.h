@@ -1019,6 +1019,43 @@ size_t clx_region_hull_workspace(long long rows);
 int clx_region_hull(const int32_t* labels, int nd, int Z, int Y, int X, int nid, const int32_t* bbox,
                     const long long* row_base, long long rows, void* workspace, size_t workspace_bytes,
                     long long* hull, int32_t* bad, clx_stream stream);
+/* Label-aware distance map: for every object pixel the squared distance to the nearest pixel that carries ANOTHER value,
+ * another object or the background alike -- what distance_transform_edt(labels == i) gives inside object i, for every i in
+ * one call.  (clx_edt_sq is binary: in a tissue whose objects touch it measures the distance to the background instead.)
+ * Label map [Z][Y][X] of int32; nd == 2 needs Z == 1.
+ *   labels    0 is background, every other value (a negative one too) an object.  Values are only compared with each
+ *             other, never followed as an index
+ *   d2(p)     for labels[p] != 0: the smallest |p - q|^2 over the pixels q with labels[q] != labels[p], between pixel centres
+ *             at unit spacing; 0 for labels[p] == 0
+ *   edge      0: only pixels of the map are candidates (scipy's convention).  1: the map counts as padded with one layer of
+ *             0 on both ends of every counted axis: y and x for nd == 2, z, y and x for nd == 3 (Z == 1 allowed: every object
+ *             pixel is then at distance 1 from the padding)
+ *   CLX_DIST_INF  the value of a pixel without any candidate: only with edge == 0, on a map that carries one non-zero value
+ *             everywhere.  Every other distance is below it
+ *   dist_sq   [Z][Y][X] int32, every element is written
+ *   workspace at least clx_label_distance_workspace(Z*Y*X) bytes (a host-only function; 0: npix outside [1, 2^32)), 4-byte
+ *             aligned: one more map, the other side of the passes' ping-pong
+ * Separable and exact: a pass along x, then min-plus passes along y (and z) in which a pixel of another value counts as
+ * distance 0 and a pixel of the same value with what the pass before left there.  Integers only: the same bits in every run.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent, edge not
+ * 0 or 1, Z*Y*X >= 2^32, (Z-1)^2 + (Y-1)^2 + (X-1)^2 >= 2^30 (a finite distance must stay below CLX_DIST_INF),
+ * workspace_bytes below clx_label_distance_workspace(Z*Y*X), a workspace that is not 4-byte aligned. */
+#define CLX_DIST_INF (1 << 30)
+size_t clx_label_distance_workspace(long long npix);
+int clx_label_distance_sq(const int32_t* labels, int nd, int Z, int Y, int X, int edge, int32_t* dist_sq,
+                          void* workspace, size_t workspace_bytes, clx_stream stream);
+/* Largest inscribed circle / ball: per id the maximum of a distance map over the id's pixels, where it is attained, and
+ * the map's sum (cellulus_amd.measure.inscribed_columns forms the columns).  labels and dist_sq: npix values each.
+ *   out [nid][3]  [0] D2   the largest dist_sq over the id's pixels: inscribed radius = sqrt(D2)
+ *                 [1]      the smallest linear index (z Y + y) X + x among the pixels that attain it
+ *                 [2]      the sum of dist_sq over the id's pixels (at most 2^32 2^30)
+ *   bad [1]       bit 0: a label outside [0, nid) -- never followed as an index, that pixel is skipped
+ *                 bit 1: a dist_sq outside [0, CLX_DIST_INF] under an id in [1, nid); that pixel is skipped
+ * The entry point initialises out and bad itself.  Row 0 and the rows of absent ids are zero.  Integer maxima and adds
+ * only: the same bits in every run.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nid outside [1, 2^24], npix outside [1, 2^32). */
+int clx_region_inscribed(const int32_t* labels, const int32_t* dist_sq, long long npix, int nid,
+                         unsigned long long* out, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
