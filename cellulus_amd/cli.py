@@ -1,5 +1,5 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
-(``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed]``)."""
+(``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]``)."""
 
 import click
 import tomli
@@ -35,8 +35,16 @@ def infer(config_file):
 @click.option("--topology", is_flag=True, help="add the Euler numbers and the Crofton perimeter (2-D) / surface area and sphericity (3-D)")
 @click.option("--hull", is_flag=True, help="add the convex hull columns: convex area, solidity, maximum / minimum Feret diameter")
 @click.option("--inscribed", is_flag=True, help="add the largest inscribed circle / ball: radius, centre, mean squared distance")
-def measure(config_file, contacts, topology, hull, inscribed):
+@click.option("--quantiles", default=None, metavar="Q,Q,...",
+              help="add per raw channel the intensity quantiles of a comma-separated list in [0, 1], e.g. 0.25,0.5,0.75")
+@click.option("--mad", is_flag=True, help="add per raw channel the median absolute deviation of the intensity (unscaled)")
+def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad):
     from .measure import measure as measure_experiment
 
+    if quantiles is not None:
+        try:
+            quantiles = tuple(float(q) for q in quantiles.split(","))
+        except ValueError:
+            raise click.BadParameter(f"not a comma-separated list of numbers: {quantiles!r}", param_hint="--quantiles")
     measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology, hull=hull,
-                       inscribed=inscribed)
+                       inscribed=inscribed, quantiles=quantiles, mad=mad)

@@ -11,16 +11,23 @@ perimeter in 2-D, surface area and sphericity in 3-D, from integer sums over the
 of the pixels' corner points, exact integers again (``clx_region_hull``; the definitions are the project's own, not
 scikit-image's rasterised ones: ``hull_columns``).  And its THICKNESS: the largest inscribed circle / ball and where it sits,
 from the label-aware distance map (``label_distance_sq``: for every object pixel the squared distance to the nearest pixel
-of another value; ``clx_label_distance_sq``, ``clx_region_inscribed``, ``inscribed_columns``).
+of another value; ``clx_label_distance_sq``, ``clx_region_inscribed``, ``inscribed_columns``).  And the ORDER STATISTICS of
+its intensity: quantiles (the median among them) and the median absolute deviation per raw channel, which a one-pass sum
+cannot give: the pixels' order-preserving keys are bucketed by object and selected by rank on the device
+(``csrc/region_order.hip``: ``clx_region_order_stats``).  A selected key is one of the values, so it is exact; the
+interpolation between two of them is rational arithmetic with one rounding (``quantile_ranks``, ``quantile_columns``).
 
     python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull] [--inscribed]
+                                                   [--quantiles 0.25,0.5,0.75] [--mad]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
 the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns,
-``--hull`` the convex hull columns, ``--inscribed`` the inscribed circle / ball columns.
+``--hull`` the convex hull columns, ``--inscribed`` the inscribed circle / ball columns, ``--quantiles`` one
+``intensity_q<q>_c<k>`` column per quantile and channel, ``--mad`` ``intensity_mad_c<k>``.
 """
 
 import math
+from fractions import Fraction
 
 import numpy as np
 
@@ -43,6 +50,8 @@ SURFACE_WEIGHTS = (0.09155578240952184, 0.07396125575215028, 0.07039127956463334
 _SQRT3 = math.sqrt(3.0)
 DIST_INF = 1 << 30                      # CLX_DIST_INF: a pixel of clx_label_distance_sq's map that has no candidate
 _BAD_LABEL, _BAD_DISTANCE = 1, 2        # bits of clx_region_inscribed's bad[0]
+MAX_QUANTILES = 16                      # two ranks each: clx_region_order_stats takes nq <= 32
+_ORDER_BAD_LABEL, _ORDER_BAD_VALUE, _ORDER_BAD_AREA, _ORDER_BAD_RANK = 1, 2, 4, 8   # bits of clx_region_order_stats' bad[0]
 
 
 def intensity_shift(max_abs, npix):
@@ -235,6 +244,56 @@ def inscribed_columns(area, rows, shape, nd):
         cols[f"inscribed_centre_{axis}"] = np.asarray(c, dtype=np.int64)
     cols["distance_sq_mean"] = np.array([math.inf if i else r[2] / a for r, a, i in zip(rows, area, inf)], dtype=np.float64)
     return cols
+
+
+def quantile_ranks(area, q):
+    """Where the ``q``-quantile of ``area`` sorted values lies, by NumPy's default ("linear") definition with the index
+    computed without rounding: ``h = Fraction(q) * (area - 1)`` with ``q`` taken as the float64 it is, ``lo = floor(h)``,
+    ``hi = ceil(h)``, ``t = h - lo``.  area (n) counts >= 1.  Returns ``(lo, hi, t)``: int64 arrays (n) of 0-based ranks and a
+    list of n ``Fraction`` in [0, 1)."""
+    q = float(q)
+    if not 0.0 <= q <= 1.0:                                  # a NaN fails both comparisons
+        raise ValueError(f"quantile_ranks: q must lie in [0, 1], got {q}")
+    fq = Fraction(q)
+    area = [int(a) for a in np.asarray(area).reshape(-1)]
+    if any(a < 1 for a in area):
+        raise ValueError("quantile_ranks: every area must be >= 1")
+    h = [fq * (a - 1) for a in area]
+    lo = [v.numerator // v.denominator for v in h]
+    hi = [-((-v.numerator) // v.denominator) for v in h]
+    return np.array(lo, dtype=np.int64), np.array(hi, dtype=np.int64), [v - f for v, f in zip(h, lo)]
+
+
+def quantile_columns(low, high, t):
+    """``float(Fraction(a) + (Fraction(b) - Fraction(a)) * t)`` per object as float64: the quantile from the order statistics
+    ``a = x_(lo)`` (low) and ``b = x_(hi)`` (high), finite numbers of any one dtype, and ``quantile_ranks``' ``t``.  The sum
+    is exact; the only rounding is the last step, as in ``_exact_div``.  Where ``t == 0`` the column is ``a`` itself."""
+    low, high = np.asarray(low).reshape(-1), np.asarray(high).reshape(-1)
+    assert len(low) == len(high) == len(t)
+    integral = low.dtype.kind in "ui"
+    out = np.empty(len(low), dtype=np.float64)
+    for i, (a, b, w) in enumerate(zip(low, high, t)):
+        if w == 0 or a == b:
+            out[i] = float(a)
+        else:
+            fa, fb = (Fraction(int(a)), Fraction(int(b))) if integral else (Fraction(float(a)), Fraction(float(b)))
+            out[i] = float(fa + (fb - fa) * w)
+    return out
+
+
+def _check_quantiles(quantiles, mad, raw, who="region_table"):
+    """-> tuple of float64 quantiles (empty for None) after the checks the table's new arguments share"""
+    qs = () if quantiles is None else tuple(float(q) + 0.0 for q in quantiles)       # -0.0 is 0.0, in the column's name too
+    if len(qs) > MAX_QUANTILES:
+        raise ValueError(f"{who}: at most {MAX_QUANTILES} quantiles, got {len(qs)}")
+    for q in qs:
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"{who}: a quantile must lie in [0, 1], got {q}")
+    if len(set(qs)) != len(qs):
+        raise ValueError(f"{who}: quantiles must be distinct, got {list(qs)}")
+    if (qs or mad) and raw is None:
+        raise ValueError(f"{who}: quantiles and mad need raw")
+    return qs
 
 
 def _resolve_device(labels, device):
@@ -498,7 +557,86 @@ def _inscribed_rows(lab, nd, Z, Y, X, nid, edge):
     return out.cpu().numpy()
 
 
-def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False):
+def _order_keys(lab, raw_d, raw_type, nid, area_d, seg_base_d, total, centre_d, rank_d, workspace, nbytes, k):
+    """one clx_region_order_stats call -> uint64 keys (nid, nq) on the host"""
+    import torch
+
+    device = lab.device
+    nq = rank_d.shape[1]
+    out = torch.empty((nid, nq), dtype=torch.int64, device=device)
+    bad = torch.empty(1, dtype=torch.int32, device=device)
+    _clx.call("clx_region_order_stats", _clx.ptr(lab), _clx.ptr(raw_d), raw_type, lab.numel(), nid, _clx.ptr(area_d),
+              _clx.ptr(seg_base_d), total, _clx.ptr(centre_d), _clx.ptr(rank_d), nq, _clx.ptr(out), _clx.ptr(workspace), nbytes,
+              _clx.ptr(bad), _clx.stream_ptr(device))
+    flags = int(bad.item())
+    if flags & _ORDER_BAD_VALUE:
+        raise ValueError(f"region_table: raw channel {k} has non-finite values inside objects")
+    if flags & (_ORDER_BAD_LABEL | _ORDER_BAD_AREA):
+        raise ValueError("region_table: label ids changed under the measurement")
+    if flags & _ORDER_BAD_RANK:
+        raise RuntimeError("region_table: internal error: a rank at or above its object's area reached clx_region_order_stats")
+    return out.cpu().numpy().view(np.uint64)
+
+
+def _order_columns(lab, channels, nid, present, area, area_d, quantiles, mad):
+    """the quantile and MAD columns of every channel: one clx_region_order_stats call per channel for all quantiles (two
+    ranks each, and the median's where ``mad`` needs them; a second call where that makes more than 32 ranks), and one with
+    the medians as ``centre`` for the MAD.
+    channels: [(raw_d, raw_type)]; area: the host copy of area_d with area[0] = 0"""
+    import torch
+
+    from .segment import _RAW_F64, _decode_keys
+
+    device = lab.device
+    names = [f"intensity_q{float(q)!r}" for q in quantiles]
+    cols = {}
+    if not len(present):
+        for k in range(len(channels)):
+            cols.update({f"{n}_c{k}": np.zeros(0) for n in names})
+            if mad:
+                cols[f"intensity_mad_c{k}"] = np.zeros(0)
+        return cols
+    needed = list(quantiles) + ([0.5] if mad and 0.5 not in quantiles else [])
+    nq = 2 * len(needed)
+    rank = np.zeros((nid, nq), dtype=np.int64)
+    weights = []
+    for j, q in enumerate(needed):
+        lo, hi, t = quantile_ranks(area[present], q)
+        rank[present, 2 * j], rank[present, 2 * j + 1] = lo, hi
+        weights.append(t)
+    seg_base = np.cumsum(area) - area                        # exclusive; absent ids (and row 0) take no pixels
+    total = int(area.sum())
+    nbytes = int(_clx.load().clx_region_order_workspace(total, nid))
+    if nbytes == 0:
+        raise ValueError("region_table: too many object pixels for clx_region_order_stats")
+    workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)         # reused by every call
+    seg_base_d = torch.from_numpy(seg_base.astype(np.int64)).to(device)
+    rank_d = torch.from_numpy(rank).to(device)
+    if mad:
+        m = needed.index(0.5)
+        mad_rank_d = rank_d[:, 2 * m:2 * m + 2].contiguous()
+    # 16 quantiles without 0.5 and the MAD's median are 17 pairs of ranks: more than one call takes
+    pairs = 2 * MAX_QUANTILES
+    rank_calls = [rank_d[:, c:c + pairs].contiguous() for c in range(0, nq, pairs)]
+    for k, (raw_d, raw_type) in enumerate(channels):
+        keys = np.concatenate([_order_keys(lab, raw_d, raw_type, nid, area_d, seg_base_d, total, None, r, workspace, nbytes, k)
+                               for r in rank_calls], axis=1)
+        vals = _decode_keys(keys[present], raw_type)
+        columns = [quantile_columns(vals[:, 2 * j], vals[:, 2 * j + 1], weights[j]) for j in range(len(needed))]
+        for n, c in zip(names, columns):
+            cols[f"{n}_c{k}"] = c
+        if mad:
+            centre = np.zeros(nid, dtype=np.float64)
+            centre[present] = columns[m]
+            keys = _order_keys(lab, raw_d, raw_type, nid, area_d, seg_base_d, total, torch.from_numpy(centre).to(device),
+                               mad_rank_d, workspace, nbytes, k)
+            dev = _decode_keys(keys[present], _RAW_F64)
+            cols[f"intensity_mad_c{k}"] = quantile_columns(dev[:, 0], dev[:, 1], weights[m])
+    return cols
+
+
+def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False,
+                 quantiles=None, mad=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -516,14 +654,22 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False, 
     object: the maximum of ``label_distance_sq`` over its pixels, square-rooted), ``inscribed_centre_*`` (where it sits) and
     ``distance_sq_mean`` (``inscribed_columns``); ``edge`` is ``label_distance_sq``'s: whether the image edge counts as
     background.
+    ``quantiles`` (at most 16 distinct floats in [0, 1], ``-0.0`` counting as ``0.0``; needs ``raw``) appends, after all of those, per channel k the float64
+    columns ``intensity_q{repr(float(q))}_c{k}`` in the order given (``intensity_q0.25_c0``, ``intensity_q0.5_c0`` ...): NumPy's
+    default ("linear") quantile of the object's raw values, with the index and the interpolation in exact rational
+    arithmetic and one rounding (``quantile_ranks``, ``quantile_columns``).  ``mad=True`` appends ``intensity_mad_c{k}`` behind
+    them: the median, by the same rule, of ``|v - median|`` in float64, unscaled (CellProfiler's MADIntensity).  The columns
+    of channel 0 come first, then those of channel 1.
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
-    return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge)[0]
+    return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge, quantiles, mad)[0]
 
 
-def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False):
+def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False, quantiles=None,
+                  mad=False):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     import torch
 
+    quantiles = _check_quantiles(quantiles, mad, raw)
     lab, device, nd, spatial, nid = _labels_on_device(labels, device, "region_table")
     Z, Y, X = (1,) * (3 - nd) + spatial
     if lab.numel() == 0 or nid == 1:
@@ -532,7 +678,7 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
                              np.zeros((0, 3), np.uint64), np.zeros((0, 6), np.uint64), nd)
         present = np.zeros(0, dtype=np.int64)
         bbox = np.zeros((0, 6), dtype=np.int32)
-        bbox_d = bbox_all = None
+        bbox_d = bbox_all = area_d = None
     else:
         area_d = torch.empty(nid, dtype=torch.int64, device=device)
         bbox_d = torch.empty((nid, 6), dtype=torch.int32, device=device)
@@ -551,6 +697,7 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         cols = shape_columns(present, area[present], bbox,
                              sum1_d.cpu().numpy().view(np.uint64)[present],
                              sum2_d.cpu().numpy().view(np.uint64)[present], nd)
+    channels = []                                            # kept on the device for the order statistics
     if raw is not None:
         if tuple(raw.shape) == spatial:
             raw = raw[None]
@@ -558,6 +705,8 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
             raise ValueError(f"region_table: raw has shape {tuple(raw.shape)}, labels {spatial}")
         for k in range(raw.shape[0]):
             raw_d, raw_type = _to_device_raw(raw[k], device)
+            if quantiles or mad:
+                channels.append((raw_d.reshape(-1), raw_type))
             if len(present):
                 cols.update(_channel_columns(lab.reshape(-1), raw_d.reshape(-1), raw_type, nid, present, area, k))
             else:
@@ -583,6 +732,8 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
     if inscribed:
         ints = _inscribed_rows(lab.reshape(-1), nd, Z, Y, X, nid, edge)[present] if len(present) else np.zeros((0, 3), dtype=np.int64)
         cols.update(inscribed_columns(area[present], ints, spatial, nd))
+    if quantiles or mad:
+        cols.update(_order_columns(lab.reshape(-1), channels, nid, present, area, area_d, quantiles, mad))
     return cols, pairs
 
 
@@ -590,14 +741,15 @@ def _format(value):
     return "%.17g" % value if isinstance(value, (float, np.floating)) else "%d" % value
 
 
-def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False) -> None:
+def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False, quantiles=None, mad=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
     and writes ``contacts_bandwidth-<b>.csv`` beside it: ``sample,label_a,label_b,faces``, one line per pair of
     objects that touch.  ``topology=True`` adds the topology columns, ``hull=True`` the convex hull columns,
-    ``inscribed=True`` the inscribed circle / ball columns (``edge=False``: distances to pixels of the map only).  Rank 0
-    works alone under torch.distributed."""
+    ``inscribed=True`` the inscribed circle / ball columns (``edge=False``: distances to pixels of the map only),
+    ``quantiles`` and ``mad`` the intensity quantile and median-absolute-deviation columns of every channel
+    (``region_table``'s arguments).  Rank 0 works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -619,7 +771,7 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
         header, lines, pair_lines = None, [], []
         for sample in range(meta.num_samples):
             labels = ds_seg[sample, bandwidth].astype(np.int32)
-            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed)
+            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed, False, quantiles, mad)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

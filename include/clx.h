@@ -1056,6 +1056,46 @@ int clx_label_distance_sq(const int32_t* labels, int nd, int Z, int Y, int X, in
  * Refused (CLX_ERR_ARG) before any launch: null pointers, nid outside [1, 2^24], npix outside [1, 2^32). */
 int clx_region_inscribed(const int32_t* labels, const int32_t* dist_sq, long long npix, int nid,
                          unsigned long long* out, int32_t* bad, clx_stream stream);
+/* Order statistics: per id the keys of given ranks among the keys of the id's pixels in one raw channel -- what np.quantile /
+ * np.median over an object's pixels sort for, for every object in one call (cellulus_amd.measure.quantile_columns forms the
+ * columns).  labels and raw: npix values each.  A key is the order-preserving 64-bit key of clx_inst_stats /
+ * clx_region_intensity; for CLX_RAW_F32 and CLX_RAW_I32 it lies in the low 32 bits.
+ *   area      [nid] clx_region_moments' output, left on the device
+ *   seg_base  [nid] exclusive prefix sum of area over the ids 1 .., an absent id taking 0 pixels; `total` is the sum.  The
+ *             keys of object i are gathered in positions [seg_base[i], seg_base[i] + area[i]) of a buffer in the workspace
+ *   centre    NULL: the key of a pixel is that of its value, in the raw type.  [nid] float64: the key is that of
+ *             fabs((double) v - centre[id]), one IEEE subtraction in float64, and decodes as float64 whatever raw_type is
+ *             (the median absolute deviation: centre = the medians of a first call)
+ *   rank      [nid][nq] 0-based ranks, 0 the smallest key
+ *   out       [nid][nq] the key of that rank among the id's keys.  An order statistic is one of the values: exact, the
+ *             same bits in every run although the order inside a segment is not.  ~0 in every column of an absent id
+ *   workspace at least clx_region_order_workspace(total, nid) bytes (a host-only function; 0: an argument out of range),
+ *             8-byte aligned: the key buffer, a cursor per id, and the histograms of the segments too long for one block
+ *   bad [1]   bit 0: a label outside [0, nid) -- never followed as an index, that pixel is skipped
+ *             bit 1: a NaN or +-Inf under an id in [1, nid).  Its key is still written, so the segment stays full; that
+ *                    object's row is unspecified, every other row is right.  Non-finite values on background are ignored
+ *             bit 2: the map disagrees with area / seg_base: a cursor went past area[id] (that key is dropped: nothing is
+ *                    ever written outside the segment) or ended below it (the row is unspecified), or a segment does not
+ *                    lie inside [0, total) (nothing of it is read or written, the row stays ~0)
+ *             bit 3: a rank >= area[id] for a present id; that element is ~0, nothing out of bounds is read
+ * The entry point initialises out, bad and the workspace itself; row 0 is unspecified.  The number of launches does not
+ * depend on the number of objects or ranks.
+ * Refused (CLX_ERR_ARG) before any launch, the outputs untouched: null pointers (centre may be null), an unknown raw_type,
+ * nid outside [1, 2^24], npix outside [1, 2^32), nq outside [1, 32], total outside [0, npix], workspace_bytes below
+ * clx_region_order_workspace(total, nid), a workspace that is not 8-byte aligned.  total == 0 launches the initialisation
+ * only. */
+size_t clx_region_order_workspace(long long total, int nid);
+int clx_region_order_stats(const int32_t* labels, const void* raw, int raw_type, long long npix, int nid,
+                           const unsigned long long* area, const unsigned long long* seg_base, long long total,
+                           const double* centre, const unsigned long long* rank, int nq, unsigned long long* out,
+                           void* workspace, size_t workspace_bytes, int32_t* bad, clx_stream stream);
+/* One phase of clx_region_order_stats alone, for timing (tools/bench_order_stats.py): the same arguments and refusals;
+ * phase 1 initialises the outputs and gathers the keys, phase 2 selects from a workspace that phase 1 has filled with the
+ * same arguments and leaves bad as it is.  Any other phase is refused. */
+int clx_region_order_phase(const int32_t* labels, const void* raw, int raw_type, long long npix, int nid,
+                           const unsigned long long* area, const unsigned long long* seg_base, long long total,
+                           const double* centre, const unsigned long long* rank, int nq, unsigned long long* out,
+                           void* workspace, size_t workspace_bytes, int32_t* bad, int phase, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
