@@ -212,6 +212,9 @@ PROTOTYPES = {
     "clx_region_order_workspace": (c_size_t, [_LL, _I]),
     "clx_region_order_stats": (_I, [_P, _P, _I, _LL, _I, _P, _P, _LL, _P, _P, _I, _P, _P, c_size_t, _P, _P]),
     "clx_region_order_phase": (_I, [_P, _P, _I, _LL, _I, _P, _P, _LL, _P, _P, _I, _P, _P, c_size_t, _P, _I, _P]),
+    "clx_region_cooccurrence_workspace": (c_size_t, [_LL, _I]),
+    "clx_region_cooccurrence": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, c_double, c_double, _I, _I, _P, _P, _P, _P,
+                                     c_size_t, _P]),
     "clx_lz4_decompress": (_LL, [_P, _LL, _P, _LL]),
     "clx_blosclz_decompress": (_LL, [_P, _LL, _P, _LL]),
     "clx_blosc_compress_bound": (_LL, [_LL]),

@@ -1,5 +1,6 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
-(``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]``)."""
+(``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]
+[--texture] [--texture-levels N] [--texture-distance D]``)."""
 
 import click
 import tomli
@@ -38,7 +39,13 @@ def infer(config_file):
 @click.option("--quantiles", default=None, metavar="Q,Q,...",
               help="add per raw channel the intensity quantiles of a comma-separated list in [0, 1], e.g. 0.25,0.5,0.75")
 @click.option("--mad", is_flag=True, help="add per raw channel the median absolute deviation of the intensity (unscaled)")
-def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad):
+@click.option("--texture", is_flag=True,
+              help="add per raw channel Haralick's texture features of the grey-level co-occurrence matrices; the grey levels "
+                   "divide the range of the values under each sample's objects")
+@click.option("--texture-levels", default=8, show_default=True, metavar="N", type=click.IntRange(2, 32), help="grey levels of --texture")
+@click.option("--texture-distance", default=1, show_default=True, metavar="D", type=click.IntRange(1, 64),
+              help="pixel distance of the pairs of --texture")
+def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, texture, texture_levels, texture_distance):
     from .measure import measure as measure_experiment
 
     if quantiles is not None:
@@ -47,4 +54,5 @@ def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad):
         except ValueError:
             raise click.BadParameter(f"not a comma-separated list of numbers: {quantiles!r}", param_hint="--quantiles")
     measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology, hull=hull,
-                       inscribed=inscribed, quantiles=quantiles, mad=mad)
+                       inscribed=inscribed, quantiles=quantiles, mad=mad, texture=texture, texture_levels=texture_levels,
+                       texture_distance=texture_distance)

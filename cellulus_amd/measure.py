@@ -16,14 +16,21 @@ its intensity: quantiles (the median among them) and the median absolute deviati
 cannot give: the pixels' order-preserving keys are bucketed by object and selected by rank on the device
 (``csrc/region_order.hip``: ``clx_region_order_stats``).  A selected key is one of the values, so it is exact; the
 interpolation between two of them is rational arithmetic with one rounding (``quantile_ranks``, ``quantile_columns``).
+And its TEXTURE, the one family of columns that changes when an object's pixels are shuffled: the grey-level co-occurrence
+matrices of every object per raw channel (``cooccurrence``; ``csrc/region_texture.hip``: ``clx_region_cooccurrence``), integer
+counts again, and Haralick's thirteen features of them (``texture_columns``).  The grey levels divide the range between the
+smallest and the largest value under the objects of ONE image: levels are relative to each image's objects, so texture
+columns of two images are comparable only where their ranges are (or where ``region_table`` is given a ``texture_range``).
 
     python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull] [--inscribed]
                                                    [--quantiles 0.25,0.5,0.75] [--mad]
+                                                   [--texture] [--texture-levels 8] [--texture-distance 1]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
 the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns,
 ``--hull`` the convex hull columns, ``--inscribed`` the inscribed circle / ball columns, ``--quantiles`` one
-``intensity_q<q>_c<k>`` column per quantile and channel, ``--mad`` ``intensity_mad_c<k>``.
+``intensity_q<q>_c<k>`` column per quantile and channel, ``--mad`` ``intensity_mad_c<k>``, ``--texture``
+``texture_pairs_c<k>`` and the thirteen ``texture_<feature>_c<k>`` per channel (the range is per sample and channel).
 """
 
 import math
@@ -52,6 +59,14 @@ DIST_INF = 1 << 30                      # CLX_DIST_INF: a pixel of clx_label_dis
 _BAD_LABEL, _BAD_DISTANCE = 1, 2        # bits of clx_region_inscribed's bad[0]
 MAX_QUANTILES = 16                      # two ranks each: clx_region_order_stats takes nq <= 32
 _ORDER_BAD_LABEL, _ORDER_BAD_VALUE, _ORDER_BAD_AREA, _ORDER_BAD_RANK = 1, 2, 4, 8   # bits of clx_region_order_stats' bad[0]
+MIN_LEVELS, MAX_LEVELS = 2, 32          # clx_region_cooccurrence: thirteen 32 x 32 int32 matrices are 52 KiB of LDS
+MAX_TEXTURE_DISTANCE = 64
+TEXTURE_TABLE_BYTES = 1 << 28           # the counts table of one clx_region_cooccurrence call stays below this
+_TEXTURE_BAD_LABEL, _TEXTURE_BAD_VALUE = 1, 2       # bits of clx_region_cooccurrence's bad[0]
+TEXTURE_FEATURES = ("asm", "contrast", "correlation", "variance", "idm", "sum_average", "sum_variance", "sum_entropy", "entropy",
+                    "difference_variance", "difference_entropy", "info_correlation_1", "info_correlation_2")
+_TEXTURE_INT64_MAX_T = 1 << 25          # texture_columns: numerators are below 2^12 T^2, so int64 holds them up to here
+_TEXTURE_SLICE_CELLS = 1 << 22          # matrix cells texture_columns holds as float64 at a time
 
 
 def intensity_shift(max_abs, npix):
@@ -296,6 +311,141 @@ def _check_quantiles(quantiles, mad, raw, who="region_table"):
     return qs
 
 
+def _check_texture(levels, distance, value_range, who="region_table"):
+    """-> (levels, distance, (lo, hi) or None) after the checks the texture arguments share"""
+    levels, distance = int(levels), int(distance)
+    if not MIN_LEVELS <= levels <= MAX_LEVELS:
+        raise ValueError(f"{who}: texture levels must lie in [{MIN_LEVELS}, {MAX_LEVELS}], got {levels}")
+    if not 1 <= distance <= MAX_TEXTURE_DISTANCE:
+        raise ValueError(f"{who}: texture distance must lie in [1, {MAX_TEXTURE_DISTANCE}], got {distance}")
+    if value_range is not None:
+        lo, hi = (float(v) for v in value_range)
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            raise ValueError(f"{who}: texture range must be finite with lo <= hi, got {(lo, hi)}")
+        value_range = (lo, hi)
+    return levels, distance, value_range
+
+
+def texture_directions(nd):
+    """The offsets of {-1, 0, 1}^nd that are lexicographically greater than zero, ascending: 4 in 2-D, ``(dy, dx)`` =
+    (0,1), (1,-1), (1,0), (1,1); 13 in 3-D.  The order of ``cooccurrence``'s direction axis."""
+    assert nd in (2, 3)
+    codes = range(14, 18) if nd == 2 else range(14, 27)      # (dz+1)*9 + (dy+1)*3 + (dx+1), from (0, 0, 1) on
+    return [tuple(v - 1 for v in (c // 9, c // 3 % 3, c % 3))[3 - nd:] for c in codes]
+
+
+def _neg_xlog2x(p, axis):
+    """``-Σ p log2 p`` along ``axis`` (a tuple or an int), a zero ``p`` contributing 0"""
+    positive = p > 0
+    return -(p * np.log2(np.where(positive, p, 1.0))).sum(axis=axis)
+
+
+def _texture_slice(counts):
+    """texture_columns for a slice of objects -> (pairs (n), features (13, n))"""
+    n, ndir, L, _ = counts.shape
+    C = counts.astype(np.int64)
+    N = C.sum(axis=(2, 3))                                   # (n, ndir) pairs per direction
+    present = N > 0
+    T64 = 2 * N
+    dt = np.int64 if int(T64.max(initial=0)) <= _TEXTURE_INT64_MAX_T else object
+    S = (C + C.transpose(0, 1, 3, 2)).astype(dt).reshape(n, ndir, L * L)
+    T = T64.astype(dt)
+    i = np.arange(L).astype(dt)
+    ii, jj = (v.reshape(-1) for v in np.meshgrid(i, i, indexing="ij"))
+    # exact integer numerators over T or T^2; with levels <= 32 the weights are at most 62^2 = 3844 < 2^12, so every one
+    # of them is below 2^12 T^2 in magnitude and fits int64 for T <= 2^25; above that they are Python ints
+    A = (S * S).sum(axis=2)                                  # Σ S^2                <= T^2
+    M1 = (S * ii).sum(axis=2)                                # Σ i S = T μ          <= 31 T
+    M2 = (S * (ii * ii)).sum(axis=2)                         # Σ i^2 S              <= 961 T
+    MIJ = (S * (ii * jj)).sum(axis=2)                        # Σ i j S              <= 961 T
+    DA = (S * abs(ii - jj)).sum(axis=2)                      # Σ k D_k              <= 31 T
+    DQ = (S * ((ii - jj) * (ii - jj))).sum(axis=2)           # Σ k^2 D_k            <= 961 T
+    SA = (S * (ii + jj)).sum(axis=2)                         # Σ k P_k              <= 62 T
+    SQ = (S * ((ii + jj) * (ii + jj))).sum(axis=2)           # Σ k^2 P_k            <= 3844 T
+    V = T * M2 - M1 * M1                                     # T^2 σ^2              <= 961 T^2
+    Tf = np.where(present, T64, 1).astype(np.float64)        # exact: T < 2^33
+
+    def ratio(num, den):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return num.astype(np.float64) / den.astype(np.float64)
+
+    TT = T * T
+    f = {}
+    f["asm"] = ratio(A, TT)
+    f["contrast"] = ratio(DQ, T)
+    f["correlation"] = np.where(V == 0, 1.0, ratio(T * MIJ - M1 * M1, V))
+    f["variance"] = ratio(V, TT)
+    f["sum_average"] = ratio(SA, T)
+    f["sum_variance"] = ratio(T * SQ - SA * SA, TT)
+    f["difference_variance"] = ratio(T * DQ - DA * DA, TT)
+    # the others in float64: S, its row sums and its diagonal sums are integers below 2^53, so every probability is ONE
+    # rounding of an exact ratio
+    Sf = (C + C.transpose(0, 1, 3, 2)).astype(np.float64)
+    flat = Sf.reshape(n * ndir, L * L)
+    ki, kj = np.meshgrid(np.arange(L), np.arange(L), indexing="ij")
+    diff_of = (abs(ki - kj).reshape(-1)[:, None] == np.arange(L)[None, :]).astype(np.float64)              # (L^2, L)
+    sum_of = ((ki + kj).reshape(-1)[:, None] == np.arange(2 * L - 1)[None, :]).astype(np.float64)          # (L^2, 2L-1)
+    p = Sf / Tf[:, :, None, None]
+    px = Sf.sum(axis=3) / Tf[:, :, None]
+    p_diff = (flat @ diff_of).reshape(n, ndir, L) / Tf[:, :, None]          # sums of integers in float64: exact
+    p_sum = (flat @ sum_of).reshape(n, ndir, 2 * L - 1) / Tf[:, :, None]
+    k = np.arange(L, dtype=np.float64)
+    f["idm"] = (p_diff / (1.0 + k * k)).sum(axis=2)
+    f["sum_entropy"] = _neg_xlog2x(p_sum, 2)
+    f["entropy"] = hxy = _neg_xlog2x(p, (2, 3))
+    f["difference_entropy"] = _neg_xlog2x(p_diff, 2)
+    hx = _neg_xlog2x(px, 2)
+    lx = np.log2(np.where(px > 0, px, 1.0))
+    lxy = lx[:, :, :, None] + lx[:, :, None, :]              # log2(px(i) px(j)) where both are positive
+    hxy1 = -(p * lxy).sum(axis=(2, 3))
+    hxy2 = -(px[:, :, :, None] * px[:, :, None, :] * lxy).sum(axis=(2, 3))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f["info_correlation_1"] = np.where(hx == 0.0, 0.0, (hxy - hxy1) / hx)
+    f["info_correlation_2"] = np.sqrt(np.maximum(0.0, 1.0 - np.exp2(-2.0 * (hxy2 - hxy))))
+    ndirs = present.sum(axis=1)
+    out = np.empty((len(TEXTURE_FEATURES), n), dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for row, name in enumerate(TEXTURE_FEATURES):
+            out[row] = np.where(present, f[name], 0.0).sum(axis=1) / ndirs          # 0 / 0: no direction has a pair
+    return N.sum(axis=1), out
+
+
+def texture_columns(counts, nd):
+    """Haralick's texture features from ``cooccurrence``'s integer counts.  counts (n, ndir, levels, levels), ndir 4 for
+    nd == 2 and 13 for nd == 3.  Returns a dict of ``pairs`` (int64: the ordered same-object pixel pairs, summed over the
+    directions) and thirteen float64 columns.  Per direction with ``N = Σ C > 0``: ``S = C + Cᵀ``, ``p = S / (2N)``, ``i, j``
+    0-based levels, ``px(i) = Σ_j p(i, j)``, ``μ = Σ i px(i)``, ``σ² = Σ (i − μ)² px(i)``, ``p₊(k) = Σ_{i+j=k} p``,
+    ``p₋(k) = Σ_{|i−j|=k} p``, entropies in bits, a zero probability contributing 0:
+    ``asm`` Σ p²; ``contrast`` Σ k² p₋(k); ``correlation`` (Σ i j p − μ²) / σ², 1.0 where σ² = 0; ``variance`` σ²; ``idm``
+    Σ p / (1 + (i−j)²); ``sum_average`` Σ k p₊(k); ``sum_variance`` Σ (k − sum_average)² p₊(k); ``sum_entropy`` −Σ p₊ log2 p₊;
+    ``entropy`` HXY = −Σ p log2 p; ``difference_variance`` the variance of p₋; ``difference_entropy`` −Σ p₋ log2 p₋;
+    ``info_correlation_1`` (HXY − HXY1) / HX with HXY1 = −Σ p log2(px(i) px(j)) and HX the entropy of px, 0.0 where HX = 0;
+    ``info_correlation_2`` sqrt(max(0, 1 − 2^(−2 (HXY2 − HXY)))) with HXY2 = −Σ px(i) px(j) log2(px(i) px(j)).
+    A column is the mean over the directions that have a pair, NaN where none has (a one-pixel object, a distance larger
+    than the object).  These are the project's own stated conventions (Haralick's 1973 features with 0-based levels, base-2
+    logarithms and his 14th left out); no fixture compares them with mahotas, scikit-image or CellProfiler, whose
+    conventions differ from each other in the level numbering, the logarithm and the normalisation.
+    The seven rational features (asm, contrast, correlation, variance, sum_average, sum_variance, difference_variance) are
+    exact integer numerators and denominators (vectorised int64 while ``2N <= 2**25``, which bounds every numerator by
+    ``2**12 (2N)**2 < 2**63``; Python ints above that), each converted to float64 and divided once; the others are float64
+    sums of probabilities that are each one rounding of an exact ratio.  Vectorised over the objects."""
+    assert nd in (2, 3)
+    counts = np.asarray(counts)
+    ndir = 4 if nd == 2 else 13
+    if counts.ndim != 4 or counts.shape[1] != ndir or counts.shape[2] != counts.shape[3]:
+        raise ValueError(f"texture_columns: counts must have shape (n, {ndir}, levels, levels), got {counts.shape}")
+    if counts.dtype.kind not in "ui":
+        raise TypeError(f"texture_columns: counts must be integers, got {counts.dtype}")
+    n = counts.shape[0]
+    step = max(1, _TEXTURE_SLICE_CELLS // (ndir * counts.shape[2] * counts.shape[3]))
+    parts = [_texture_slice(counts[a:a + step]) for a in range(0, n, step)]
+    cols = {"pairs": np.concatenate([p[0] for p in parts]).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)}
+    values = np.concatenate([p[1] for p in parts], axis=1) if parts else np.zeros((len(TEXTURE_FEATURES), 0))
+    for row, name in enumerate(TEXTURE_FEATURES):
+        cols[name] = np.ascontiguousarray(values[row])
+    return cols
+
+
 def _resolve_device(labels, device):
     import torch
 
@@ -403,6 +553,23 @@ def _labels_on_device(labels, device, who):
     _clx.require_device(lab, "labels")
     nid = int(lab.max().item()) + 1 if lab.numel() else 1
     return lab, device, nd, spatial, nid
+
+
+def _moments(lab, Z, Y, X, nid, who):
+    """one clx_region_moments call -> (area, bbox, sum1, sum2) left on the device"""
+    import torch
+
+    device = lab.device
+    area_d = torch.empty(nid, dtype=torch.int64, device=device)
+    bbox_d = torch.empty((nid, 6), dtype=torch.int32, device=device)
+    sum1_d = torch.empty((nid, 3), dtype=torch.int64, device=device)
+    sum2_d = torch.empty((nid, 6), dtype=torch.int64, device=device)
+    bad_d = torch.empty(1, dtype=torch.int32, device=device)
+    _clx.call("clx_region_moments", _clx.ptr(lab), Z, Y, X, nid, _clx.ptr(area_d), _clx.ptr(bbox_d),
+              _clx.ptr(sum1_d), _clx.ptr(sum2_d), _clx.ptr(bad_d), _clx.stream_ptr(device))
+    if int(bad_d.item()):
+        raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
+    return area_d, bbox_d, sum1_d, sum2_d
 
 
 def _pair_capacity(objects):
@@ -635,8 +802,98 @@ def _order_columns(lab, channels, nid, present, area, area_d, quantiles, mad):
     return cols
 
 
+def _cooccurrence_counts(lab, raw_d, raw_type, nd, Z, Y, X, nid, bbox_d, ids, area, lo, hi, levels, distance, k, who):
+    """clx_region_cooccurrence for the objects ``ids`` (host int64, any order), in chunks of them whose counts table stays
+    below TEXTURE_TABLE_BYTES -> counts int64 (len(ids), ndir, levels, levels).  area: the host areas by id, against which
+    the pixels every call saw are checked"""
+    import torch
+
+    device = lab.device
+    ndir = 4 if nd == 2 else 13
+    row_bytes = ndir * levels * levels * 4
+    step = max(1, TEXTURE_TABLE_BYTES // row_bytes)
+    out = np.empty((len(ids), ndir, levels, levels), dtype=np.int64)
+    workspace, have = None, 0
+    for a in range(0, len(ids), step):
+        chunk = np.asarray(ids[a:a + step], dtype=np.int64)
+        nrows = len(chunk)
+        nbytes = int(_clx.load().clx_region_cooccurrence_workspace(lab.numel(), nrows))
+        if nbytes == 0:
+            raise ValueError(f"{who}: the map must have fewer than 2^31 pixels for the texture columns")
+        if nbytes > have:
+            workspace, have = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device), nbytes
+        ids_d = torch.from_numpy(chunk.astype(np.int32)).to(device)
+        counts = torch.empty((nrows, ndir, levels, levels), dtype=torch.int32, device=device)
+        seen = torch.empty(nrows, dtype=torch.int64, device=device)
+        bad = torch.empty(1, dtype=torch.int32, device=device)
+        _clx.call("clx_region_cooccurrence", _clx.ptr(lab), _clx.ptr(raw_d), raw_type, nd, Z, Y, X, nid, _clx.ptr(bbox_d),
+                  _clx.ptr(ids_d), nrows, float(lo), float(hi), levels, distance, _clx.ptr(counts), _clx.ptr(seen), _clx.ptr(bad),
+                  _clx.ptr(workspace), nbytes, _clx.stream_ptr(device))
+        flags = int(bad.item())
+        if flags & _TEXTURE_BAD_VALUE:
+            raise ValueError(f"{who}: raw channel {k} has non-finite values inside objects")
+        if flags & _TEXTURE_BAD_LABEL or not np.array_equal(seen.cpu().numpy(), area[chunk]):
+            raise ValueError(f"{who}: label ids changed under the measurement")
+        out[a:a + nrows] = counts.cpu().numpy()
+    return out
+
+
+def _texture_columns_of(lab, channels, nd, Z, Y, X, nid, bbox_d, present, area, cols, levels, distance, value_range):
+    """the texture columns of every channel; channels: [(raw_d, raw_type)]; cols: the table so far, whose
+    intensity_min / _max columns give the range where none is given"""
+    out = {}
+    for k, (raw_d, raw_type) in enumerate(channels):
+        if len(present):
+            lo, hi = value_range or (float(cols[f"intensity_min_c{k}"].min()), float(cols[f"intensity_max_c{k}"].max()))
+            counts = _cooccurrence_counts(lab, raw_d, raw_type, nd, Z, Y, X, nid, bbox_d, present, area, lo, hi, levels, distance, k,
+                                          "region_table")
+        else:
+            counts = np.zeros((0, 4 if nd == 2 else 13, levels, levels), dtype=np.int64)
+        t = texture_columns(counts, nd)
+        out[f"texture_pairs_c{k}"] = t.pop("pairs")
+        out.update({f"texture_{name}_c{k}": column for name, column in t.items()})
+    return out
+
+
+def cooccurrence(labels, raw, levels=8, distance=1, value_range=None, device=None):
+    """The grey-level co-occurrence matrices of every object of ``labels`` (2-D or 3-D integers, array or device tensor; the
+    same types and range as ``region_table``) in ONE raw channel ``raw`` (the shape of ``labels``; float32, float64 or
+    integers that fit int32): ``(ids, counts)``, ``ids`` int64 (n) the objects present, ascending, ``counts`` int64
+    (n, ndir, levels, levels).  ``counts[r, k, a, b]`` is the number of pixels ``p`` of ``ids[r]`` at level ``a`` whose
+    partner ``p + distance * texture_directions(nd)[k]`` lies inside the map, carries the same id and is at level ``b``:
+    ordered pairs, not symmetrised, no wrap across the map's ends (``texture_columns`` forms ``C + Cᵀ``).
+    ``level(v) = min(levels - 1, max(0, floor((float64(v) - lo) / (hi - lo) * levels)))`` with ``2 <= levels <= 32``; ``hi ==
+    lo`` puts every pixel at level 0.  ``value_range=(lo, hi)``; ``None`` takes the smallest and the largest value under
+    the objects of this map, so the levels are relative to this image's objects.  ``1 <= distance <= 64``.
+    This is the door to the matrices for per-direction features; ``region_table(texture=True)`` has their means.
+    Runs on a HIP device; there is no CPU path."""
+    who = "cooccurrence"
+    levels, distance, value_range = _check_texture(levels, distance, value_range, who)
+    lab, device, nd, spatial, nid = _labels_on_device(labels, device, who)
+    ndir = 4 if nd == 2 else 13
+    if tuple(raw.shape) != spatial:
+        raise ValueError(f"{who}: raw has shape {tuple(raw.shape)}, labels {spatial}: one channel in the shape of labels")
+    empty = np.zeros(0, dtype=np.int64), np.zeros((0, ndir, levels, levels), dtype=np.int64)
+    if lab.numel() == 0 or nid == 1:
+        return empty
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    area_d, bbox_d, _, _ = _moments(lab, Z, Y, X, nid, who)
+    area = area_d.cpu().numpy()
+    area[0] = 0
+    present = np.flatnonzero(area > 0)
+    if not len(present):
+        return empty
+    raw_d, raw_type = _to_device_raw(raw, device)
+    raw_d = raw_d.reshape(-1)
+    if value_range is None:
+        c = _channel_columns(lab.reshape(-1), raw_d, raw_type, nid, present, area, 0)
+        value_range = float(c["intensity_min_c0"].min()), float(c["intensity_max_c0"].max())
+    counts = _cooccurrence_counts(lab, raw_d, raw_type, nd, Z, Y, X, nid, bbox_d, present, area, *value_range, levels, distance, 0, who)
+    return present.astype(np.int64), counts
+
+
 def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False,
-                 quantiles=None, mad=False):
+                 quantiles=None, mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -660,16 +917,27 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False, 
     arithmetic and one rounding (``quantile_ranks``, ``quantile_columns``).  ``mad=True`` appends ``intensity_mad_c{k}`` behind
     them: the median, by the same rule, of ``|v - median|`` in float64, unscaled (CellProfiler's MADIntensity).  The columns
     of channel 0 come first, then those of channel 1.
+    ``texture=True`` (needs ``raw``) appends, after all of those, per channel k ``texture_pairs_c{k}`` (int64: the ordered
+    same-object pixel pairs over all directions) and the thirteen float64 columns ``texture_<feature>_c{k}``, features in
+    ``TEXTURE_FEATURES``' order: Haralick's features of the object's grey-level co-occurrence matrices at ``texture_levels``
+    levels (2 .. 32) and pixel distance ``texture_distance`` (1 .. 64), the mean over the 4 (2-D) or 13 (3-D) directions that
+    have a pair, NaN where none has (``cooccurrence``, ``texture_columns``: the project's own stated conventions).
+    ``texture_range=(lo, hi)`` is the range the levels divide, for every channel; ``None`` takes per channel the smallest
+    and the largest value under the objects of this map: levels are then relative to this image's objects.  All of
+    channel 0's texture columns come before channel 1's.
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
-    return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge, quantiles, mad)[0]
+    return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge, quantiles, mad, texture, texture_levels,
+                         texture_distance, texture_range)[0]
 
 
 def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False, quantiles=None,
-                  mad=False):
+                  mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
-    import torch
-
     quantiles = _check_quantiles(quantiles, mad, raw)
+    if texture:
+        if raw is None:
+            raise ValueError("region_table: texture needs raw")
+        texture_levels, texture_distance, texture_range = _check_texture(texture_levels, texture_distance, texture_range)
     lab, device, nd, spatial, nid = _labels_on_device(labels, device, "region_table")
     Z, Y, X = (1,) * (3 - nd) + spatial
     if lab.numel() == 0 or nid == 1:
@@ -680,15 +948,7 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         bbox = np.zeros((0, 6), dtype=np.int32)
         bbox_d = bbox_all = area_d = None
     else:
-        area_d = torch.empty(nid, dtype=torch.int64, device=device)
-        bbox_d = torch.empty((nid, 6), dtype=torch.int32, device=device)
-        sum1_d = torch.empty((nid, 3), dtype=torch.int64, device=device)
-        sum2_d = torch.empty((nid, 6), dtype=torch.int64, device=device)
-        bad_d = torch.empty(1, dtype=torch.int32, device=device)
-        _clx.call("clx_region_moments", _clx.ptr(lab), Z, Y, X, nid, _clx.ptr(area_d), _clx.ptr(bbox_d),
-                  _clx.ptr(sum1_d), _clx.ptr(sum2_d), _clx.ptr(bad_d), _clx.stream_ptr(device))
-        if int(bad_d.item()):
-            raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
+        area_d, bbox_d, sum1_d, sum2_d = _moments(lab, Z, Y, X, nid, "region_table")
         area = area_d.cpu().numpy()
         area[0] = 0
         present = np.flatnonzero(area > 0)
@@ -705,7 +965,7 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
             raise ValueError(f"region_table: raw has shape {tuple(raw.shape)}, labels {spatial}")
         for k in range(raw.shape[0]):
             raw_d, raw_type = _to_device_raw(raw[k], device)
-            if quantiles or mad:
+            if quantiles or mad or texture:
                 channels.append((raw_d.reshape(-1), raw_type))
             if len(present):
                 cols.update(_channel_columns(lab.reshape(-1), raw_d.reshape(-1), raw_type, nid, present, area, k))
@@ -734,6 +994,9 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         cols.update(inscribed_columns(area[present], ints, spatial, nd))
     if quantiles or mad:
         cols.update(_order_columns(lab.reshape(-1), channels, nid, present, area, area_d, quantiles, mad))
+    if texture:
+        cols.update(_texture_columns_of(lab, channels, nd, Z, Y, X, nid, bbox_d, present, area, cols, texture_levels, texture_distance,
+                                        texture_range))
     return cols, pairs
 
 
@@ -741,7 +1004,8 @@ def _format(value):
     return "%.17g" % value if isinstance(value, (float, np.floating)) else "%d" % value
 
 
-def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False, quantiles=None, mad=False) -> None:
+def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False, quantiles=None, mad=False, texture=False,
+            texture_levels=8, texture_distance=1) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
@@ -749,7 +1013,9 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
     objects that touch.  ``topology=True`` adds the topology columns, ``hull=True`` the convex hull columns,
     ``inscribed=True`` the inscribed circle / ball columns (``edge=False``: distances to pixels of the map only),
     ``quantiles`` and ``mad`` the intensity quantile and median-absolute-deviation columns of every channel
-    (``region_table``'s arguments).  Rank 0 works alone under torch.distributed."""
+    (``region_table``'s arguments), ``texture=True`` the texture columns of every channel at ``texture_levels`` grey levels and
+    pixel distance ``texture_distance``; their range is per sample and channel, the smallest and the largest value under that
+    sample's objects, so the levels are relative to each image's objects.  Rank 0 works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -771,7 +1037,8 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
         header, lines, pair_lines = None, [], []
         for sample in range(meta.num_samples):
             labels = ds_seg[sample, bandwidth].astype(np.int32)
-            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed, False, quantiles, mad)
+            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed, False, quantiles, mad,
+                                         texture, texture_levels, texture_distance)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

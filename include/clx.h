@@ -1096,6 +1096,49 @@ int clx_region_order_phase(const int32_t* labels, const void* raw, int raw_type,
                            const unsigned long long* area, const unsigned long long* seg_base, long long total,
                            const double* centre, const unsigned long long* rank, int nq, unsigned long long* out,
                            void* workspace, size_t workspace_bytes, int32_t* bad, int phase, clx_stream stream);
+/* Texture: per object the grey-level co-occurrence matrices of one raw channel, from which the caller forms Haralick's
+ * features (cellulus_amd.measure.texture_columns).  Label map and raw [Z][Y][X]; nd == 2 needs Z == 1.
+ *   level(v)    min(levels - 1, max(0, (int) floor(((double) v - lo) / (hi - lo) * levels))): IEEE float64 in that order
+ *               of operations (the floor is clamped as a double, so no cast is out of range; a NaN quotient, which only
+ *               an infinite hi - lo gives, is level 0).  hi == lo: every pixel is at level 0.  Values outside [lo, hi]
+ *               clamp to level 0 / levels - 1
+ *   direction k the k-th offset of {-1, 0, 1}^nd that is lexicographically greater than zero, ascending: (dy, dx) = (0,1),
+ *               (1,-1), (1,0), (1,1) for nd == 2 (ndir = 4); 13 for nd == 3, (0,0,1) first, (1,1,1) last.  Each is multiplied
+ *               by `distance`
+ *   counts [nrows][ndir][levels][levels] int32.  counts[r][k][a][b]: the pixels p of id ids[r] at level a whose partner
+ *               q = p + distance * offset_k lies inside the map (no wrap across row, slice or map ends), carries the same id
+ *               and is at level b.  Ordered pairs, not symmetrised.  A partner in another object, on background or outside
+ *               the map gives no pair
+ *   ids [nrows] the objects this call takes, any order.  An id outside [1, nid), an absent id, and an id whose box fails the
+ *               check below get a row of zeros and seen 0.  Rows are independent of each other: an id that appears twice
+ *               gets two equal rows
+ *   bbox        [nid][6] clx_region_moments' output, left on the device.  A box is checked against the map before use
+ *               (0 <= min <= max < extent on every axis), so no index outside labels, raw or counts is ever formed whatever
+ *               bbox and ids hold; only pixels p inside the box of their id are visited (their partners q may lie outside it)
+ *   seen [nrows] the pixels of ids[r] that the call visited: equal to the id's area unless the box is stale
+ *   bad [1]     over the WHOLE map, whatever ids holds: bit 0 a label outside [0, nid) -- never followed as an index, it
+ *               matches no id; bit 1 a NaN or +-Inf under a label in [1, nid): that pixel takes part in no pair, neither
+ *               as p nor as q.  Non-finite values on background are ignored
+ *   workspace   at least clx_region_cooccurrence_workspace(Z*Y*X, nrows) bytes (a host-only function; 0: an argument out of
+ *               range), 8-byte aligned: the list of work items (below) and the levels staged as one byte per pixel
+ * Three kernels ahead of the main one: a pass over the map stages the levels (one float64 division per object pixel, not
+ * one per pair) and sets bad; one block turns the boxes of ids into the exclusive prefix sum of their slab counts -- a slab
+ * is a run of box rows (z, y) of about 8192 pixels, so an object that fills the map is cut into thousands of work items and a
+ * small one is a single item; the third zeroes seen and the rows that more than one item adds into.  The main kernel's
+ * blocks take the items in turn (the grid does not grow with nrows), find the row by bisection, keep the ndir x levels^2
+ * matrices in LDS (at most 13 x 32 x 32 x 4 = 52 KiB) and write them out once: plain stores for a single-item object, atomic
+ * adds for a shared one.  p owns its pair whichever slab q lies in.
+ * The entry point initialises counts, seen, bad and the workspace itself.  Integer adds only: the same bits in every run.
+ * Refused (CLX_ERR_ARG) before any launch, the outputs untouched: null pointers, an unknown raw_type, nd not 2 or 3, nd == 2
+ * with Z != 1, a non-positive extent, Z*Y*X >= 2^31 (counts are int32), nid outside [1, 2^24], nrows outside [0, nid),
+ * levels outside [2, 32], distance outside [1, 64], lo or hi not finite, hi < lo, a byte size of counts that does not fit
+ * size_t (with a 64-bit size_t the bounds above already exclude it), workspace_bytes below
+ * clx_region_cooccurrence_workspace(Z*Y*X, nrows), a workspace that is not 8-byte aligned. */
+size_t clx_region_cooccurrence_workspace(long long npix, int nrows);
+int clx_region_cooccurrence(const int32_t* labels, const void* raw, int raw_type, int nd, int Z, int Y, int X, int nid,
+                            const int32_t* bbox, const int32_t* ids, int nrows, double lo, double hi, int levels,
+                            int distance, int32_t* counts, long long* seen, int32_t* bad, void* workspace,
+                            size_t workspace_bytes, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
