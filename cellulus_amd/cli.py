@@ -1,6 +1,6 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
 (``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]
-[--texture] [--texture-levels N] [--texture-distance D]``)."""
+[--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]``)."""
 
 import click
 import tomli
@@ -45,7 +45,17 @@ def infer(config_file):
 @click.option("--texture-levels", default=8, show_default=True, metavar="N", type=click.IntRange(2, 32), help="grey levels of --texture")
 @click.option("--texture-distance", default=1, show_default=True, metavar="D", type=click.IntRange(1, 64),
               help="pixel distance of the pairs of --texture")
-def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, texture, texture_levels, texture_distance):
+@click.option("--radial", is_flag=True,
+              help="add the radial distribution: per ring of every object its area and, per raw channel, its mean, its share of "
+                   "the object's intensity and its mean over the object's mean; ring 0 is the rim")
+@click.option("--radial-rings", default=4, show_default=True, metavar="N", type=click.IntRange(1, 32), help="rings of --radial")
+@click.option("--radial-width", default=None, metavar="W", type=click.IntRange(1, 32768),
+              help="rings of --radial that are W pixels wide, counted from the boundary, the last one taking what lies deeper "
+                   "[default: rings relative to every object's inscribed radius]")
+@click.option("--radial-wedges", is_flag=True,
+              help="with --radial (2-D): add per ring the variation of the means of eight 45-degree wedges around the inscribed centre")
+def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, texture, texture_levels, texture_distance, radial,
+            radial_rings, radial_width, radial_wedges):
     from .measure import measure as measure_experiment
 
     if quantiles is not None:
@@ -55,4 +65,5 @@ def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, te
             raise click.BadParameter(f"not a comma-separated list of numbers: {quantiles!r}", param_hint="--quantiles")
     measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology, hull=hull,
                        inscribed=inscribed, quantiles=quantiles, mad=mad, texture=texture, texture_levels=texture_levels,
-                       texture_distance=texture_distance)
+                       texture_distance=texture_distance, radial=radial, radial_rings=radial_rings, radial_width=radial_width,
+                       radial_wedges=radial_wedges)

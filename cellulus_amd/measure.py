@@ -21,16 +21,25 @@ matrices of every object per raw channel (``cooccurrence``; ``csrc/region_textur
 counts again, and Haralick's thirteen features of them (``texture_columns``).  The grey levels divide the range between the
 smallest and the largest value under the objects of ONE image: levels are relative to each image's objects, so texture
 columns of two images are comparable only where their ranges are (or where ``region_table`` is given a ``texture_range``).
+And its RADIAL DISTRIBUTION, where inside the object the signal sits: every pixel is sorted into a ring by its distance to the
+object's boundary (and in 2-D into one of eight wedges around the inscribed centre) and counted and summed per ring
+(``radial_distribution``; ``csrc/region_radial.hip``: ``clx_region_radial``), integers again; ``radial_columns`` forms the
+mean, the fraction of the object's sum and the normalised mean of every ring and the variation around it (CellProfiler's
+FracAtD, MeanFrac, RadialCV).
 
     python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull] [--inscribed]
                                                    [--quantiles 0.25,0.5,0.75] [--mad]
                                                    [--texture] [--texture-levels 8] [--texture-distance 1]
+                                                   [--radial] [--radial-rings 4] [--radial-width W] [--radial-wedges]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
 the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns,
 ``--hull`` the convex hull columns, ``--inscribed`` the inscribed circle / ball columns, ``--quantiles`` one
 ``intensity_q<q>_c<k>`` column per quantile and channel, ``--mad`` ``intensity_mad_c<k>``, ``--texture``
-``texture_pairs_c<k>`` and the thirteen ``texture_<feature>_c<k>`` per channel (the range is per sample and channel).
+``texture_pairs_c<k>`` and the thirteen ``texture_<feature>_c<k>`` per channel (the range is per sample and channel),
+``--radial`` ``radial_area_r<j>`` and per channel ``radial_mean_r<j>_c<k>``, ``radial_frac_r<j>_c<k>`` and
+``radial_meanfrac_r<j>_c<k>`` for ``--radial-rings`` rings (relative to every object's inscribed radius, or ``--radial-width``
+pixels wide from the boundary), ``--radial-wedges`` ``radial_cv_r<j>_c<k>`` too (2-D).
 """
 
 import math
@@ -67,6 +76,9 @@ TEXTURE_FEATURES = ("asm", "contrast", "correlation", "variance", "idm", "sum_av
                     "difference_variance", "difference_entropy", "info_correlation_1", "info_correlation_2")
 _TEXTURE_INT64_MAX_T = 1 << 25          # texture_columns: numerators are below 2^12 T^2, so int64 holds them up to here
 _TEXTURE_SLICE_CELLS = 1 << 22          # matrix cells texture_columns holds as float64 at a time
+MAX_RINGS, MAX_RADIAL_WIDTH, RADIAL_WEDGES = 32, 32768, 8      # clx_region_radial: rings <= 32, width <= 2^15, 1 or 8 wedges
+RADIAL_TABLE_BYTES = 1 << 28            # the count and isum tables of one clx_region_radial call stay below this together
+_RADIAL_BAD_LABEL, _RADIAL_BAD_VALUE, _RADIAL_BAD_MAP, _RADIAL_BAD_ROW = 1, 2, 4, 8     # bits of clx_region_radial's bad[0]
 
 
 def intensity_shift(max_abs, npix):
@@ -446,6 +458,71 @@ def texture_columns(counts, nd):
     return cols
 
 
+def _check_radial(rings, width, wedges, nd, who="region_table"):
+    """-> (rings, width or 0, 1 or 8 wedges) after the checks the radial arguments share; ``nd`` None: not known yet"""
+    if isinstance(rings, bool) or rings != int(rings) or not 1 <= int(rings) <= MAX_RINGS:
+        raise ValueError(f"{who}: radial rings must be an integer in [1, {MAX_RINGS}], got {rings!r}")
+    if width is not None and (isinstance(width, bool) or width != int(width) or not 1 <= int(width) <= MAX_RADIAL_WIDTH):
+        raise ValueError(f"{who}: radial width must be None or an integer in [1, {MAX_RADIAL_WIDTH}], got {width!r}")
+    if wedges and nd == 3:
+        raise ValueError(f"{who}: radial wedges need a 2-D map")
+    return int(rings), 0 if width is None else int(width), RADIAL_WEDGES if wedges else 1
+
+
+def radial_columns(area, count, isum=None, shift=0, nd=2, k=None):
+    """The radial columns of ``region_table`` from ``radial_distribution``'s integers, in Python integers.  area (n) pixel
+    counts, count (n, rings, W) pixels per ring and wedge (W 1 or 8; 8 needs nd == 2), and either
+    ``isum=None``: the columns that belong to no channel, ``radial_area_r{j}`` (int64): the pixels of ring j, ring 0 the rim;
+    or ``isum`` (n, rings, W) the sums of channel ``k`` quantised with ``shift``: per ring j, with S_j and N_j the ring's sum and
+    count, S the object's sum and A its area,
+    ``radial_mean_r{j}_c{k}`` = S_j / N_j, one division, then ``ldexp(-shift)``; NaN for an empty ring;
+    ``radial_frac_r{j}_c{k}`` = S_j / S, the share of the object's intensity in the ring (CellProfiler's FracAtD); NaN where S = 0;
+    ``radial_meanfrac_r{j}_c{k}`` = (S_j A) / (S N_j), the ring's mean over the object's mean (MeanFrac), one rounding of the
+    exact rational; NaN for an empty ring or S = 0;
+    and with W == 8 ``radial_cv_r{j}_c{k}``: with m_o = S_jo / N_jo the means of the occupied wedges (one division each) and
+    w their number, in float64 ``mu = sum(m) / w``, ``sqrt(sum((m - mu)^2) / w) / mu``: the population standard deviation over
+    the mean of the wedge means (RadialCV, which no scaling of the channel changes); NaN with no occupied wedge or mu = 0.
+    An object thinner than ``rings * width`` leaves inner rings empty in absolute mode, and a small one may leave some empty in
+    relative mode (its squared distances take few values); the core ring of relative mode always holds the centre."""
+    assert nd in (2, 3)
+    count = np.asarray(count)
+    if count.ndim != 3 or count.shape[2] not in (1, RADIAL_WEDGES) or (count.shape[2] == RADIAL_WEDGES and nd != 2):
+        raise ValueError(f"radial_columns: count must have shape (n, rings, 1) or, in 2-D, (n, rings, {RADIAL_WEDGES}), got {count.shape}")
+    n, rings, W = count.shape
+    area = [int(v) for v in np.asarray(area).reshape(-1)]
+    assert len(area) == n
+    N = [[[int(v) for v in ring] for ring in obj] for obj in count.tolist()]
+    ring_n = [[sum(ring) for ring in obj] for obj in N]
+    for a, r in zip(area, ring_n):
+        assert sum(r) == a, "radial_columns: the rings of an object do not add up to its area"
+    if isum is None:
+        return {f"radial_area_r{j}": np.array([r[j] for r in ring_n], dtype=np.int64) for j in range(rings)}
+    isum = np.asarray(isum)
+    assert isum.shape == count.shape and isum.dtype.kind in "iu" and k is not None
+    S = [[[int(v) for v in ring] for ring in obj] for obj in isum.tolist()]
+    ring_s = [[sum(ring) for ring in obj] for obj in S]
+    total = [sum(r) for r in ring_s]
+    nan = math.nan
+    cols = {}
+    for j in range(rings):
+        mean = np.array([r[j] / c[j] if c[j] else nan for r, c in zip(ring_s, ring_n)], dtype=np.float64)
+        cols[f"radial_mean_r{j}_c{k}"] = np.ldexp(mean, -shift) if shift else mean
+        cols[f"radial_frac_r{j}_c{k}"] = np.array([r[j] / t if t else nan for r, t in zip(ring_s, total)], dtype=np.float64)
+        cols[f"radial_meanfrac_r{j}_c{k}"] = np.array([(r[j] * a) / (t * c[j]) if t and c[j] else nan
+                                                       for r, c, t, a in zip(ring_s, ring_n, total, area)], dtype=np.float64)
+        if W == RADIAL_WEDGES:
+            cv = np.full(n, nan, dtype=np.float64)
+            for i in range(n):
+                m = np.array([s / c for s, c in zip(S[i][j], N[i][j]) if c], dtype=np.float64)
+                if len(m):
+                    mu = m.sum() / len(m)
+                    if mu != 0.0:
+                        d = m - mu
+                        cv[i] = math.sqrt((d * d).sum() / len(m)) / mu
+            cols[f"radial_cv_r{j}_c{k}"] = cv
+    return cols
+
+
 def _resolve_device(labels, device):
     import torch
 
@@ -512,6 +589,7 @@ def _intensity(lab, raw_d, raw_type, nid, shift):
 
 
 def _channel_columns(lab, raw_d, raw_type, nid, present, area, k):
+    """-> (the intensity columns of channel k, the shift its sums were quantised with)"""
     from .segment import _RAW_I32, _decode_keys
     from .utils.otsu import minmax_on_device
 
@@ -538,7 +616,7 @@ def _channel_columns(lab, raw_d, raw_type, nid, present, area, k):
     mean = _exact_div(isum[present].astype(object), area[present].astype(object))
     if shift:
         mean = np.ldexp(mean, -shift)
-    return {f"intensity_mean_c{k}": mean, f"intensity_min_c{k}": vals[:, 0].copy(), f"intensity_max_c{k}": vals[:, 1].copy()}
+    return {f"intensity_mean_c{k}": mean, f"intensity_min_c{k}": vals[:, 0].copy(), f"intensity_max_c{k}": vals[:, 1].copy()}, shift
 
 
 def _labels_on_device(labels, device, who):
@@ -707,7 +785,8 @@ def label_distance_sq(labels, edge=False, device=None):
 
 
 def _inscribed_rows(lab, nd, Z, Y, X, nid, edge):
-    """clx_label_distance_sq, then clx_region_inscribed on its map -> int64 (nid, 3)"""
+    """clx_label_distance_sq, then clx_region_inscribed on its map -> (the map, flat int32; the rows, int64 (nid, 3)), both
+    left on the device"""
     import torch
 
     device = lab.device
@@ -721,7 +800,7 @@ def _inscribed_rows(lab, nd, Z, Y, X, nid, edge):
         raise ValueError(f"region_table: label ids must lie in [0, {MAX_IDS})")
     if flags & _BAD_DISTANCE:
         raise ValueError("region_table: the distance map changed under the measurement")
-    return out.cpu().numpy()
+    return dist, out
 
 
 def _order_keys(lab, raw_d, raw_type, nid, area_d, seg_base_d, total, centre_d, rank_d, workspace, nbytes, k):
@@ -886,14 +965,109 @@ def cooccurrence(labels, raw, levels=8, distance=1, value_range=None, device=Non
     raw_d, raw_type = _to_device_raw(raw, device)
     raw_d = raw_d.reshape(-1)
     if value_range is None:
-        c = _channel_columns(lab.reshape(-1), raw_d, raw_type, nid, present, area, 0)
+        c, _ = _channel_columns(lab.reshape(-1), raw_d, raw_type, nid, present, area, 0)
         value_range = float(c["intensity_min_c0"].min()), float(c["intensity_max_c0"].max())
     counts = _cooccurrence_counts(lab, raw_d, raw_type, nd, Z, Y, X, nid, bbox_d, present, area, *value_range, levels, distance, 0, who)
     return present.astype(np.int64), counts
 
 
+def _radial_tables(lab, dist, inscribed_d, channels, nd, Z, Y, X, nid, ids, area, rings, width, wedges, who):
+    """clx_region_radial for the objects ``ids`` (host int64, any order) on the distance map ``dist`` and
+    clx_region_inscribed's rows ``inscribed_d`` (both on the device), in chunks of objects whose two tables stay below
+    RADIAL_TABLE_BYTES together; one call per chunk and channel, one without a channel where there is none
+    -> (count int64 (len(ids), rings, wedges), [isum int64 of the same shape per channel]).
+    channels: [(raw_d, raw_type, shift)]; width 0: relative rings; area: the host areas by id, against which the pixels
+    every call counted are checked"""
+    import torch
+
+    device = lab.device
+    n = len(ids)
+    step = max(1, RADIAL_TABLE_BYTES // (rings * wedges * 16))
+    count = np.empty((n, rings, wedges), dtype=np.int64)
+    isums = [np.empty((n, rings, wedges), dtype=np.int64) for _ in channels]
+    for a in range(0, n, step):
+        chunk = np.asarray(ids[a:a + step], dtype=np.int64)
+        nrows = len(chunk)
+        row = np.full(nid, -1, dtype=np.int32)
+        row[chunk] = np.arange(nrows, dtype=np.int32)
+        row_d = torch.from_numpy(row).to(device)
+        count_d = torch.empty((nrows, rings, wedges), dtype=torch.int64, device=device)
+        isum_d = torch.empty((nrows, rings, wedges), dtype=torch.int64, device=device) if channels else None
+        bad = torch.empty(1, dtype=torch.int32, device=device)
+        for k, (raw_d, raw_type, shift) in enumerate(channels or [(None, 0, 0)]):
+            _clx.call("clx_region_radial", _clx.ptr(lab), _clx.ptr(dist), _clx.ptr(raw_d), raw_type, nd, Z, Y, X, nid,
+                      _clx.ptr(inscribed_d), _clx.ptr(row_d), nrows, rings, width, wedges, int(shift), _clx.ptr(count_d),
+                      _clx.ptr(isum_d), _clx.ptr(bad), _clx.stream_ptr(device))
+            flags = int(bad.item())
+            if flags & _RADIAL_BAD_VALUE:
+                raise ValueError(f"{who}: raw channel {k} has non-finite values inside objects")
+            if flags & _RADIAL_BAD_MAP:
+                raise ValueError(f"{who}: the distance map changed under the measurement")
+            got = count_d.cpu().numpy()
+            if flags & (_RADIAL_BAD_LABEL | _RADIAL_BAD_ROW) or not np.array_equal(got.sum(axis=(1, 2)), area[chunk]):
+                raise ValueError(f"{who}: label ids changed under the measurement")
+            count[a:a + nrows] = got
+            if raw_d is not None:
+                isums[k][a:a + nrows] = isum_d.cpu().numpy()
+    return count, isums
+
+
+def _raw_channels(raw, spatial, who):
+    """``raw`` as (C, *spatial): one channel in the shape of the labels gets its leading axis"""
+    if tuple(raw.shape) == spatial:
+        raw = raw[None]
+    if tuple(raw.shape[1:]) != spatial:
+        raise ValueError(f"{who}: raw has shape {tuple(raw.shape)}, labels {spatial}")
+    return raw
+
+
+def radial_distribution(labels, raw=None, rings=4, width=None, wedges=False, edge=False, device=None):
+    """The radial distribution of every object of ``labels`` (2-D or 3-D integers, array or device tensor; the same types and
+    range as ``region_table``) as integer tables: ``(ids, count, isum, shift)``.  ``ids`` int64 (n): the objects present,
+    ascending.  ``count`` int64 (n, rings, W): the pixels of ``ids[r]`` in ring j and wedge o.  ``isum``: per channel of ``raw``
+    (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32, float64 or integers that fit int32) an int64 (n, rings, W) with the
+    sums of ``q = rint(v * 2**shift[k])`` over those pixels; ``shift``: per channel the scale ``region_table`` uses for its
+    ``intensity_mean`` (``intensity_shift``; 0 for integers).  Both lists are empty without ``raw``.
+    Ring: with ``d2`` the pixel's ``label_distance_sq`` (``edge`` is that function's) and ``D2`` its object's largest,
+    ``width=None`` takes the smallest j with ``d2 * rings**2 <= (j + 1)**2 * D2``: rings of equal width in units of the
+    object's inscribed radius, ring 0 the rim and ring ``rings - 1`` the core; ``width`` in 1 .. 32768 the smallest j with
+    ``d2 <= ((j + 1) * width)**2``, at most ``rings - 1``: bands of ``width`` pixels from the boundary.  ``1 <= rings <= 32``.
+    Wedge: ``wedges=False``: W = 1.  ``wedges=True`` (2-D): W = 8 sectors of 45 degrees around the object's inscribed centre
+    (the first pixel in raster order that attains D2), wedge o holding ``o * 45 <= atan2(dy, dx) < (o + 1) * 45`` degrees.
+    Every number is an exact integer and the same in every run; the tables do not depend on RADIAL_TABLE_BYTES, which only
+    bounds what one call holds.  ``radial_columns`` forms ``region_table``'s columns of them.
+    Runs on a HIP device; there is no CPU path."""
+    who = "radial_distribution"
+    rings, width, W = _check_radial(rings, width, wedges, getattr(labels, "ndim", None), who)
+    lab, device, nd, spatial, nid = _labels_on_device(labels, device, who)
+    if raw is not None:
+        raw = _raw_channels(raw, spatial, who)
+    nch = 0 if raw is None else raw.shape[0]
+    empty = (np.zeros(0, dtype=np.int64), np.zeros((0, rings, W), dtype=np.int64),
+             [np.zeros((0, rings, W), dtype=np.int64) for _ in range(nch)], [0] * nch)
+    if lab.numel() == 0 or nid == 1:
+        return empty
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    area_d, _, _, _ = _moments(lab, Z, Y, X, nid, who)
+    area = area_d.cpu().numpy()
+    area[0] = 0
+    present = np.flatnonzero(area > 0)
+    if not len(present):
+        return empty
+    flat = lab.reshape(-1)
+    channels = []
+    for k in range(nch):
+        raw_d, raw_type = _to_device_raw(raw[k], device)
+        _, shift = _channel_columns(flat, raw_d.reshape(-1), raw_type, nid, present, area, k)
+        channels.append((raw_d.reshape(-1), raw_type, shift))
+    dist, inscribed_d = _inscribed_rows(flat, nd, Z, Y, X, nid, edge)
+    count, isums = _radial_tables(flat, dist, inscribed_d, channels, nd, Z, Y, X, nid, present, area, rings, width, W, who)
+    return present.astype(np.int64), count, isums, [c[2] for c in channels]
+
+
 def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False,
-                 quantiles=None, mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None):
+                 quantiles=None, mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None,
+                 radial=False, radial_rings=4, radial_width=None, radial_wedges=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -925,15 +1099,27 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False, 
     ``texture_range=(lo, hi)`` is the range the levels divide, for every channel; ``None`` takes per channel the smallest
     and the largest value under the objects of this map: levels are then relative to this image's objects.  All of
     channel 0's texture columns come before channel 1's.
+    ``radial=True`` appends, after all of those, ``radial_area_r{j}`` (int64) for the ``radial_rings`` rings j (1 .. 32; ring 0
+    is the rim, the last ring the core) and, with ``raw``, per channel k and ring j the float64 columns
+    ``radial_mean_r{j}_c{k}``, ``radial_frac_r{j}_c{k}`` and ``radial_meanfrac_r{j}_c{k}``, with ``radial_wedges=True`` (2-D only)
+    ``radial_cv_r{j}_c{k}`` behind them: the ring's mean, its share of the object's sum, its mean over the object's mean and
+    the variation of the means of its eight 45-degree wedges (``radial_distribution``, ``radial_columns``: the quantities of
+    CellProfiler's MeasureObjectIntensityDistribution on the project's own ring and wedge definitions, exact integers).  ``radial_width=None``: the rings divide every object's
+    inscribed radius; an integer in 1 .. 32768: bands of that many pixels from the boundary, the last ring taking what lies
+    deeper.  ``edge`` is the one of ``inscribed``; the distance map is formed once for both.  All of channel 0's radial
+    columns come before channel 1's.
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
     return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge, quantiles, mad, texture, texture_levels,
-                         texture_distance, texture_range)[0]
+                         texture_distance, texture_range, radial, radial_rings, radial_width, radial_wedges)[0]
 
 
 def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False, quantiles=None,
-                  mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None):
+                  mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None, radial=False,
+                  radial_rings=4, radial_width=None, radial_wedges=False):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     quantiles = _check_quantiles(quantiles, mad, raw)
+    if radial:
+        radial_rings, radial_width, radial_W = _check_radial(radial_rings, radial_width, radial_wedges, getattr(labels, "ndim", None))
     if texture:
         if raw is None:
             raise ValueError("region_table: texture needs raw")
@@ -957,18 +1143,17 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         cols = shape_columns(present, area[present], bbox,
                              sum1_d.cpu().numpy().view(np.uint64)[present],
                              sum2_d.cpu().numpy().view(np.uint64)[present], nd)
-    channels = []                                            # kept on the device for the order statistics
+    channels, shifts = [], []                                # kept on the device for the order statistics, texture, radial
     if raw is not None:
-        if tuple(raw.shape) == spatial:
-            raw = raw[None]
-        if tuple(raw.shape[1:]) != spatial:
-            raise ValueError(f"region_table: raw has shape {tuple(raw.shape)}, labels {spatial}")
+        raw = _raw_channels(raw, spatial, "region_table")
         for k in range(raw.shape[0]):
             raw_d, raw_type = _to_device_raw(raw[k], device)
-            if quantiles or mad or texture:
+            if quantiles or mad or texture or radial:
                 channels.append((raw_d.reshape(-1), raw_type))
+            shifts.append(0)
             if len(present):
-                cols.update(_channel_columns(lab.reshape(-1), raw_d.reshape(-1), raw_type, nid, present, area, k))
+                intensity, shifts[k] = _channel_columns(lab.reshape(-1), raw_d.reshape(-1), raw_type, nid, present, area, k)
+                cols.update(intensity)
             else:
                 dt = raw_d.cpu().numpy().dtype
                 cols.update({f"intensity_mean_c{k}": np.zeros(0), f"intensity_min_c{k}": np.zeros(0, dt),
@@ -989,14 +1174,26 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
     if hull:
         ints = _hull_rows(lab, nd, Z, Y, X, nid, bbox_d, bbox_all, present)[present] if len(present) else np.zeros((0, 5), dtype=np.int64)
         cols.update(hull_columns(area[present], ints, nd))
+    if (inscribed or radial) and len(present):               # one distance map and one reduction for both
+        dist_d, inscribed_d = _inscribed_rows(lab.reshape(-1), nd, Z, Y, X, nid, edge)
     if inscribed:
-        ints = _inscribed_rows(lab.reshape(-1), nd, Z, Y, X, nid, edge)[present] if len(present) else np.zeros((0, 3), dtype=np.int64)
+        ints = inscribed_d.cpu().numpy()[present] if len(present) else np.zeros((0, 3), dtype=np.int64)
         cols.update(inscribed_columns(area[present], ints, spatial, nd))
     if quantiles or mad:
         cols.update(_order_columns(lab.reshape(-1), channels, nid, present, area, area_d, quantiles, mad))
     if texture:
         cols.update(_texture_columns_of(lab, channels, nd, Z, Y, X, nid, bbox_d, present, area, cols, texture_levels, texture_distance,
                                         texture_range))
+    if radial:
+        if len(present):
+            count, isums = _radial_tables(lab.reshape(-1), dist_d, inscribed_d, [c + (s,) for c, s in zip(channels, shifts)], nd, Z, Y,
+                                          X, nid, present, area, radial_rings, radial_width, radial_W, "region_table")
+        else:
+            count = np.zeros((0, radial_rings, radial_W), dtype=np.int64)
+            isums = [count] * len(channels)
+        cols.update(radial_columns(area[present], count, nd=nd))
+        for k, isum in enumerate(isums):
+            cols.update(radial_columns(area[present], count, isum, shifts[k], nd, k))
     return cols, pairs
 
 
@@ -1005,7 +1202,7 @@ def _format(value):
 
 
 def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False, quantiles=None, mad=False, texture=False,
-            texture_levels=8, texture_distance=1) -> None:
+            texture_levels=8, texture_distance=1, radial=False, radial_rings=4, radial_width=None, radial_wedges=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
@@ -1015,7 +1212,9 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
     ``quantiles`` and ``mad`` the intensity quantile and median-absolute-deviation columns of every channel
     (``region_table``'s arguments), ``texture=True`` the texture columns of every channel at ``texture_levels`` grey levels and
     pixel distance ``texture_distance``; their range is per sample and channel, the smallest and the largest value under that
-    sample's objects, so the levels are relative to each image's objects.  Rank 0 works alone under torch.distributed."""
+    sample's objects, so the levels are relative to each image's objects; ``radial=True`` the radial distribution columns at
+    ``radial_rings`` rings, relative or ``radial_width`` pixels wide, with ``radial_wedges`` the wedge variation too
+    (``region_table``'s arguments, ``edge=False``).  Rank 0 works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -1038,7 +1237,8 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
         for sample in range(meta.num_samples):
             labels = ds_seg[sample, bandwidth].astype(np.int32)
             table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed, False, quantiles, mad,
-                                         texture, texture_levels, texture_distance)
+                                         texture, texture_levels, texture_distance, None, radial, radial_rings, radial_width,
+                                         radial_wedges)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

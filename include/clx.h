@@ -1139,6 +1139,48 @@ int clx_region_cooccurrence(const int32_t* labels, const void* raw, int raw_type
                             const int32_t* bbox, const int32_t* ids, int nrows, double lo, double hi, int levels,
                             int distance, int32_t* counts, long long* seen, int32_t* bad, void* workspace,
                             size_t workspace_bytes, clx_stream stream);
+/* Radial distribution: per object, ring and angular wedge the pixel count and the sum of one raw channel -- where inside the
+ * object the signal sits: rim against core (a membrane against a cytoplasm, a translocation), one side against the other (a
+ * polarity); cellulus_amd.measure.radial_columns forms the columns (CellProfiler's FracAtD, MeanFrac, RadialCV).  Label map,
+ * dist_sq and raw [Z][Y][X]; nd == 2 needs Z == 1.  The definitions are the project's own:
+ *   d2(p)     dist_sq[p], clx_label_distance_sq's map of the same labels
+ *   D2(i)     inscribed[i][0];  c(i): the pixel with linear index inscribed[i][1]  (clx_region_inscribed's out [nid][3], left on
+ *             the device)
+ *   ring      relative mode (width == 0): for a pixel of object i the smallest k in [0, rings) with
+ *             d2 * rings^2 <= (k + 1)^2 * D2: ceil(rings * sqrt(d2 / D2)) - 1 decided in 64-bit integers (the products reach
+ *             2^40), with no square root and no floating point; a pixel exactly on a ring's edge lies in the ring the inequality
+ *             gives.  Ring 0 is the RIM, next to the boundary; ring rings - 1 the CORE, which holds c(i).
+ *             absolute mode (width in [1, 32768]): the smallest k with d2 <= ((k + 1) * width)^2, clamped to rings - 1: bands
+ *             of `width` pixels counted from the boundary, the last ring taking everything deeper
+ *   wedge     wedges == 1: always 0.  wedges == 8 (nd == 2 only): (dy, dx) = p - c(i), theta = atan2(dy, dx) in [0, 2 pi); wedge
+ *             o holds o * 45 deg <= theta < (o + 1) * 45 deg, decided by integer comparisons of dy, dx, |dy|, |dx|: a boundary
+ *             ray belongs to the wedge that starts at it, (0, 0) is in wedge 0
+ *   row [nid] the output row of an id; < 0: the id is not taken.  Ids that share a row are summed into it
+ *   count [nrows][rings][wedges]  the pixels of the id with row[id] == r in ring k and wedge o
+ *   isum  [nrows][rings][wedges]  Σ q over those pixels, q exactly clx_region_intensity's: CLX_RAW_I32: q = v, `shift` ignored;
+ *             CLX_RAW_F32 / _F64: q = (long long) rint(ldexp((double) v, shift)) under the same per-pixel bound
+ *             2^62 >> bit_length(Z*Y*X).  For every taken id the sum of isum over its rings and wedges is clx_region_intensity's
+ *             isum for the same shift, bit for bit, and the sum of count is its area
+ *   raw       may be NULL, and isum then too: counts only, raw_type and shift are ignored (an isum given all the same is zeroed)
+ *   bad [1]   bit 0: a label outside [0, nid) -- never followed as an index, counts as background
+ *             bit 1: a NaN, +-Inf or |q| above the bound under a taken id; that pixel is skipped in count and isum alike.
+ *                    Such values on background and under ids that are not taken are ignored
+ *             bit 2: the maps disagree: under a taken id a d2 outside [1, D2] (relative) or [1, CLX_DIST_INF] (absolute), or, with
+ *                    wedges == 8, a centre index outside [0, Z*Y*X); the pixel is skipped.  No index outside count / isum is
+ *                    ever formed, whatever inscribed, row and dist_sq hold (a D2 above 2^41 is cut there: every d2 is in ring 0
+ *                    either way)
+ *             bit 3: a row[id] >= nrows under a pixel of the map; the id is treated as not taken
+ * The entry point initialises count, isum and bad itself.  Integer adds only: the same bits in every run.  Two launches,
+ * whatever the number of objects: the initialisation, and one pass in which a block combines runs of pixels of one cell in a
+ * table of 1024 cells in LDS that it adds to the outputs once.
+ * Refused (CLX_ERR_ARG) before any launch, the outputs untouched: null pointers other than the raw / isum pair, an unknown
+ * raw_type with a non-null raw, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent, Z*Y*X >= 2^32, nid outside
+ * [1, 2^24], nrows outside [0, nid), rings outside [1, 32], width outside [0, 32768], wedges not 1 or 8, wedges == 8 with
+ * nd == 3, nrows * rings * wedges >= 2^31. */
+int clx_region_radial(const int32_t* labels, const int32_t* dist_sq, const void* raw, int raw_type, int nd, int Z, int Y,
+                      int X, int nid, const unsigned long long* inscribed, const int32_t* row, int nrows, int rings,
+                      int width, int wedges, int shift, unsigned long long* count, long long* isum, int32_t* bad,
+                      clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
