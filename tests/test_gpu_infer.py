@@ -642,6 +642,102 @@ def test_nucleus_refine_on_device_matches_oracle_random(device):
             np.testing.assert_array_equal(out.cpu().numpy(), ref, err_msg=f"{shape} {dtype}")
 
 
+def _refine_on_device(seg, raw, device):
+    from cellulus_amd.segment import _raw_to_device, nucleus_refine_on_device
+
+    raw_d, rt = _raw_to_device(raw, device)
+    return nucleus_refine_on_device(torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int32)).to(device), raw_d, rt).cpu().numpy()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64, np.int32, np.uint8])
+def test_nucleus_refine_on_device_flood_fixtures_match_oracle(dtype, device):
+    """the whole wrapper (stats -> histograms -> host Otsu -> refine) on the label maps of tests/nucleus_ref.py: a ten-row
+    serpentine corridor (sealed: one hole; opened at its far end: none), a 300 x 300 box, nested instances in both id
+    orders with overlapping boxes"""
+    import nucleus_ref as NR
+
+    def raw_of(bright):
+        return np.where(bright, 7, 2).astype(dtype) if np.issubdtype(dtype, np.integer) else np.where(bright, 0.75, -0.25).astype(dtype)
+
+    for transpose in (False, True):
+        seg, bright, corridor = NR.serpentine(True, transpose)
+        ref = IO.nucleus_refine(seg, raw_of(bright))
+        assert (ref == 1).all()
+        np.testing.assert_array_equal(_refine_on_device(seg, raw_of(bright), device), ref)
+        seg, bright, corridor = NR.serpentine(False, transpose)
+        ref = IO.nucleus_refine(seg, raw_of(bright))
+        assert not ref[corridor].any() and (ref[bright] == 1).all()
+        np.testing.assert_array_equal(_refine_on_device(seg, raw_of(bright), device), ref)
+    seg, bright = NR.wide_box()
+    ref = IO.nucleus_refine(seg, raw_of(bright))
+    assert ref[275, 270] == 1 and ref[150, 295] == 0
+    np.testing.assert_array_equal(_refine_on_device(seg, raw_of(bright), device), ref)
+    for ring, blob in ((2, 5), (5, 2)):
+        seg, bright = NR.nested(ring, blob)
+        ref = IO.nucleus_refine(seg, raw_of(bright))
+        assert ref[6, 6] == ring and ref[9, 9] == max(ring, blob)
+        np.testing.assert_array_equal(_refine_on_device(seg, raw_of(bright), device), ref)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_nucleus_refine_on_device_negative_and_signed_zero_values(dtype, device):
+    """float raw values below zero (the negative branch of the order-preserving keys decides every histogram range), and
+    an instance whose only two values are -0.0 and +0.0: equal as numbers, so it is constant and nothing is written"""
+    rng = np.random.default_rng(23)
+    for shape in ((50, 70), (6, 30, 33)):
+        blocks = rng.integers(0, 7, size=tuple(-(-s // 10) for s in shape))
+        blocks.flat[:4] = [1, 2, 4, 3]
+        seg = np.kron(blocks, np.ones((10,) * len(shape), dtype=np.int64))[tuple(slice(0, s) for s in shape)].astype(np.int32)
+        raw = -3.0 - rng.random(shape)                          # all negative
+        raw[rng.random(shape) < 0.3] -= 2.0
+        raw[seg == 4] += 3.5                                    # mixed sign in one instance
+        raw = raw.astype(dtype)
+        n2 = int((seg == 2).sum())
+        raw[seg == 2] = np.where(rng.random(n2) < 0.5, dtype(-0.0), dtype(0.0))
+        assert n2 > 0 and np.signbit(raw[seg == 2]).any() and not np.signbit(raw[seg == 2]).all()
+        ref = IO.nucleus_refine(seg, raw)
+        assert not (ref == 2).any() and (ref == 4).any() and (ref == 1).any()
+        np.testing.assert_array_equal(_refine_on_device(seg, raw, device), ref, err_msg=f"{shape}")
+
+
+def test_nucleus_refine_on_device_above_the_grid_cap(device):
+    """1030 x 1031 = 1 061 930 pixels: more than the 1 048 576 threads the statistics and histogram launches are capped at;
+    instance 6 lies entirely in the pixels of the second trip, instance 5 has its brightest and darkest pixels there"""
+    rng = np.random.default_rng(31)
+    shape = (1030, 1031)
+    seg = np.zeros(shape, dtype=np.int32)
+    seg[100:300, 200:500], seg[400:700, 50:350], seg[350:380, 600:1000] = 1, 2, 3
+    seg[500:600, 100:200] = 4                                    # nested in 2
+    seg[900:1030, 400:700] = 5
+    seg[1020:1030, 800:1031] = 6
+    raw = rng.random(shape).astype(np.float32)
+    raw[rng.random(shape) < 0.3] *= 0.2
+    raw[1025, 500], raw[1026, 500] = 40.0, -40.0                 # instance 5's range is set on the second trip
+    assert 1020 * 1031 >= 4096 * 256
+    ref = IO.nucleus_refine(seg, raw)
+    assert len(np.unique(ref)) == 7
+    np.testing.assert_array_equal(_refine_on_device(seg, raw, device), ref)
+
+
+def test_seeds_on_device_reruns_when_a_plateau_exceeds_the_first_capacity(device):
+    """a bit-identical plateau of 2304 pixels at the minimum of the smoothed map: every one of them is a peak, the first
+    buffer (1127 slots for 100 x 100) overflows, and the list comes from the rerun"""
+    from scipy.ndimage import gaussian_filter
+
+    from cellulus_amd.detect import peak_local_max, seeds_on_device
+
+    emb = np.zeros((2, 100, 100))
+    emb[0] = 5.0
+    emb[0, 18:82, 18:82] = 1.0
+    mag = np.linalg.norm(emb, axis=0)
+    smooth = gaussian_filter(mag, sigma=2)
+    assert int((smooth == smooth.min()).sum()) == 2304
+    ref = np.flip(peak_local_max(-smooth), 1)
+    assert len(ref) == 2304 > max(1024, mag.size // 9 + 16) == 1127
+    got = seeds_on_device(torch.from_numpy(emb).to(device), 2)
+    np.testing.assert_array_equal(got, ref)
+
+
 def test_fused_infer_writes_the_same_datasets_as_the_staged_path(device, tmp_path, monkeypatch):
     """infer() hands embeddings and label maps from stage to stage in device memory (default) or
     goes through the zarr datasets stage by stage (CLX_FUSED_INFER=0, the reference's order): every
