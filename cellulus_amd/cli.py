@@ -1,6 +1,7 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
 (``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]
-[--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]``)."""
+[--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]
+[--std] [--colocalization] [--coloc-threshold F]``)."""
 
 import click
 import tomli
@@ -54,8 +55,14 @@ def infer(config_file):
                    "[default: rings relative to every object's inscribed radius]")
 @click.option("--radial-wedges", is_flag=True,
               help="with --radial (2-D): add per ring the variation of the means of eight 45-degree wedges around the inscribed centre")
+@click.option("--std", is_flag=True, help="add per raw channel the (population) standard deviation of the intensity")
+@click.option("--colocalization", is_flag=True,
+              help="add per pair of raw channels Pearson's correlation, the slope, the overlap coefficient, K1 / K2 and the Manders "
+                   "coefficients inside every object (needs at least 2 channels)")
+@click.option("--coloc-threshold", default=0.15, show_default=True, metavar="F", type=click.FloatRange(0.0, 1.0),
+              help="fraction of an object's maximum from which a pixel counts for the overlap, K1 / K2 and Manders columns")
 def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, texture, texture_levels, texture_distance, radial,
-            radial_rings, radial_width, radial_wedges):
+            radial_rings, radial_width, radial_wedges, std, colocalization, coloc_threshold):
     from .measure import measure as measure_experiment
 
     if quantiles is not None:
@@ -66,4 +73,4 @@ def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, te
     measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology, hull=hull,
                        inscribed=inscribed, quantiles=quantiles, mad=mad, texture=texture, texture_levels=texture_levels,
                        texture_distance=texture_distance, radial=radial, radial_rings=radial_rings, radial_width=radial_width,
-                       radial_wedges=radial_wedges)
+                       radial_wedges=radial_wedges, std=std, colocalization=colocalization, coloc_threshold=coloc_threshold)

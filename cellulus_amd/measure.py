@@ -26,11 +26,17 @@ object's boundary (and in 2-D into one of eight wedges around the inscribed cent
 (``radial_distribution``; ``csrc/region_radial.hip``: ``clx_region_radial``), integers again; ``radial_columns`` forms the
 mean, the fraction of the object's sum and the normalised mean of every ring and the variation around it (CellProfiler's
 FracAtD, MeanFrac, RadialCV).
+And its SECOND MOMENTS, the columns that compare a channel with itself or with another: the intensity standard deviation and,
+for every pair of raw channels, Pearson's correlation, the regression slope, the overlap coefficient, K1 / K2 and the Manders
+coefficients inside every object (CellProfiler's MeasureColocalization).  They need Σ q_a q_b, which 64 bits do not hold for
+values quantised to 62 - L bits: the products are summed exactly in 128 bits on the device (``channel_products``;
+``csrc/region_coloc.hip``: ``clx_region_products``) and ``products_columns`` rounds once.
 
     python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull] [--inscribed]
                                                    [--quantiles 0.25,0.5,0.75] [--mad]
                                                    [--texture] [--texture-levels 8] [--texture-distance 1]
                                                    [--radial] [--radial-rings 4] [--radial-width W] [--radial-wedges]
+                                                   [--std] [--colocalization] [--coloc-threshold 0.15]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
 the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns,
@@ -39,7 +45,9 @@ the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--top
 ``texture_pairs_c<k>`` and the thirteen ``texture_<feature>_c<k>`` per channel (the range is per sample and channel),
 ``--radial`` ``radial_area_r<j>`` and per channel ``radial_mean_r<j>_c<k>``, ``radial_frac_r<j>_c<k>`` and
 ``radial_meanfrac_r<j>_c<k>`` for ``--radial-rings`` rings (relative to every object's inscribed radius, or ``--radial-width``
-pixels wide from the boundary), ``--radial-wedges`` ``radial_cv_r<j>_c<k>`` too (2-D).
+pixels wide from the boundary), ``--radial-wedges`` ``radial_cv_r<j>_c<k>`` too (2-D), ``--std`` ``intensity_std_c<k>`` per
+channel and ``--colocalization`` the seven ``coloc_<quantity>_c<j>_c<k>`` per pair of channels, with ``--coloc-threshold`` the
+fraction of an object's maximum from which a pixel counts for overlap, K1 / K2 and Manders.
 """
 
 import math
@@ -520,6 +528,120 @@ def radial_columns(area, count, isum=None, shift=0, nd=2, k=None):
                         d = m - mu
                         cv[i] = math.sqrt((d * d).sum() / len(m)) / mu
             cols[f"radial_cv_r{j}_c{k}"] = cv
+    return cols
+
+
+def _check_products(std, colocalization, coloc_threshold, labels, raw, who="region_table"):
+    """-> coloc_threshold as a float after the checks the std / colocalization arguments share (no device is touched)"""
+    f = float(coloc_threshold)
+    if not 0.0 <= f <= 1.0:                                  # a NaN fails both comparisons
+        raise ValueError(f"{who}: coloc_threshold must lie in [0, 1], got {coloc_threshold!r}")
+    if (std or colocalization) and raw is None:
+        raise ValueError(f"{who}: std and colocalization need raw")
+    if colocalization and (raw.ndim == getattr(labels, "ndim", raw.ndim - 1) or raw.shape[0] < 2):
+        raise ValueError(f"{who}: colocalization needs at least 2 raw channels")
+    return f + 0.0
+
+
+def quantised(values, shift):
+    """``q`` of ``clx_region_intensity`` for values of one raw dtype as Python ints: integers are themselves, floats
+    ``rint(ldexp(float64(v), shift))``"""
+    values = np.asarray(values).reshape(-1)
+    if values.dtype.kind in "ui":
+        return [int(v) for v in values]
+    return [int(v) for v in np.rint(np.ldexp(values.astype(np.float64), int(shift)))]
+
+
+def coloc_thresholds(qmax, f):
+    """``ceil(f * qmax)`` per object in exact rational arithmetic, ``f`` in [0, 1] taken as the float64 it is and ``qmax`` the
+    object's quantised maximum (Python ints): a pixel is "above" where ``q >= threshold``, so a pixel exactly at ``f * qmax`` is.
+    ``f = 0`` puts every non-negative pixel above, ``f = 1`` the pixels at the maximum only.  The project's own convention, in
+    the manner of CellProfiler's "15 % of the object's maximum".  Returns an int64 array."""
+    f = float(f)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError(f"coloc_thresholds: f must lie in [0, 1], got {f}")
+    fq = Fraction(f)
+    out = np.empty(len(qmax), dtype=np.int64)
+    for i, q in enumerate(qmax):
+        t = fq * int(q)
+        out[i] = -((-t.numerator) // t.denominator)
+    return out
+
+
+PRODUCT_WORDS = 20                      # clx_region_products: words per id
+_PRODUCT_SUMS = ("n", "sum_a", "sum_b", "n_both", "sum_a_above", "sum_b_above", "sum_a_both", "sum_b_both")
+_PRODUCT_SQUARES = ("sum_aa", "sum_bb", "sum_ab", "sum_aa_both", "sum_bb_both", "sum_ab_both")
+_PRODUCTS_BAD_LABEL, _PRODUCTS_BAD_VALUE = 1, 2     # bits of clx_region_products' bad[0]
+
+
+def product_table(words):
+    """``clx_region_products``' rows (n, 20) of uint64 words as a dict: int64 arrays ``n, sum_a, sum_b, n_both, sum_a_above,
+    sum_b_above, sum_a_both, sum_b_both`` and object arrays of Python ints ``sum_aa, sum_bb, sum_ab, sum_aa_both, sum_bb_both,
+    sum_ab_both`` (a (lo, hi) pair is one signed 128-bit integer, two's complement)"""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, PRODUCT_WORDS)
+    table = {name: np.ascontiguousarray(words[:, i]).view(np.int64) for i, name in enumerate(_PRODUCT_SUMS)}
+    for i, name in enumerate(_PRODUCT_SQUARES):
+        lo, hi = words[:, 8 + 2 * i].tolist(), words[:, 9 + 2 * i].tolist()
+        table[name] = np.empty(len(lo), dtype=object)
+        table[name][:] = [l + (h << 64) - ((h >> 63) << 128) for l, h in zip(lo, hi)]
+    return table
+
+
+def _signed_root(num, den):
+    """``sign(num) * sqrt(num**2 / den)`` of Python ints, NaN where ``den == 0``: one correctly rounded operation"""
+    if den == 0:
+        return math.nan
+    r = _sqrt_ratio(num * num, den)
+    return -r if num < 0 else r
+
+
+def _ratio(num, den):
+    return num / den if den else math.nan
+
+
+def products_columns(table, shift_a=0, shift_b=0, j=0, k=1, std=False, colocalization=True):
+    """The columns of ``region_table`` that need second moments, from ``product_table``'s exact integers (channel ``j`` is a,
+    quantised with ``shift_a``; channel ``k`` is b with ``shift_b``), in Python integers.  With ``A = Σa``, ``B = Σb``,
+    ``Va = n Σaa − A²``, ``Vb = n Σbb − B²``, ``C = n Σab − A B`` and the subscript T for the sums over the pixels above both
+    thresholds:
+    ``std=True``: ``intensity_std_c{j}`` = sqrt(Va / n²) · 2^−shift_a, the POPULATION standard deviation (regionprops'
+    ``intensity_std``, CellProfiler's StdIntensity), and, where ``k != j``, ``intensity_std_c{k}`` likewise;
+    ``colocalization=True``:
+    ``coloc_pearson_c{j}_c{k}`` = sign(C) sqrt(C² / (Va Vb)); ``coloc_slope_c{j}_c{k}`` = C / Va · 2^(shift_a − shift_b), the
+    regression of channel k on channel j; ``coloc_overlap_c{j}_c{k}`` = sign(Σab_T) sqrt(Σab_T² / (Σaa_T Σbb_T));
+    ``coloc_k1_c{j}_c{k}`` = Σab_T / Σaa_T · 2^(shift_a − shift_b); ``coloc_k2_c{j}_c{k}`` = Σab_T / Σbb_T · 2^(shift_b − shift_a);
+    ``coloc_manders1_c{j}_c{k}`` = Σa_T / Σa|above a; ``coloc_manders2_c{j}_c{k}`` = Σb_T / Σb|above b.
+    Every column is ONE correctly rounded operation on exact integers and an exact scaling by a power of two; NaN where its
+    denominator is 0 (a constant channel has no correlation, an object with no pixel above both thresholds no overlap)."""
+    n = [int(v) for v in table["n"]]
+    A, B = [int(v) for v in table["sum_a"]], [int(v) for v in table["sum_b"]]
+    aa, bb, ab = (list(table[name]) for name in ("sum_aa", "sum_bb", "sum_ab"))
+    Va = [m * s - a * a for m, s, a in zip(n, aa, A)]
+    Vb = [m * s - b * b for m, s, b in zip(n, bb, B)]
+    assert all(v >= 0 for v in Va) and all(v >= 0 for v in Vb), "products_columns: a negative variance: the sums do not belong together"
+    scale = int(shift_a) - int(shift_b)
+    cols = {}
+
+    def column(values, exponent=0):
+        c = np.array(values, dtype=np.float64).reshape(len(n))
+        with np.errstate(over="ignore", under="ignore"):       # shifts at both clamps can leave float64's range
+            return np.ldexp(c, exponent) if exponent else c
+
+    if std:
+        cols[f"intensity_std_c{j}"] = column([_sqrt_ratio(v, m * m) if m else math.nan for v, m in zip(Va, n)], -int(shift_a))
+        if k != j:
+            cols[f"intensity_std_c{k}"] = column([_sqrt_ratio(v, m * m) if m else math.nan for v, m in zip(Vb, n)], -int(shift_b))
+    if colocalization:
+        C = [m * s - a * b for m, s, a, b in zip(n, ab, A, B)]
+        aT, bT, abT = (list(table[name]) for name in ("sum_aa_both", "sum_bb_both", "sum_ab_both"))
+        pair = f"c{j}_c{k}"
+        cols[f"coloc_pearson_{pair}"] = column([_signed_root(c, va * vb) for c, va, vb in zip(C, Va, Vb)])
+        cols[f"coloc_slope_{pair}"] = column([_ratio(c, va) for c, va in zip(C, Va)], scale)
+        cols[f"coloc_overlap_{pair}"] = column([_signed_root(s, x * y) for s, x, y in zip(abT, aT, bT)])
+        cols[f"coloc_k1_{pair}"] = column([_ratio(s, x) for s, x in zip(abT, aT)], scale)
+        cols[f"coloc_k2_{pair}"] = column([_ratio(s, y) for s, y in zip(abT, bT)], -scale)
+        cols[f"coloc_manders1_{pair}"] = column([_ratio(int(s), int(d)) for s, d in zip(table["sum_a_both"], table["sum_a_above"])])
+        cols[f"coloc_manders2_{pair}"] = column([_ratio(int(s), int(d)) for s, d in zip(table["sum_b_both"], table["sum_b_above"])])
     return cols
 
 
@@ -1065,9 +1187,111 @@ def radial_distribution(labels, raw=None, rings=4, width=None, wedges=False, edg
     return present.astype(np.int64), count, isums, [c[2] for c in channels]
 
 
+def _products_rows(lab, chan_a, chan_b, nid, shift_a, shift_b, thr_a, thr_b, area, present, who, j, k):
+    """one clx_region_products call -> product_table of the present ids.  chan_*: (raw_d, raw_type); thr_*: int64 host arrays
+    (nid) or None, both or neither; area: the host areas by id, against which the pixels the call counted are checked"""
+    import torch
+
+    device = lab.device
+    if chan_a[1] != chan_b[1]:
+        raise ValueError(f"{who}: raw channels {j} and {k} differ in type")
+    out = torch.empty((nid, PRODUCT_WORDS), dtype=torch.int64, device=device)
+    bad = torch.empty(1, dtype=torch.int32, device=device)
+    thr_a_d = None if thr_a is None else torch.from_numpy(np.ascontiguousarray(thr_a, dtype=np.int64)).to(device)
+    thr_b_d = None if thr_b is None else torch.from_numpy(np.ascontiguousarray(thr_b, dtype=np.int64)).to(device)
+    _clx.call("clx_region_products", _clx.ptr(lab), _clx.ptr(chan_a[0]), _clx.ptr(chan_b[0]), chan_a[1], lab.numel(), nid,
+              int(shift_a), int(shift_b), _clx.ptr(thr_a_d), _clx.ptr(thr_b_d), _clx.ptr(out), _clx.ptr(bad), _clx.stream_ptr(device))
+    flags = int(bad.item())
+    if flags & _PRODUCTS_BAD_VALUE:
+        raise ValueError(f"{who}: raw channel {j} or {k} has non-finite values inside objects")
+    words = out.cpu().numpy().view(np.uint64)
+    if flags & _PRODUCTS_BAD_LABEL or not np.array_equal(words[present, 0].view(np.int64), area[present]):
+        raise ValueError(f"{who}: label ids changed under the measurement")
+    return product_table(words[present])
+
+
+def _channel_thresholds(qmax, f, nid, present):
+    thr = np.zeros(nid, dtype=np.int64)
+    thr[present] = coloc_thresholds(qmax, f)
+    return thr
+
+
+def _products_columns_of(lab, channels, shifts, nid, present, area, cols, std, colocalization, f):
+    """the std and colocalization columns; channels: [(raw_d, raw_type)]; cols: the table so far, whose intensity_max columns
+    give the thresholds.  One clx_region_products call per pair j < k; a channel that no pair covers (no colocalization) takes
+    one with a == b and no thresholds for its std"""
+    nch = len(channels)
+    pairs = [(j, k) for j in range(nch) for k in range(j + 1, nch)] if colocalization else []
+    out_std, out_coloc = {}, {}
+    if not len(present):
+        empty = product_table(np.zeros((0, PRODUCT_WORDS), dtype=np.uint64))
+        for k in range(nch if std else 0):
+            out_std.update(products_columns(empty, j=k, k=k, std=True, colocalization=False))
+        for j, k in pairs:
+            out_coloc.update(products_columns(empty, j=j, k=k))
+        return {**out_std, **out_coloc}
+    thr = {}
+    for j, k in pairs:
+        for c in (j, k):
+            if c not in thr:
+                thr[c] = _channel_thresholds(quantised(cols[f"intensity_max_c{c}"], shifts[c]), f, nid, present)
+        table = _products_rows(lab, channels[j], channels[k], nid, shifts[j], shifts[k], thr[j], thr[k], area, present, "region_table", j, k)
+        got = products_columns(table, shifts[j], shifts[k], j, k, std=std, colocalization=True)
+        for name in [n for n in got if n.startswith("intensity_std_")]:
+            out_std.setdefault(name, got.pop(name))
+        out_coloc.update(got)
+    for k in range(nch if std and not pairs else 0):
+        table = _products_rows(lab, channels[k], channels[k], nid, shifts[k], shifts[k], None, None, area, present, "region_table", k, k)
+        out_std.update(products_columns(table, shifts[k], shifts[k], k, k, std=True, colocalization=False))
+    return {**{f"intensity_std_c{k}": out_std[f"intensity_std_c{k}"] for k in range(nch if std else 0)}, **out_coloc}
+
+
+def channel_products(labels, raw, j=0, k=1, threshold=None, device=None):
+    """The sums of products of channels ``j`` and ``k`` of ``raw`` (``(*spatial)`` or ``(C, *spatial)``; float32, float64 or
+    integers that fit int32) inside every object of ``labels`` (2-D or 3-D integers, array or device tensor; the same types and
+    range as ``region_table``): ``(ids, table, shift_j, shift_k)``.  ``ids`` int64 (n): the objects present, ascending.
+    ``table``: ``product_table``'s dict of ``clx_region_products``' twenty words per object, exact integers of
+    ``q = rint(v * 2**shift)`` with the scales ``region_table`` uses for its ``intensity_mean`` (``intensity_shift``; 0 for
+    integers): int64 arrays ``n, sum_a, sum_b, n_both, sum_a_above, sum_b_above, sum_a_both, sum_b_both`` and object arrays of
+    Python ints ``sum_aa, sum_bb, sum_ab, sum_aa_both, sum_bb_both, sum_ab_both`` (a is channel j, b channel k; ``j == k`` is
+    allowed).  ``threshold=None``: every pixel counts as above, the conditioned sums equal the others; a float ``f`` in [0, 1]:
+    a pixel of object i is above in a channel where ``q >= ceil(f * qmax_i)``, ``qmax_i`` the object's quantised maximum in that
+    channel (``coloc_thresholds``).  ``products_columns`` forms ``region_table``'s columns of the table.
+    Runs on a HIP device; there is no CPU path."""
+    who = "channel_products"
+    f = None if threshold is None else _check_products(False, False, threshold, labels, raw, who)
+    if raw is None:
+        raise ValueError(f"{who}: raw is needed")
+    raw = _raw_channels(raw, tuple(int(v) for v in labels.shape), who)
+    j, k = int(j), int(k)
+    if not (0 <= j < raw.shape[0] and 0 <= k < raw.shape[0]):
+        raise ValueError(f"{who}: channels j = {j} and k = {k} must lie in [0, {raw.shape[0]})")
+    lab, device, nd, spatial, nid = _labels_on_device(labels, device, who)
+    empty = np.zeros(0, dtype=np.int64), product_table(np.zeros((0, PRODUCT_WORDS), dtype=np.uint64)), 0, 0
+    if lab.numel() == 0 or nid == 1:
+        return empty
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    area_d, _, _, _ = _moments(lab, Z, Y, X, nid, who)
+    area = area_d.cpu().numpy()
+    area[0] = 0
+    present = np.flatnonzero(area > 0)
+    if not len(present):
+        return empty
+    flat = lab.reshape(-1)
+    chans, shifts, thr = {}, {}, {}
+    for c in sorted({j, k}):
+        raw_d, raw_type = _to_device_raw(raw[c], device)
+        chans[c] = (raw_d.reshape(-1), raw_type)
+        columns, shifts[c] = _channel_columns(flat, chans[c][0], raw_type, nid, present, area, c)
+        thr[c] = None if f is None else _channel_thresholds(quantised(columns[f"intensity_max_c{c}"], shifts[c]), f, nid, present)
+    table = _products_rows(flat, chans[j], chans[k], nid, shifts[j], shifts[k], thr[j], thr[k], area, present, who, j, k)
+    return present.astype(np.int64), table, shifts[j], shifts[k]
+
+
 def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False,
                  quantiles=None, mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None,
-                 radial=False, radial_rings=4, radial_width=None, radial_wedges=False):
+                 radial=False, radial_rings=4, radial_width=None, radial_wedges=False, std=False, colocalization=False,
+                 coloc_threshold=0.15):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -1108,16 +1332,27 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False, 
     inscribed radius; an integer in 1 .. 32768: bands of that many pixels from the boundary, the last ring taking what lies
     deeper.  ``edge`` is the one of ``inscribed``; the distance map is formed once for both.  All of channel 0's radial
     columns come before channel 1's.
+    ``std=True`` (needs ``raw``) appends, after all of those, ``intensity_std_c{k}`` per channel: the population standard
+    deviation of the object's raw values (regionprops' ``intensity_std``, CellProfiler's StdIntensity), from the exact 128-bit
+    sum of the squared quantised values.  ``colocalization=True`` (needs at least 2 channels) appends, after those, for every
+    pair of channels j < k in lexicographic order ``coloc_pearson_c{j}_c{k}``, ``coloc_slope_c{j}_c{k}``,
+    ``coloc_overlap_c{j}_c{k}``, ``coloc_k1_c{j}_c{k}``, ``coloc_k2_c{j}_c{k}``, ``coloc_manders1_c{j}_c{k}`` and
+    ``coloc_manders2_c{j}_c{k}``: the quantities of CellProfiler's MeasureColocalization per object (``channel_products``,
+    ``products_columns``).  Pearson and slope take all of the object's pixels; the other five the pixels at or above
+    ``coloc_threshold`` (a float in [0, 1]) times the object's quantised maximum in each channel (``coloc_thresholds``: the
+    project's own convention).  A column is NaN where its denominator is 0.
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
     return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge, quantiles, mad, texture, texture_levels,
-                         texture_distance, texture_range, radial, radial_rings, radial_width, radial_wedges)[0]
+                         texture_distance, texture_range, radial, radial_rings, radial_width, radial_wedges, std, colocalization,
+                         coloc_threshold)[0]
 
 
 def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False, quantiles=None,
                   mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None, radial=False,
-                  radial_rings=4, radial_width=None, radial_wedges=False):
+                  radial_rings=4, radial_width=None, radial_wedges=False, std=False, colocalization=False, coloc_threshold=0.15):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     quantiles = _check_quantiles(quantiles, mad, raw)
+    coloc_threshold = _check_products(std, colocalization, coloc_threshold, labels, raw)
     if radial:
         radial_rings, radial_width, radial_W = _check_radial(radial_rings, radial_width, radial_wedges, getattr(labels, "ndim", None))
     if texture:
@@ -1148,7 +1383,7 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         raw = _raw_channels(raw, spatial, "region_table")
         for k in range(raw.shape[0]):
             raw_d, raw_type = _to_device_raw(raw[k], device)
-            if quantiles or mad or texture or radial:
+            if quantiles or mad or texture or radial or std or colocalization:
                 channels.append((raw_d.reshape(-1), raw_type))
             shifts.append(0)
             if len(present):
@@ -1194,6 +1429,8 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         cols.update(radial_columns(area[present], count, nd=nd))
         for k, isum in enumerate(isums):
             cols.update(radial_columns(area[present], count, isum, shifts[k], nd, k))
+    if std or colocalization:
+        cols.update(_products_columns_of(lab.reshape(-1), channels, shifts, nid, present, area, cols, std, colocalization, coloc_threshold))
     return cols, pairs
 
 
@@ -1202,7 +1439,8 @@ def _format(value):
 
 
 def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False, quantiles=None, mad=False, texture=False,
-            texture_levels=8, texture_distance=1, radial=False, radial_rings=4, radial_width=None, radial_wedges=False) -> None:
+            texture_levels=8, texture_distance=1, radial=False, radial_rings=4, radial_width=None, radial_wedges=False, std=False,
+            colocalization=False, coloc_threshold=0.15) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
@@ -1214,7 +1452,9 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
     pixel distance ``texture_distance``; their range is per sample and channel, the smallest and the largest value under that
     sample's objects, so the levels are relative to each image's objects; ``radial=True`` the radial distribution columns at
     ``radial_rings`` rings, relative or ``radial_width`` pixels wide, with ``radial_wedges`` the wedge variation too
-    (``region_table``'s arguments, ``edge=False``).  Rank 0 works alone under torch.distributed."""
+    (``region_table``'s arguments, ``edge=False``); ``std=True`` the intensity standard deviation of every channel,
+    ``colocalization=True`` the colocalization columns of every pair of channels with ``coloc_threshold`` (``region_table``'s
+    arguments).  Rank 0 works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -1238,7 +1478,7 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
             labels = ds_seg[sample, bandwidth].astype(np.int32)
             table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed, False, quantiles, mad,
                                          texture, texture_levels, texture_distance, None, radial, radial_rings, radial_width,
-                                         radial_wedges)
+                                         radial_wedges, std, colocalization, coloc_threshold)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

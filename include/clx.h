@@ -1181,6 +1181,35 @@ int clx_region_radial(const int32_t* labels, const int32_t* dist_sq, const void*
                       int X, int nid, const unsigned long long* inscribed, const int32_t* row, int nrows, int rings,
                       int width, int wedges, int shift, unsigned long long* count, long long* isum, int32_t* bad,
                       clx_stream stream);
+/* Sums of products of two raw channels per object: what the intensity standard deviation and the colocalization of two
+ * channels inside every object need (cellulus_amd.measure.products_columns forms the columns: regionprops' intensity_std,
+ * CellProfiler's MeasureColocalization).  labels, raw_a and raw_b hold npix values; both channels are of `raw_type`;
+ * raw_a == raw_b is allowed.
+ *   q_a, q_b  exactly clx_region_intensity's q of the two channels for shift_a and shift_b: CLX_RAW_I32: q = v, the shifts
+ *             ignored; CLX_RAW_F32 / _F64: q = (long long) rint(ldexp((double) v, shift)) under the same per-pixel bound
+ *             |q| <= 2^62 >> L, L = bit_length(npix).  A product is then at most 2^(124 - 2 L) in magnitude and a sum of fewer
+ *             than 2^L of them is below 2^(124 - L): it fits a signed 128-bit integer, which is how the products are summed
+ *   classes   a pixel of object i is "above a" when q_a >= thr_a[i], "above b" when q_b >= thr_b[i], "both" when it is above
+ *             a and above b.  thr_a, thr_b [nid]: per-id thresholds in q units (any int64); both may be NULL together, and every
+ *             pixel is then above both
+ *   out [nid][20]  per id, as 64-bit words: [0] n, the pixels; [1] Σa, [2] Σb (signed, two's complement); [3] n_both;
+ *             [4] Σa over the pixels above a, [5] Σb over those above b; [6] Σa, [7] Σb over `both`; then six signed 128-bit
+ *             sums as (lo, hi) pairs of words, two's complement: [8,9] Σaa, [10,11] Σbb, [12,13] Σab over all the id's pixels,
+ *             [14,15] Σaa, [16,17] Σbb, [18,19] Σab over `both`.  Σa and Σb equal clx_region_intensity's isum for the same
+ *             shift bit for bit, and n is clx_region_moments' area.  Row 0 (background) is unspecified
+ *   bad [1]   bit 0: a label outside [0, nid) -- never followed as an index, counts as background
+ *             bit 1: under an object id a NaN, +-Inf or |q| above the bound in EITHER channel; that pixel is skipped in all
+ *                    20 words.  Such values on the background are ignored
+ * The entry point initialises out and bad itself.  Integer adds only; a 128-bit add, to LDS and to global memory alike, is
+ * two 64-bit atomic adds (the low limbs, whose returned old value gives the carry exactly, then the high limbs plus carry),
+ * and adds modulo 2^128 commute: the same map gives the same bits in every run.  Two launches, whatever the number of
+ * objects: the initialisation, and one pass in which a block combines runs of pixels of one id in a table of 256 ids in LDS
+ * (20 words an id with thresholds, 9 without, where the conditioned words are copies) that it adds to the output once.
+ * Refused (CLX_ERR_ARG) before any launch, the outputs untouched: null pointers other than the threshold pair as a pair,
+ * exactly one of thr_a / thr_b null, an unknown raw_type, nid outside [1, 2^24], npix outside [1, 2^32). */
+int clx_region_products(const int32_t* labels, const void* raw_a, const void* raw_b, int raw_type, long long npix, int nid,
+                        int shift_a, int shift_b, const long long* thr_a, const long long* thr_b,
+                        unsigned long long* out /* [nid][20] */, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
