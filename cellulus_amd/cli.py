@@ -1,7 +1,7 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
 (``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]
 [--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]
-[--std] [--colocalization] [--coloc-threshold F]``)."""
+[--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity]``)."""
 
 import click
 import tomli
@@ -61,8 +61,14 @@ def infer(config_file):
                    "coefficients inside every object (needs at least 2 channels)")
 @click.option("--coloc-threshold", default=0.15, show_default=True, metavar="F", type=click.FloatRange(0.0, 1.0),
               help="fraction of an object's maximum from which a pixel counts for the overlap, K1 / K2 and Manders columns")
+@click.option("--weighted", is_flag=True,
+              help="add per raw channel the integrated intensity, the intensity-weighted centroid and covariance, the distance between "
+                   "the plain and the weighted centroid and the position of the brightest pixel")
+@click.option("--border-intensity", is_flag=True,
+              help="add the number of border pixels of every object and per raw channel the sum, mean, standard deviation, minimum "
+                   "and maximum of the intensity over them")
 def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, texture, texture_levels, texture_distance, radial,
-            radial_rings, radial_width, radial_wedges, std, colocalization, coloc_threshold):
+            radial_rings, radial_width, radial_wedges, std, colocalization, coloc_threshold, weighted, border_intensity):
     from .measure import measure as measure_experiment
 
     if quantiles is not None:
@@ -73,4 +79,5 @@ def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, te
     measure_experiment(ExperimentConfig(**_load(config_file)).inference_config, contacts=contacts, topology=topology, hull=hull,
                        inscribed=inscribed, quantiles=quantiles, mad=mad, texture=texture, texture_levels=texture_levels,
                        texture_distance=texture_distance, radial=radial, radial_rings=radial_rings, radial_width=radial_width,
-                       radial_wedges=radial_wedges, std=std, colocalization=colocalization, coloc_threshold=coloc_threshold)
+                       radial_wedges=radial_wedges, std=std, colocalization=colocalization, coloc_threshold=coloc_threshold,
+                       weighted=weighted, border_intensity=border_intensity)

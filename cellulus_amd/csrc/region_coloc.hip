@@ -21,11 +21,9 @@
 // block a CU with thresholds; 128 would double the ids that a block of a crowded map sends to global memory one atomic at
 // a time.  Words are the slow index (acc[word][slot]): the lanes of a flush walk consecutive banks.
 // What the kernel lives on is bytes in flight, so a lane issues the loads of its next trip before it works on this one.
-#include "region_scan.h"
+#include "region_sums.h"
 
 namespace {
-
-typedef __int128 i128;
 
 constexpr int NW = 20;                  // words per id in the output and in the table
 constexpr int NS = 8;                   // 64-bit words: n Σa Σb n_both Σa|above_a Σb|above_b Σa|both Σb|both
@@ -34,35 +32,6 @@ constexpr int INIT_GRID = 1024;
 // With thresholds a block's registers and its 41 KiB table let 3 blocks share a CU: on the 256 CUs of an MI355X 768 blocks run
 // at once, and MAX_GRID = 1024 of them would be one full round and a second one a third full.  (Without thresholds 4 fit.)
 constexpr int THR_GRID = 768;
-enum { BAD_LABEL = 1, BAD_VALUE = 2 };
-
-template <typename T> struct alignas(16) Raw4 { T v[PPL]; };
-
-// q of one raw value as clx_region_intensity forms it; false: not finite, or |q| above the bound
-template <typename T>
-__device__ __forceinline__ bool quantise(T v, int shift, long long bound, long long* q) {
-  const double t = rint(ldexp((double)v, shift));       // NaN and ±Inf fail the comparison / exceed the bound
-  if (!(fabs(t) <= (double)bound)) return false;        // bound is a power of two: exact as a double
-  *q = (long long)t;
-  return true;
-}
-template <>
-__device__ __forceinline__ bool quantise<int>(int v, int, long long, long long* q) {
-  *q = (long long)v;
-  return true;
-}
-
-template <typename T>
-__device__ __forceinline__ Raw4<T> load_raw(const T* __restrict__ raw, bool vec, long long p0, long long npix) {
-  Raw4<T> rv;
-  if (vec && p0 + PPL <= npix) {
-    rv = *reinterpret_cast<const Raw4<T>*>(raw + p0);
-  } else {
-#pragma unroll
-    for (int k = 0; k < PPL; ++k) rv.v[k] = p0 + k < npix ? raw[p0 + k] : (T)0;
-  }
-  return rv;
-}
 
 // what a lane has summed of one id.  THR false (no thresholds): every pixel is above both, the conditioned words equal
 // the unconditioned ones and are filled in by complete() when the sums leave the lane
@@ -99,22 +68,6 @@ __device__ __forceinline__ void complete(Sums& v) {
     v.s[3] = v.s[0]; v.s[4] = v.s[1]; v.s[5] = v.s[2]; v.s[6] = v.s[1]; v.s[7] = v.s[2];
     v.p[3] = v.p[0]; v.p[4] = v.p[1]; v.p[5] = v.p[2];
   }
-}
-
-__device__ __forceinline__ i128 shfl_down128(i128 v, int d) {
-  const u64 lo = __shfl_down((u64)v, d), hi = __shfl_down((u64)((unsigned __int128)v >> 64), d);
-  return (i128)(((unsigned __int128)hi << 64) | lo);
-}
-
-// (*lo, *hi) += v modulo 2^128, in LDS or global memory: the returned old low limb tells the carry exactly
-__device__ __forceinline__ void add128(u64* lo, u64* hi, i128 v) {
-  const u64 vl = (u64)v;
-  u64 vh = (u64)((unsigned __int128)v >> 64);
-  if (vl) {
-    const u64 old = atomicAdd(lo, vl);
-    if (old + vl < old) ++vh;                           // the low limbs wrapped (vh may wrap to 0: nothing to add then)
-  }
-  if (vh) atomicAdd(hi, vh);
 }
 
 // the twenty words of one id to global memory
@@ -307,12 +260,6 @@ void launch_products(const ProductsArgs& a, const void* raw_a, const void* raw_b
     products_kernel<T, true><<<grid, BLOCK, 0, st>>>(a, (const T*)raw_a, (const T*)raw_b);
   else
     products_kernel<T, false><<<grid, BLOCK, 0, st>>>(a, (const T*)raw_a, (const T*)raw_b);
-}
-
-inline int bit_length(unsigned long long v) {
-  int n = 0;
-  while (v) { ++n; v >>= 1; }
-  return n;
 }
 
 }  // namespace

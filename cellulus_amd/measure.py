@@ -31,12 +31,21 @@ for every pair of raw channels, Pearson's correlation, the regression slope, the
 coefficients inside every object (CellProfiler's MeasureColocalization).  They need Σ q_a q_b, which 64 bits do not hold for
 values quantised to 62 - L bits: the products are summed exactly in 128 bits on the device (``channel_products``;
 ``csrc/region_coloc.hip``: ``clx_region_products``) and ``products_columns`` rounds once.
+And WHERE the signal sits, in coordinates, and what it is on the object's RIM: the intensity-weighted centroid and covariance, the
+distance between the plain and the weighted centroid, the integrated intensity and the position of the brightest pixel
+(regionprops' ``centroid_weighted``, CellProfiler's Location_CenterMassIntensity, MassDisplacement, Location_MaxIntensity,
+IntegratedIntensity), from Σ q·a and Σ q·a·b over an object's pixels, 128-bit sums again, and an arg-max whose ties go to the first
+pixel in raster order (``weighted_moments``; ``csrc/region_weighted.hip``: ``clx_region_weighted``; ``weighted_columns``); and the
+sum, mean, standard deviation, minimum and maximum over the pixels that have a face neighbour outside the object (CellProfiler's
+*IntensityEdge; ``border_intensity``; ``csrc/region_border.hip``: ``clx_region_border_intensity``, a stencil fused with the value
+reduction; ``border_intensity_columns``).  With these the stage covers CellProfiler's MeasureObjectIntensity.
 
     python -m cellulus_amd.measure experiment.toml [--contacts] [--topology] [--hull] [--inscribed]
                                                    [--quantiles 0.25,0.5,0.75] [--mad]
                                                    [--texture] [--texture-levels 8] [--texture-distance 1]
                                                    [--radial] [--radial-rings 4] [--radial-width W] [--radial-wedges]
                                                    [--std] [--colocalization] [--coloc-threshold 0.15]
+                                                   [--weighted] [--border-intensity]
 
 writes ``measurements_bandwidth-<b>.csv`` next to ``evaluate``'s ``results_bandwidth-<b>.txt`` and, with ``--contacts``,
 the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--topology`` adds the topology columns,
@@ -47,7 +56,10 @@ the boundary columns in it and ``contacts_bandwidth-<b>.csv`` beside it; ``--top
 ``radial_meanfrac_r<j>_c<k>`` for ``--radial-rings`` rings (relative to every object's inscribed radius, or ``--radial-width``
 pixels wide from the boundary), ``--radial-wedges`` ``radial_cv_r<j>_c<k>`` too (2-D), ``--std`` ``intensity_std_c<k>`` per
 channel and ``--colocalization`` the seven ``coloc_<quantity>_c<j>_c<k>`` per pair of channels, with ``--coloc-threshold`` the
-fraction of an object's maximum from which a pixel counts for overlap, K1 / K2 and Manders.
+fraction of an object's maximum from which a pixel counts for overlap, K1 / K2 and Manders, ``--weighted`` per channel
+``intensity_sum_c<k>``, ``centroid_weighted_<a>_c<k>``, ``cov_weighted_<ab>_c<k>``, ``mass_displacement_c<k>`` and
+``intensity_peak_<a>_c<k>``, and ``--border-intensity`` ``intensity_border_pixels`` and per channel
+``intensity_border_{sum,mean,std,min,max}_c<k>``.
 """
 
 import math
@@ -645,6 +657,129 @@ def products_columns(table, shift_a=0, shift_b=0, j=0, k=1, std=False, colocaliz
     return cols
 
 
+WEIGHTED_WORDS = 21                     # clx_region_weighted: words per id
+BORDER_WORDS = 7                        # clx_region_border_intensity: words per id
+NO_PEAK = (1 << 64) - 1                 # clx_region_weighted's word 2 where no pixel carries the key
+_WEIGHTED_MOMENTS = ("sum_qz", "sum_qy", "sum_qx", "sum_qzz", "sum_qyy", "sum_qxx", "sum_qzy", "sum_qzx", "sum_qyx")
+_WEIGHTED_BAD_LABEL, _WEIGHTED_BAD_VALUE = 1, 2     # bits of bad[0] of clx_region_weighted and clx_region_border_intensity
+
+
+def _signed128(lo, hi):
+    """Python ints of (lo, hi) uint64 word columns: signed 128-bit, two's complement"""
+    out = np.empty(len(lo), dtype=object)
+    out[:] = [l + (h << 64) - ((h >> 63) << 128) for l, h in zip(lo.tolist(), hi.tolist())]
+    return out
+
+
+def weighted_table(words):
+    """``clx_region_weighted``'s rows (n, 21) of uint64 words as a dict: int64 arrays ``n`` (the counted pixels) and ``sum_q``,
+    an object array ``peak`` (the flat index of the first pixel that attains the maximum, ``NO_PEAK`` where there is none) and
+    object arrays of Python ints ``sum_qz, sum_qy, sum_qx, sum_qzz, sum_qyy, sum_qxx, sum_qzy, sum_qzx, sum_qyx`` (a (lo, hi) pair
+    is one signed 128-bit integer, two's complement)"""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, WEIGHTED_WORDS)
+    table = {"n": np.ascontiguousarray(words[:, 0]).view(np.int64), "sum_q": np.ascontiguousarray(words[:, 1]).view(np.int64)}
+    table["peak"] = np.empty(len(words), dtype=object)
+    table["peak"][:] = words[:, 2].tolist()
+    for i, name in enumerate(_WEIGHTED_MOMENTS):
+        table[name] = _signed128(words[:, 3 + 2 * i], words[:, 4 + 2 * i])
+    return table
+
+
+def border_table(words):
+    """``clx_region_border_intensity``'s rows (n, 7) of uint64 words as a dict: int64 arrays ``pixels`` (the border pixels),
+    ``n`` (those whose value was counted) and ``sum_q``, uint64 arrays ``key_min`` and ``key_max`` (order keys) and an object array
+    of Python ints ``sum_qq``"""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, BORDER_WORDS)
+    table = {name: np.ascontiguousarray(words[:, i]).view(np.int64) for i, name in enumerate(("pixels", "n", "sum_q"))}
+    table["key_min"], table["key_max"] = words[:, 3].copy(), words[:, 4].copy()
+    table["sum_qq"] = _signed128(words[:, 5], words[:, 6])
+    return table
+
+
+def _scaled_column(values, n, exponent):
+    c = np.array(values, dtype=np.float64).reshape(n)
+    with np.errstate(over="ignore", under="ignore"):           # shifts at both clamps can leave float64's range
+        return np.ldexp(c, exponent) if exponent else c
+
+
+def weighted_columns(area, sum1, table, shift, nd, k, shape):
+    """The intensity-weighted columns of channel ``k`` of ``region_table`` from exact integers.  area (n) pixel counts and sum1
+    (n, 3) ``clx_region_moments``' ``Σz Σy Σx`` of the same objects (for the plain centroid), table ``weighted_table``'s dict
+    of them, its sums those of ``q = rint(v * 2**shift)``; nd 2 or 3 (2-D: the z entries are ignored); shape the map's ``nd``
+    extents, which place the peak.  With ``Q = Σq``:
+    ``intensity_sum_c{k}`` = Q · 2^−shift (CellProfiler's IntegratedIntensity);
+    ``centroid_weighted_{a}_c{k}`` = Σq·a / Q (regionprops' ``centroid_weighted``, CellProfiler's Location_CenterMassIntensity);
+    ``cov_weighted_{ab}_c{k}`` = (Q · Σq·a·b − Σq·a · Σq·b) / Q², in ``shape_columns``' pair order (the order-2 central weighted
+    moments over Q);
+    ``mass_displacement_c{k}`` = the distance between ``centroid_*`` and ``centroid_weighted_*`` (MassDisplacement), the square
+    root of the exact fraction;
+    ``intensity_peak_{a}_c{k}`` (int64) = the coordinates of the first pixel in raster order that attains the object's maximum
+    (Location_MaxIntensity; ties go to the first pixel: the project's own convention).
+    Every float is ONE correctly rounded operation on exact integers (and an exact scaling by a power of two); NaN where
+    Q = 0.  Negative weights are taken as they are.  A peak of ``NO_PEAK`` raises: the object has pixels, one of them is its
+    maximum."""
+    assert nd in (2, 3) and len(shape) == nd
+    n = len(table["n"])
+    area = [int(v) for v in np.asarray(area).reshape(-1)]
+    s1 = [[int(v) for v in r] for r in np.asarray(sum1).reshape(-1, 3).tolist()]
+    assert len(area) == len(s1) == n
+    Q = [int(v) for v in table["sum_q"]]
+    m1 = [list(table[name]) for name in _WEIGHTED_MOMENTS[:3]]
+    m2 = [list(table[name]) for name in _WEIGHTED_MOMENTS[3:]]
+    axes = range(3 - nd, 3)
+    nan = math.nan
+    cols = {f"intensity_sum_c{k}": _scaled_column([float(q) for q in Q], n, -int(shift))}
+    for a in axes:
+        cols[f"centroid_weighted_{_AXES[a]}_c{k}"] = np.array([m / q if q else nan for m, q in zip(m1[a], Q)], dtype=np.float64).reshape(n)
+    for p, (a, b) in enumerate(_PAIRS):
+        if a >= 3 - nd:
+            cols[f"cov_weighted_{_AXES[a]}{_AXES[b]}_c{k}"] = np.array(
+                [(q * s - x * y) / (q * q) if q else nan for q, s, x, y in zip(Q, m2[p], m1[a], m1[b])], dtype=np.float64).reshape(n)
+    disp = []
+    for i, (A, q) in enumerate(zip(area, Q)):
+        disp.append(_sqrt_ratio(sum((s1[i][a] * q - m1[a][i] * A) ** 2 for a in axes), (A * q) ** 2) if q and A else nan)
+    cols[f"mass_displacement_c{k}"] = np.array(disp, dtype=np.float64).reshape(n)
+    peak = [int(v) for v in table["peak"]]
+    if any(v == NO_PEAK for v in peak):
+        raise RuntimeError("weighted_columns: internal error: an object without a peak pixel")
+    where = np.unravel_index(np.array(peak, dtype=np.int64), tuple(int(v) for v in shape)) if n else (np.zeros(0, dtype=np.int64),) * nd
+    for axis, c in zip(_AXES[3 - nd:], where):
+        cols[f"intensity_peak_{axis}_c{k}"] = np.asarray(c, dtype=np.int64)
+    return cols
+
+
+def border_intensity_columns(table, shift=0, raw_type=None, k=None):
+    """The border columns of ``region_table`` from ``border_table``'s exact integers.  ``k=None``: the column that belongs to no
+    channel, ``intensity_border_pixels`` (int64): the object's pixels with a face neighbour (4 in 2-D, 6 in 3-D) that is not the
+    object's, the outside of the image among them; in 2-D it equals ``border_pixels``.  Else the columns of channel ``k``, whose
+    sums are those of ``q = rint(v * 2**shift)`` and whose keys decode to ``raw_type`` (0 float32, 1 float64, 2 int32), over the
+    border pixels (CellProfiler's *IntensityEdge): ``intensity_border_sum_c{k}`` = Σq · 2^−shift, ``intensity_border_mean_c{k}``
+    = Σq / n · 2^−shift, ``intensity_border_std_c{k}`` = sqrt((n Σq² − (Σq)²) / n²) · 2^−shift, the POPULATION standard
+    deviation, ``intensity_border_min_c{k}`` and ``intensity_border_max_c{k}`` in the raw dtype.  Every float is ONE correctly
+    rounded operation on exact integers and an exact scaling by a power of two; NaN where n = 0."""
+    if k is None:
+        return {"intensity_border_pixels": np.asarray(table["pixels"]).astype(np.int64).reshape(-1)}
+    from .segment import _decode_keys
+
+    n = [int(v) for v in table["n"]]
+    S = [int(v) for v in table["sum_q"]]
+    SS = list(table["sum_qq"])
+    var = [m * ss - s * s for m, s, ss in zip(n, S, SS)]
+    assert all(v >= 0 for v in var), "border_intensity_columns: a negative variance: the sums do not belong together"
+    nan = math.nan
+    values = _decode_keys(np.stack([np.asarray(table["key_min"], dtype=np.uint64), np.asarray(table["key_max"], dtype=np.uint64)],
+                                   axis=1).reshape(-1, 2), raw_type)
+    return {f"intensity_border_sum_c{k}": _scaled_column([float(s) for s in S], len(n), -int(shift)),
+            f"intensity_border_mean_c{k}": _scaled_column([s / m if m else nan for s, m in zip(S, n)], len(n), -int(shift)),
+            f"intensity_border_std_c{k}": _scaled_column([_sqrt_ratio(v, m * m) if m else nan for v, m in zip(var, n)], len(n), -int(shift)),
+            f"intensity_border_min_c{k}": values[:, 0].copy(), f"intensity_border_max_c{k}": values[:, 1].copy()}
+
+
+def _check_weighted(weighted, border_intensity, raw, who="region_table"):
+    if (weighted or border_intensity) and raw is None:
+        raise ValueError(f"{who}: weighted and border_intensity need raw")
+
+
 def _resolve_device(labels, device):
     import torch
 
@@ -712,6 +847,12 @@ def _intensity(lab, raw_d, raw_type, nid, shift):
 
 def _channel_columns(lab, raw_d, raw_type, nid, present, area, k):
     """-> (the intensity columns of channel k, the shift its sums were quantised with)"""
+    return _channel_columns_keys(lab, raw_d, raw_type, nid, present, area, k)[:2]
+
+
+def _channel_columns_keys(lab, raw_d, raw_type, nid, present, area, k):
+    """-> (the intensity columns of channel k, the shift its sums were quantised with, the largest order key of every id
+    (uint64 (nid)): clx_region_weighted's peak_keys)"""
     from .segment import _RAW_I32, _decode_keys
     from .utils.otsu import minmax_on_device
 
@@ -738,7 +879,8 @@ def _channel_columns(lab, raw_d, raw_type, nid, present, area, k):
     mean = _exact_div(isum[present].astype(object), area[present].astype(object))
     if shift:
         mean = np.ldexp(mean, -shift)
-    return {f"intensity_mean_c{k}": mean, f"intensity_min_c{k}": vals[:, 0].copy(), f"intensity_max_c{k}": vals[:, 1].copy()}, shift
+    return ({f"intensity_mean_c{k}": mean, f"intensity_min_c{k}": vals[:, 0].copy(), f"intensity_max_c{k}": vals[:, 1].copy()}, shift,
+            np.ascontiguousarray(keys[:, 1]))
 
 
 def _labels_on_device(labels, device, who):
@@ -1288,10 +1430,130 @@ def channel_products(labels, raw, j=0, k=1, threshold=None, device=None):
     return present.astype(np.int64), table, shifts[j], shifts[k]
 
 
+def _weighted_rows(lab, raw_d, raw_type, Z, Y, X, nid, shift, peak_keys, area, present, who, k):
+    """one clx_region_weighted call -> weighted_table of the present ids.  peak_keys: uint64 host array (nid), clx_region_intensity's
+    largest keys; area: the host areas by id, against which the pixels the call counted are checked"""
+    import torch
+
+    device = lab.device
+    out = torch.empty((nid, WEIGHTED_WORDS), dtype=torch.int64, device=device)
+    bad = torch.empty(1, dtype=torch.int32, device=device)
+    keys_d = torch.from_numpy(np.ascontiguousarray(peak_keys, dtype=np.uint64).view(np.int64)).to(device)
+    _clx.call("clx_region_weighted", _clx.ptr(lab), _clx.ptr(raw_d), raw_type, Z, Y, X, nid, int(shift), _clx.ptr(keys_d),
+              _clx.ptr(out), _clx.ptr(bad), _clx.stream_ptr(device))
+    flags = int(bad.item())
+    if flags & _WEIGHTED_BAD_VALUE:
+        raise ValueError(f"{who}: raw channel {k} has non-finite values inside objects")
+    words = out.cpu().numpy().view(np.uint64)
+    if flags & _WEIGHTED_BAD_LABEL or not np.array_equal(words[present, 0].view(np.int64), area[present]):
+        raise ValueError(f"{who}: label ids changed under the measurement")
+    return weighted_table(words[present])
+
+
+def _border_rows(lab, raw_d, raw_type, nd, Z, Y, X, nid, shift, area, present, who, k):
+    """one clx_region_border_intensity call -> border_table of the present ids; area: the host areas by id, which bound the
+    border pixels of every object from above (and 1 bounds them from below)"""
+    import torch
+
+    device = lab.device
+    out = torch.empty((nid, BORDER_WORDS), dtype=torch.int64, device=device)
+    bad = torch.empty(1, dtype=torch.int32, device=device)
+    _clx.call("clx_region_border_intensity", _clx.ptr(lab), _clx.ptr(raw_d), raw_type, nd, Z, Y, X, nid, int(shift), _clx.ptr(out),
+              _clx.ptr(bad), _clx.stream_ptr(device))
+    flags = int(bad.item())
+    if flags & _WEIGHTED_BAD_VALUE:
+        raise ValueError(f"{who}: raw channel {k} has non-finite values inside objects")
+    words = out.cpu().numpy().view(np.uint64)
+    pixels = words[present, 0].view(np.int64)
+    if flags & _WEIGHTED_BAD_LABEL or (pixels < 1).any() or (pixels > area[present]).any():
+        raise ValueError(f"{who}: label ids changed under the measurement")
+    return border_table(words[present])
+
+
+def _weighted_columns_of(lab, channels, shifts, peak_keys, nd, Z, Y, X, spatial, nid, present, area, sum1, weighted, border):
+    """the weighted and the border columns: weighted's of every channel, then the border pixels and border's of every channel;
+    one clx_region_weighted and one clx_region_border_intensity call per channel.  channels: [(raw_d, raw_type)]; peak_keys: per
+    channel clx_region_intensity's largest keys (uint64 (nid)); sum1: clx_region_moments' rows of the present ids"""
+    out = {}
+    for k, (raw_d, raw_type) in enumerate(channels if weighted else []):
+        if len(present):
+            table = _weighted_rows(lab, raw_d, raw_type, Z, Y, X, nid, shifts[k], peak_keys[k], area, present, "region_table", k)
+        else:
+            table = weighted_table(np.zeros((0, WEIGHTED_WORDS), dtype=np.uint64))
+        out.update(weighted_columns(area[present], sum1, table, shifts[k], nd, k, spatial))
+    for k, (raw_d, raw_type) in enumerate(channels if border else []):
+        if len(present):
+            table = _border_rows(lab, raw_d, raw_type, nd, Z, Y, X, nid, shifts[k], area, present, "region_table", k)
+        else:
+            table = border_table(np.zeros((0, BORDER_WORDS), dtype=np.uint64))
+        if k == 0:
+            out.update(border_intensity_columns(table))
+        out.update(border_intensity_columns(table, shifts[k], raw_type, k))
+    return out
+
+
+def _one_channel(labels, raw, k, device, who):
+    """the front weighted_moments and border_intensity share -> None for a map without objects, else (lab flat, nd, spatial,
+    (Z, Y, X), nid, area, present, raw_d flat, raw_type, shift, largest keys)"""
+    if raw is None:
+        raise ValueError(f"{who}: raw is needed")
+    raw = _raw_channels(raw, tuple(int(v) for v in labels.shape), who)
+    k = int(k)
+    if not 0 <= k < raw.shape[0]:
+        raise ValueError(f"{who}: channel k = {k} must lie in [0, {raw.shape[0]})")
+    lab, device, nd, spatial, nid = _labels_on_device(labels, device, who)
+    if lab.numel() == 0 or nid == 1:
+        return None
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    area_d, _, _, _ = _moments(lab, Z, Y, X, nid, who)
+    area = area_d.cpu().numpy()
+    area[0] = 0
+    present = np.flatnonzero(area > 0)
+    if not len(present):
+        return None
+    flat = lab.reshape(-1)
+    raw_d, raw_type = _to_device_raw(raw[k], device)
+    raw_d = raw_d.reshape(-1)
+    _, shift, keys = _channel_columns_keys(flat, raw_d, raw_type, nid, present, area, k)
+    return flat, nd, spatial, (Z, Y, X), nid, area, present, raw_d, raw_type, shift, keys
+
+
+def weighted_moments(labels, raw, k=0, device=None):
+    """The intensity-weighted sums of channel ``k`` of ``raw`` (``(*spatial)`` or ``(C, *spatial)``; float32, float64 or integers
+    that fit int32) inside every object of ``labels`` (2-D or 3-D integers, array or device tensor; the same types and range as
+    ``region_table``): ``(ids, table, shift)``.  ``ids`` int64 (n): the objects present, ascending.  ``table``:
+    ``weighted_table``'s dict of ``clx_region_weighted``'s 21 words per object, exact integers of ``q = rint(v * 2**shift)`` with
+    the scale ``region_table`` uses for its ``intensity_mean`` (``intensity_shift``; 0 for integers): int64 arrays ``n`` and
+    ``sum_q``, and Python ints ``peak`` (the flat index of the first pixel in raster order that attains the object's maximum)
+    and ``sum_qz, sum_qy, sum_qx, sum_qzz, sum_qyy, sum_qxx, sum_qzy, sum_qzx, sum_qyx`` (a 2-D map has z = 0).
+    ``weighted_columns`` forms ``region_table``'s columns of the table.  Runs on a HIP device; there is no CPU path."""
+    who = "weighted_moments"
+    got = _one_channel(labels, raw, k, device, who)
+    if got is None:
+        return np.zeros(0, dtype=np.int64), weighted_table(np.zeros((0, WEIGHTED_WORDS), dtype=np.uint64)), 0
+    flat, _, _, (Z, Y, X), nid, area, present, raw_d, raw_type, shift, keys = got
+    return present.astype(np.int64), _weighted_rows(flat, raw_d, raw_type, Z, Y, X, nid, shift, keys, area, present, who, int(k)), shift
+
+
+def border_intensity(labels, raw, k=0, device=None):
+    """The sums of channel ``k`` of ``raw`` over the BORDER pixels of every object of ``labels`` (the arguments of
+    ``weighted_moments``): ``(ids, table, shift)``.  A border pixel of object i has a face neighbour (4 in 2-D, 6 in 3-D) that is
+    not i: another object, background or the outside of the image.  ``table``: ``border_table``'s dict of
+    ``clx_region_border_intensity``'s seven words per object: int64 arrays ``pixels`` (the border pixels), ``n`` (those counted)
+    and ``sum_q``, uint64 order keys ``key_min`` and ``key_max`` and Python ints ``sum_qq``, of ``q = rint(v * 2**shift)``.
+    ``border_intensity_columns`` forms ``region_table``'s columns of the table.  Runs on a HIP device; there is no CPU path."""
+    who = "border_intensity"
+    got = _one_channel(labels, raw, k, device, who)
+    if got is None:
+        return np.zeros(0, dtype=np.int64), border_table(np.zeros((0, BORDER_WORDS), dtype=np.uint64)), 0
+    flat, nd, _, (Z, Y, X), nid, area, present, raw_d, raw_type, shift, _ = got
+    return present.astype(np.int64), _border_rows(flat, raw_d, raw_type, nd, Z, Y, X, nid, shift, area, present, who, int(k)), shift
+
+
 def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False,
                  quantiles=None, mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None,
                  radial=False, radial_rings=4, radial_width=None, radial_wedges=False, std=False, colocalization=False,
-                 coloc_threshold=0.15):
+                 coloc_threshold=0.15, weighted=False, border_intensity=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -1341,18 +1603,33 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False, 
     ``products_columns``).  Pearson and slope take all of the object's pixels; the other five the pixels at or above
     ``coloc_threshold`` (a float in [0, 1]) times the object's quantised maximum in each channel (``coloc_thresholds``: the
     project's own convention).  A column is NaN where its denominator is 0.
+    ``weighted=True`` (needs ``raw``) appends, after all of those, per channel k ``intensity_sum_c{k}`` (the integrated
+    intensity), ``centroid_weighted_*_c{k}``, ``cov_weighted_*_c{k}`` (the pairs of ``cov_*``), ``mass_displacement_c{k}`` (the
+    distance between ``centroid_*`` and ``centroid_weighted_*``) and ``intensity_peak_*_c{k}`` (int64: where the object's
+    brightest pixel sits, the first in raster order among equals): regionprops' ``centroid_weighted`` and order-2
+    ``moments_weighted_central`` over the sum, CellProfiler's Location_CenterMassIntensity, MassDisplacement and
+    Location_MaxIntensity, from exact 128-bit sums of value times coordinates (``weighted_moments``, ``weighted_columns``);
+    float columns are NaN where the object's values sum to 0.  ``border_intensity=True`` (needs ``raw``) appends, after those,
+    ``intensity_border_pixels`` (int64, once: the object's pixels with a face neighbour that is not the object's; in 2-D it
+    equals ``border_pixels``) and per channel k ``intensity_border_sum_c{k}``, ``intensity_border_mean_c{k}``,
+    ``intensity_border_std_c{k}`` (population) and, in the raw dtype, ``intensity_border_min_c{k}`` and
+    ``intensity_border_max_c{k}`` over those pixels (CellProfiler's *IntensityEdge; ``border_intensity``,
+    ``border_intensity_columns``).  It has nothing to do with ``edge``, which says whether the image edge counts as background
+    for the distance map.  All of channel 0's weighted columns come before channel 1's, and so do the border columns.
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
     return _region_table(labels, raw, device, boundary, topology, hull, inscribed, edge, quantiles, mad, texture, texture_levels,
                          texture_distance, texture_range, radial, radial_rings, radial_width, radial_wedges, std, colocalization,
-                         coloc_threshold)[0]
+                         coloc_threshold, weighted, border_intensity)[0]
 
 
 def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False, quantiles=None,
                   mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None, radial=False,
-                  radial_rings=4, radial_width=None, radial_wedges=False, std=False, colocalization=False, coloc_threshold=0.15):
+                  radial_rings=4, radial_width=None, radial_wedges=False, std=False, colocalization=False, coloc_threshold=0.15,
+                  weighted=False, border_intensity=False):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
     quantiles = _check_quantiles(quantiles, mad, raw)
     coloc_threshold = _check_products(std, colocalization, coloc_threshold, labels, raw)
+    _check_weighted(weighted, border_intensity, raw)
     if radial:
         radial_rings, radial_width, radial_W = _check_radial(radial_rings, radial_width, radial_wedges, getattr(labels, "ndim", None))
     if texture:
@@ -1367,6 +1644,7 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
                              np.zeros((0, 3), np.uint64), np.zeros((0, 6), np.uint64), nd)
         present = np.zeros(0, dtype=np.int64)
         bbox = np.zeros((0, 6), dtype=np.int32)
+        sum1 = np.zeros((0, 3), dtype=np.uint64)
         bbox_d = bbox_all = area_d = None
     else:
         area_d, bbox_d, sum1_d, sum2_d = _moments(lab, Z, Y, X, nid, "region_table")
@@ -1375,19 +1653,19 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         present = np.flatnonzero(area > 0)
         bbox_all = bbox_d.cpu().numpy()
         bbox = bbox_all[present]
-        cols = shape_columns(present, area[present], bbox,
-                             sum1_d.cpu().numpy().view(np.uint64)[present],
-                             sum2_d.cpu().numpy().view(np.uint64)[present], nd)
-    channels, shifts = [], []                                # kept on the device for the order statistics, texture, radial
+        sum1 = sum1_d.cpu().numpy().view(np.uint64)[present]
+        cols = shape_columns(present, area[present], bbox, sum1, sum2_d.cpu().numpy().view(np.uint64)[present], nd)
+    channels, shifts, peak_keys = [], [], []                 # kept on the device for the order statistics, texture, radial ...
     if raw is not None:
         raw = _raw_channels(raw, spatial, "region_table")
         for k in range(raw.shape[0]):
             raw_d, raw_type = _to_device_raw(raw[k], device)
-            if quantiles or mad or texture or radial or std or colocalization:
+            if quantiles or mad or texture or radial or std or colocalization or weighted or border_intensity:
                 channels.append((raw_d.reshape(-1), raw_type))
             shifts.append(0)
+            peak_keys.append(None)
             if len(present):
-                intensity, shifts[k] = _channel_columns(lab.reshape(-1), raw_d.reshape(-1), raw_type, nid, present, area, k)
+                intensity, shifts[k], peak_keys[k] = _channel_columns_keys(lab.reshape(-1), raw_d.reshape(-1), raw_type, nid, present, area, k)
                 cols.update(intensity)
             else:
                 dt = raw_d.cpu().numpy().dtype
@@ -1431,6 +1709,9 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
             cols.update(radial_columns(area[present], count, isum, shifts[k], nd, k))
     if std or colocalization:
         cols.update(_products_columns_of(lab.reshape(-1), channels, shifts, nid, present, area, cols, std, colocalization, coloc_threshold))
+    if weighted or border_intensity:
+        cols.update(_weighted_columns_of(lab.reshape(-1), channels, shifts, peak_keys, nd, Z, Y, X, spatial, nid, present, area, sum1,
+                                         weighted, border_intensity))
     return cols, pairs
 
 
@@ -1440,7 +1721,7 @@ def _format(value):
 
 def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False, quantiles=None, mad=False, texture=False,
             texture_levels=8, texture_distance=1, radial=False, radial_rings=4, radial_width=None, radial_wedges=False, std=False,
-            colocalization=False, coloc_threshold=0.15) -> None:
+            colocalization=False, coloc_threshold=0.15, weighted=False, border_intensity=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
@@ -1454,7 +1735,9 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
     ``radial_rings`` rings, relative or ``radial_width`` pixels wide, with ``radial_wedges`` the wedge variation too
     (``region_table``'s arguments, ``edge=False``); ``std=True`` the intensity standard deviation of every channel,
     ``colocalization=True`` the colocalization columns of every pair of channels with ``coloc_threshold`` (``region_table``'s
-    arguments).  Rank 0 works alone under torch.distributed."""
+    arguments); ``weighted=True`` the intensity-weighted centroid, covariance, mass displacement, integrated intensity and peak
+    position of every channel, ``border_intensity=True`` the intensity columns over every object's border pixels
+    (``region_table``'s arguments, ``edge=False``).  Rank 0 works alone under torch.distributed."""
     import torch
 
     from . import parallel
@@ -1478,7 +1761,7 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
             labels = ds_seg[sample, bandwidth].astype(np.int32)
             table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology, hull, inscribed, False, quantiles, mad,
                                          texture, texture_levels, texture_distance, None, radial, radial_rings, radial_width,
-                                         radial_wedges, std, colocalization, coloc_threshold)
+                                         radial_wedges, std, colocalization, coloc_threshold, weighted, border_intensity)
             if contacts:
                 pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
             header = header or ["sample"] + list(table)

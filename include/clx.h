@@ -1210,6 +1210,54 @@ int clx_region_radial(const int32_t* labels, const int32_t* dist_sq, const void*
 int clx_region_products(const int32_t* labels, const void* raw_a, const void* raw_b, int raw_type, long long npix, int nid,
                         int shift_a, int shift_b, const long long* thr_a, const long long* thr_b,
                         unsigned long long* out /* [nid][20] */, int32_t* bad, clx_stream stream);
+/* Intensity-weighted moments and the place of the peak per object: what the weighted centroid, the weighted covariance, the
+ * mass displacement, the integrated intensity and the position of the brightest pixel need (cellulus_amd.measure.
+ * weighted_columns forms the columns: regionprops' centroid_weighted, CellProfiler's Location_CenterMassIntensity,
+ * MassDisplacement, Location_MaxIntensity, IntegratedIntensity).  labels and raw hold Z*Y*X values, x fastest; a 2-D map has Z = 1.
+ *   counted   a pixel counts if its id lies in [1, nid) and its value quantises under clx_region_intensity's rule: CLX_RAW_I32:
+ *             q = v, the shift ignored; CLX_RAW_F32 / _F64: q = (long long) rint(ldexp((double) v, shift)) with
+ *             |q| <= 2^62 >> L, L = bit_length(Z*Y*X).  Every other pixel is skipped in all 21 words
+ *   out [nid][21]  per id, as 64-bit words: [0] n, the counted pixels; [1] Σq modulo 2^64, two's complement (it equals
+ *             clx_region_intensity's isum for the same shift bit for bit); [2] the smallest flat index p = (z*Y + y)*X + x among
+ *             the counted pixels whose order key (clx_region_intensity's, of the raw value, not of q) equals peak_keys[id], ~0
+ *             if there is none or peak_keys is NULL: with peak_keys[id] = vkey[2*id + 1] of clx_region_intensity the first pixel in
+ *             raster order that attains the object's maximum; then nine signed 128-bit sums as (lo, hi) pairs of words, two's
+ *             complement, in the order of clx_region_moments' sum1 and sum2: [3,4] Σq·z, [5,6] Σq·y, [7,8] Σq·x, [9,10] Σq·zz,
+ *             [11,12] Σq·yy, [13,14] Σq·xx, [15,16] Σq·zy, [17,18] Σq·zx, [19,20] Σq·yx.  Every term is below 2^(62 - L) 2^(2 L) in
+ *             magnitude and a sum of fewer than 2^L of them below 2^126: it fits.  Row 0 (background) is unspecified
+ *   peak_keys [nid] or NULL
+ *   bad [1]   bit 0: a label outside [0, nid) -- never followed as an index, counts as background
+ *             bit 1: under an object id a NaN, +-Inf or |q| above the bound; that pixel is skipped.  Such values on the
+ *                    background are ignored
+ * The entry point initialises out and bad itself.  Integer adds and an integer minimum only; a 128-bit add is two 64-bit
+ * atomic adds as in clx_region_products: the same map gives the same bits in every run.  Two launches, whatever the number of
+ * objects: the initialisation, and one pass in which a block combines runs of pixels of one id and one image row in a table
+ * of 256 ids in LDS that it adds to the output once.
+ * Refused (CLX_ERR_ARG) before any launch, the outputs untouched: null pointers other than peak_keys, an unknown raw_type,
+ * nid outside [1, 2^24], a non-positive extent, Z*Y*X >= 2^32. */
+int clx_region_weighted(const int32_t* labels, const void* raw, int raw_type, int Z, int Y, int X, int nid, int shift,
+                        const unsigned long long* peak_keys, unsigned long long* out /* [nid][21] */, int32_t* bad,
+                        clx_stream stream);
+/* Intensity on every object's rim (cellulus_amd.measure.border_intensity_columns forms the columns: CellProfiler's
+ * IntegratedIntensityEdge, Mean- / Std- / Min- / MaxIntensityEdge).  A pixel of object i is a BORDER PIXEL if any of its
+ * 2*nd face neighbours is not i: another object, background, an id outside [0, nid) or the outside of the image --
+ * clx_region_perimeter's definition, in 3-D too.  nd 2 (Z must be 1; there are no z neighbours) or 3 (with Z == 1 every
+ * object pixel is a border pixel).  Labels alone decide which pixels are border pixels; only their raw values are read.
+ *   out [nid][7]  per id, as 64-bit words: [0] the border pixels (for nd == 2 clx_region_perimeter's class 0); over the
+ *             border pixels whose value quantises under clx_region_intensity's rule for `shift` (as in clx_region_weighted):
+ *             [1] their number, [2] Σq modulo 2^64, two's complement, [3] the smallest and [4] the largest order key
+ *             (clx_region_intensity's; ~0 and 0 where word 1 is 0), [5,6] Σq² as a signed 128-bit (lo, hi) pair.  Row 0
+ *             (background) is unspecified
+ *   bad [1]   bit 0: a label outside [0, nid) -- counts as background, and makes border pixels of its neighbours
+ *             bit 1: a border pixel whose value is a NaN, +-Inf or has |q| above the bound: it stays in word 0 and drops out of
+ *                    words 1 - 6.  Such values anywhere else are not looked at
+ * The entry point initialises out and bad itself; integer adds, minima and maxima only: the same map gives the same bits in
+ * every run.  Two launches: the initialisation, and one pass over the label map with a stencil of 2*nd neighbours in which a
+ * wave of 256 consecutive pixels without a border pixel reads no raw value at all.
+ * Refused (CLX_ERR_ARG) before any launch, the outputs untouched: null pointers, an unknown raw_type, nd not 2 or 3, nd == 2
+ * with Z != 1, a non-positive extent, Z*Y*X >= 2^32, nid outside [1, 2^24]. */
+int clx_region_border_intensity(const int32_t* labels, const void* raw, int raw_type, int nd, int Z, int Y, int X, int nid,
+                                int shift, unsigned long long* out /* [nid][7] */, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
