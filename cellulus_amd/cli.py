@@ -1,7 +1,8 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
 (``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]
 [--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]
-[--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity]``)."""
+[--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity]``) and the ``relate`` command
+(``python -m cellulus_amd.relate <toml> --children NAME --parents NAME [--clearance] [--tertiary NAME]``)."""
 
 import click
 import tomli
@@ -81,3 +82,19 @@ def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, te
                        texture_distance=texture_distance, radial=radial, radial_rings=radial_rings, radial_width=radial_width,
                        radial_wedges=radial_wedges, std=std, colocalization=colocalization, coloc_threshold=coloc_threshold,
                        weighted=weighted, border_intensity=border_intensity)
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
+@click.option("--children", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose objects are assigned (the nuclei)")
+@click.option("--parents", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose objects they are assigned to (the cells)")
+@click.option("--clearance", is_flag=True,
+              help="add how near every child comes to its parent's boundary: distance, position and mean squared depth")
+@click.option("--tertiary", default=None, metavar="NAME",
+              help="write the parents' maps with every pixel under a child set to 0 (the cytoplasm) into a new dataset NAME")
+def relate(config_file, children, parents, clearance, tertiary):
+    from .relate import relate_stage
+
+    relate_stage(ExperimentConfig(**_load(config_file)).inference_config, children, parents, clearance=clearance, tertiary=tertiary)

@@ -15,7 +15,7 @@
 // (open addressing, PROBES tries, then straight to global memory) which the block adds to the outputs when
 // its pixels are done: one 64-bit integer atomic per id, quantity and block.  Integer adds, min and max
 // commute, so the outputs are the same bits in every run.
-#include "region_scan.h"
+#include "pair_table.h"
 
 namespace {
 
@@ -289,54 +289,9 @@ __global__ __launch_bounds__(BLOCK) void intensity_kernel(const int* __restrict_
 // outside of the image is id 0.  A pixel owns its forward faces (+x, +y, +z; past the last column / row / slice the
 // neighbour is 0) and, in the first column / row / slice, the backward face to 0.  The output is a SET of pairs of
 // unknown size: an open-addressing table in global memory keyed by (lo << 32) | hi (never 0, as hi >= 1), filled through
-// a block-private table in LDS that is flushed once.  A lane whose pixels and forward neighbours all carry one id away
-// from the image edge has nothing to emit; a wave of such lanes skips the rest of the trip.
-
-constexpr int CSLOTS = 512;             // pairs a block keeps in LDS (power of two)
-constexpr int CPROBES = 8;
-constexpr unsigned int GPROBES = 4096;  // slots tried in the global table before the result is declared lost
-
-struct ContactsOut {
-  u64* keys;
-  u64* counts;
-  int* info;                            // [0] bit 0: label outside [0, nid); bit 2: a pair was not placed.  [1] occupied slots
-  unsigned int mask, probes;            // capacity - 1; min(capacity, GPROBES)
-};
-
-__device__ __forceinline__ u64 mix64(u64 k) {   // MurmurHash3's finaliser: ids of neighbours are close, their keys must not be
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-  return k ^ (k >> 33);
-}
-
-// n faces of `key` into the global table.  Bounded: at most o.probes slots, all inside [0, capacity); a pair that finds
-// neither its key nor an empty slot sets bit 2 and is dropped (the caller discards the table).  A stale read of a key
-// can only show 0 for a claimed slot, which the compare-and-swap corrects; a claimed key never changes.
-__device__ void pair_to_global(const ContactsOut& o, u64 key, u64 n, u64 h) {
-  unsigned int s = (unsigned int)(h >> 32) & o.mask;
-  for (unsigned int i = 0; i < o.probes; ++i) {
-    u64 k = __hip_atomic_load(&o.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == 0) {
-      k = atomicCAS(&o.keys[s], 0ull, key);
-      if (k == 0) atomicAdd(o.info + 1, 1);
-    }
-    if (k == 0 || k == key) { atomicAdd(&o.counts[s], n); return; }
-    s = (s + 1) & o.mask;
-  }
-  atomicOr(o.info, 4);
-}
-
-__device__ void add_pair(u64* lkeys, u64* lcnt, const ContactsOut& o, u64 key, unsigned int n) {
-  const u64 h = mix64(key);
-  int s = (int)(h & (CSLOTS - 1));
-  for (int i = 0; i < CPROBES; ++i) {
-    u64 k = __hip_atomic_load(&lkeys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (k == 0) k = atomicCAS(&lkeys[s], 0ull, key);
-    if (k == 0 || k == key) { atomicAdd(&lcnt[s], (u64)n); return; }
-    s = (s + 1) & (CSLOTS - 1);
-  }
-  pair_to_global(o, key, n, h);
-}
+// a block-private table in LDS that is flushed once (pair_table.h, shared with label_overlap.hip).  A lane whose pixels
+// and forward neighbours all carry one id away from the image edge has nothing to emit; a wave of such lanes skips the rest
+// of the trip.
 
 // a lane's faces in the order it meets them; equal pairs in a row (a horizontal edge gives four) become one add
 struct PairRun {
@@ -350,14 +305,6 @@ __device__ __forceinline__ void face(PairRun& r, u64* lkeys, u64* lcnt, const Co
   if (r.n) add_pair(lkeys, lcnt, o, r.key, r.n);
   r.key = key;
   r.n = 1;
-}
-
-__global__ void contacts_init(ContactsOut o, long long capacity) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 2) o.info[i] = 0;
-  if (i >= capacity) return;
-  o.keys[i] = 0;
-  o.counts[i] = 0;
 }
 
 __global__ __launch_bounds__(BLOCK) void contacts_kernel(const int* __restrict__ lab, int vec, int vec_y, int vec_z, int zfaces,
@@ -1171,8 +1118,7 @@ extern "C" int clx_region_contacts(const int32_t* labels, int nd, int Z, int Y, 
   CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_region_contacts: Z * Y * X must be below 2^32");
   const long long npix = (long long)npix128;
   hipStream_t st = (hipStream_t)stream;
-  const ContactsOut o = {keys, counts, info, (unsigned int)capacity - 1u,
-                         (unsigned int)capacity < GPROBES ? (unsigned int)capacity : GPROBES};
+  const ContactsOut o = contacts_out(keys, counts, info, capacity);
   contacts_init<<<(capacity + 255) / 256, 256, 0, st>>>(o, capacity);
   const Tiling t = tiling_for(npix);
   const int vec = ((uintptr_t)labels & 15) == 0;

@@ -1,0 +1,342 @@
+"""``relate`` stage: what connects TWO label maps of the same image -- the nuclei and the cells the pipeline segments, a
+prediction and a reference -- where the measure stage describes each map on its own.  CellProfiler's RelateObjects,
+IdentifyTertiaryObjects and MeasureObjectOverlap, which users do on the host with one mask pass per object.
+
+The device gives integers (``csrc/label_overlap.hip``): ``clx_label_overlaps``, the sparse joint histogram of the two maps as a
+set of ``(a, b, pixels)`` rows, a few per object whatever the number of objects (``label_overlaps``), and, on request,
+``clx_region_clearance``: over every child's pixels inside its parent the smallest value of the parent map's label-aware
+distance map (``clx_label_distance_sq``), where it is attained, and the map's sum.  Areas and centroids are
+``clx_region_moments``'.  The host forms the tables from them (``assign_parents``, ``relate_columns``); every float is one
+correctly rounded operation on exact integers.
+
+Definitions.  The PARENT of a child ``i`` is the object ``j > 0`` of the other map that shares the most pixels with it, the
+smallest ``j`` among equals; 0 if ``i`` lies over background only.  ``overlap`` is that number of pixels, ``fraction_inside =
+overlap / area``, ``outside`` the child's pixels over the parents' background, ``num_parents`` the distinct ``j > 0`` it
+touches, ``parent_centroid_distance`` the distance between the two centroids.  ``clearance`` is the smallest distance from a
+pixel of the child inside its parent to the nearest pixel that is not the parent's (1.0: the child touches the parent's
+boundary), ``clearance_<axis>`` the first pixel in raster order that attains it, ``depth_sq_mean`` the mean squared distance
+over those pixels.  A parent's ``num_children`` counts the children assigned to it, ``children_area`` its pixels under ANY
+child, ``tertiary_area = area - children_area`` what ``tertiary_labels`` leaves of it: the cytoplasm, cell minus nucleus.
+
+    python -m cellulus_amd.relate experiment.toml --children NAME --parents NAME [--clearance] [--tertiary NAME]
+
+writes ``relate_children_bandwidth-<b>.csv`` and ``relate_parents_bandwidth-<b>.csv`` next to the measure stage's files and,
+with ``--tertiary``, the tertiary label maps into the segmentation container.
+"""
+
+import math
+
+import numpy as np
+import torch
+
+from . import _clx
+from .measure import (_AXES, _BAD_DISTANCE, _BAD_LABEL, _INFO_FULL, DIST_INF, MAX_CAPACITY, MAX_IDS, _distance_map, _exact_div,
+                      _format, _moments, _pair_capacity, _resolve_device, _sqrt_ratio, _to_device_labels)
+
+_INFO_BAD_A, _INFO_BAD_B = 1, 2         # bits of clx_label_overlaps' info[0] (bit 2: _INFO_FULL, as clx_region_contacts')
+NO_PIXEL = (1 << 64) - 1                # clx_region_clearance's out[i][1] of an id without a counted pixel
+
+
+def _check_maps(a, b, who, names=("children", "parents")):
+    """the checks on a pair of label maps that need no device: integers, 2-D or 3-D, of one shape -> (nd, spatial)"""
+    for name, m in zip(names, (a, b)):
+        if not torch.is_tensor(m) and not isinstance(m, np.ndarray):
+            raise TypeError(f"{who}: {name} must be an array or a tensor, got {type(m).__name__}")
+        if (m.dtype.is_floating_point or m.dtype.is_complex or m.dtype == torch.bool) if torch.is_tensor(m) else m.dtype.kind not in "ui":
+            raise TypeError(f"{who}: {name} must be integers, got {m.dtype}")
+        if m.ndim not in (2, 3):
+            raise ValueError(f"{who}: {name} must be 2-D or 3-D, got {m.ndim} dimensions")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"{who}: {names[0]} has shape {tuple(a.shape)}, {names[1]} {tuple(b.shape)}")
+    return a.ndim, tuple(int(v) for v in a.shape)
+
+
+def _maps_on_device(a, b, device, who, names=("children", "parents")):
+    """-> (a, b as flat int32 device tensors, nid_a, nid_b, nd, spatial) after the host checks"""
+    nd, spatial = _check_maps(a, b, who, names)
+    on_device = [m for m in (a, b) if torch.is_tensor(m) and m.is_cuda]
+    device = _resolve_device(on_device[0] if on_device else a, device)
+    la = _to_device_labels(a, device, who).reshape(-1)
+    lb = _to_device_labels(b, device, who).reshape(-1)
+    _clx.require_device(la, names[0])
+    _clx.require_device(lb, names[1])
+    nid_a = int(la.max().item()) + 1 if la.numel() else 1
+    nid_b = int(lb.max().item()) + 1 if lb.numel() else 1
+    return la, lb, nid_a, nid_b, nd, spatial
+
+
+def _overlaps(la, lb, nid_a, nid_b, who):
+    """clx_label_overlaps, repeated with twice the table while it reports a pair it could not place -> (a, b, pixels) int64,
+    sorted by (a, b)"""
+    device = la.device
+    npix = la.numel()
+    if npix == 0 or (nid_a == 1 and nid_b == 1):             # no pixel, or background only in both maps: no pair
+        return tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+    # an object overlaps one or two of the other map and the background: a few pairs per object, never more than pixels
+    capacity = _pair_capacity(min(nid_a - 1 + nid_b - 1, npix))
+    while True:
+        if capacity > MAX_CAPACITY:
+            raise ValueError(f"{who}: more id pairs than a table of {MAX_CAPACITY} slots holds")
+        keys = torch.empty(capacity, dtype=torch.int64, device=device)
+        counts = torch.empty(capacity, dtype=torch.int64, device=device)
+        info = torch.empty(2, dtype=torch.int32, device=device)
+        _clx.call("clx_label_overlaps", _clx.ptr(la), _clx.ptr(lb), npix, nid_a, nid_b, capacity, _clx.ptr(keys), _clx.ptr(counts),
+                  _clx.ptr(info), _clx.stream_ptr(device))
+        flags, used = info.tolist()
+        if flags & (_INFO_BAD_A | _INFO_BAD_B):
+            raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
+        if not flags & _INFO_FULL:
+            break
+        capacity *= 2
+    slot = torch.nonzero(keys).reshape(-1)
+    assert slot.numel() == used
+    k = keys[slot].cpu().numpy()
+    order = np.argsort(k, kind="stable")                     # keys are (a << 32) | b with a < 2^24: the (a, b) order
+    k = k[order]
+    return k >> 32, k & 0xFFFFFFFF, counts[slot].cpu().numpy()[order]
+
+
+def label_overlaps(a, b, device=None):
+    """The sparse joint histogram of two label maps ``a`` and ``b`` (2-D or 3-D integers of one shape, arrays or device
+    tensors; the same types and range as ``region_table``): ``(ids_a, ids_b, pixels)`` int64 arrays, one row per pair
+    ``(a[p], b[p]) != (0, 0)`` that occurs, sorted by ``(a, b)``.  Rows with ``ids_b == 0`` are an object's pixels over the
+    other map's background; an object's pixel count is the sum of its rows.  Runs on a HIP device; there is no CPU path."""
+    la, lb, nid_a, nid_b, _, _ = _maps_on_device(a, b, device, "label_overlaps", ("a", "b"))
+    return _overlaps(la, lb, nid_a, nid_b, "label_overlaps")
+
+
+def _rows(ids_a, ids_b, pixels, who):
+    rows = [np.asarray(v).astype(np.int64).reshape(-1) for v in (ids_a, ids_b, pixels)]
+    if not len(rows[0]) == len(rows[1]) == len(rows[2]):
+        raise ValueError(f"{who}: ids_a, ids_b and pixels must have one length, got {[len(r) for r in rows]}")
+    if len(rows[0]) and (rows[0].min() < 0 or rows[1].min() < 0 or rows[2].min() < 1):
+        raise ValueError(f"{who}: ids must be >= 0 and pixels >= 1")
+    return rows
+
+
+def assign_parents(ids_a, ids_b, pixels):
+    """From ``label_overlaps``' rows: for every id of ``a`` (every ``ids_a > 0`` that occurs) the id ``b > 0`` it shares the
+    most pixels with, the smallest such id among equals, or 0 if it lies over background only.  Returns ``(label, parent,
+    overlap)`` int64 arrays sorted by label; ``overlap`` is the number of shared pixels (0 without a parent).  Host only."""
+    a, b, n = _rows(ids_a, ids_b, pixels, "assign_parents")
+    label = np.unique(a[a > 0])
+    parent = np.zeros(len(label), dtype=np.int64)
+    overlap = np.zeros(len(label), dtype=np.int64)
+    both = (a > 0) & (b > 0)
+    a, b, n = a[both], b[both], n[both]
+    order = np.lexsort((b, -n, a))                           # per a: most pixels first, the smaller b among equals
+    a, b, n = a[order], b[order], n[order]
+    first = np.flatnonzero(np.r_[True, a[1:] != a[:-1]]) if len(a) else np.zeros(0, dtype=np.int64)
+    at = np.searchsorted(label, a[first])
+    parent[at] = b[first]
+    overlap[at] = n[first]
+    return label, parent, overlap
+
+
+def _moments_arg(m, who, name):
+    label, area, sum1 = m
+    label = np.asarray(label).astype(np.int64).reshape(-1)
+    area = np.asarray(area).astype(np.int64).reshape(-1)
+    sum1 = np.asarray(sum1).reshape(-1, 3)
+    if not len(label) == len(area) == len(sum1):
+        raise ValueError(f"{who}: {name} must be (label (n), area (n), sum1 (n, 3)) of one n")
+    if len(label) and (np.any(np.diff(label) <= 0) or label[0] < 1 or area.min() < 1):
+        raise ValueError(f"{who}: {name} needs increasing labels >= 1 with areas >= 1")
+    return label, area, [[int(v) for v in r] for r in sum1]
+
+
+def relate_columns(ids_a, ids_b, pixels, child_moments, parent_moments, shape, clearance=None):
+    """The two tables of ``relate`` from integers.  ``ids_a, ids_b, pixels``: ``label_overlaps``' rows of (children, parents);
+    ``child_moments`` / ``parent_moments``: ``(label (n), area (n), sum1 (n, 3) = Σz Σy Σx)`` of the objects present in either
+    map, as ``clx_region_moments`` gives them; ``shape`` the maps' 2 or 3 extents; ``clearance``: ``clx_region_clearance``'s
+    rows ``(n, 3)`` of the children, or None.  Returns ``(child_table, parent_table)``, dicts of columns:
+
+    child: ``label``, ``area``, ``parent`` (0: none), ``overlap``, ``fraction_inside``, ``outside``, ``num_parents``,
+    ``parent_centroid_distance`` (NaN without a parent) and, with ``clearance``, ``clearance`` (NaN without a pixel inside a
+    parent, inf where the parent fills a map without an edge to measure to), ``clearance_z/_y/_x`` (2-D: y and x; int64, -1
+    without such a pixel) and ``depth_sq_mean``.
+    parent: ``label``, ``area``, ``num_children``, ``children_area``, ``children_fraction``, ``tertiary_area``.
+    Host only; the module's docstring has the definitions."""
+    who = "relate_columns"
+    nd = len(shape)
+    if nd not in (2, 3):
+        raise ValueError(f"{who}: shape must have 2 or 3 extents, got {nd}")
+    a, b, n = _rows(ids_a, ids_b, pixels, who)
+    clabel, carea, csum = _moments_arg(child_moments, who, "child_moments")
+    plabel, parea, psum = _moments_arg(parent_moments, who, "parent_moments")
+    nc, npar = len(clabel), len(plabel)
+    # the pixel counts are the row and column sums of the table: the rows must belong to these moments
+    rows_a, rows_b = a[a > 0], b[b > 0]
+    if (not np.array_equal(np.unique(rows_a), clabel) or not np.array_equal(np.unique(rows_b), plabel)
+            or not np.array_equal(np.bincount(np.searchsorted(clabel, rows_a), n[a > 0], nc).astype(np.int64), carea)
+            or not np.array_equal(np.bincount(np.searchsorted(plabel, rows_b), n[b > 0], npar).astype(np.int64), parea)):
+        raise ValueError(f"{who}: the overlap rows and the moments describe different maps")
+    label, parent, overlap = assign_parents(a, b, n)
+    at = np.searchsorted(clabel, a[a > 0])
+    outside = np.bincount(at[b[a > 0] == 0], n[(a > 0) & (b == 0)], nc).astype(np.int64)
+    num_parents = np.bincount(at[b[a > 0] > 0], minlength=nc).astype(np.int64)
+    distance = np.full(nc, math.nan)
+    where = np.searchsorted(plabel, parent)
+    for i in np.flatnonzero(parent > 0):
+        na, nb = int(carea[i]), int(parea[where[i]])
+        num = sum((sa * nb - sb * na) ** 2 for sa, sb in zip(csum[i][3 - nd:], psum[where[i]][3 - nd:]))
+        distance[i] = _sqrt_ratio(num, (na * nb) ** 2)
+    child = {"label": clabel, "area": carea, "parent": parent, "overlap": overlap,
+             "fraction_inside": _exact_div(overlap.astype(object), carea.astype(object)), "outside": outside,
+             "num_parents": num_parents, "parent_centroid_distance": distance}
+    if clearance is not None:
+        rows = np.asarray(clearance).reshape(-1, 3)
+        if len(rows) != nc:
+            raise ValueError(f"{who}: clearance has {len(rows)} rows for {nc} children")
+        rows = [[int(v) & NO_PIXEL for v in r] for r in rows]                 # int64 views of the device words included
+        some = [r[0] > 0 for r in rows]
+        if any(s != (r[1] != NO_PIXEL) for s, r in zip(some, rows)) or any(r[0] != o for r, o in zip(rows, overlap)):
+            raise ValueError(f"{who}: the clearance rows and the overlap rows describe different maps")
+        d2 = [r[1] >> 32 for r in rows]
+        inf = [s and d >= DIST_INF for s, d in zip(some, d2)]
+        child["clearance"] = np.array([math.nan if not s else math.inf if i else _sqrt_ratio(d, 1) for s, d, i in zip(some, d2, inf)],
+                                      dtype=np.float64)
+        index = np.array([r[1] & 0xFFFFFFFF if s else 0 for r, s in zip(rows, some)], dtype=np.int64)
+        if len(index) and index.max() >= int(np.prod(shape)):
+            raise ValueError(f"{who}: a clearance row points outside a map of shape {tuple(shape)}")
+        centre = np.unravel_index(index, tuple(int(v) for v in shape)) if nc else (np.zeros(0, dtype=np.int64),) * nd
+        for axis, c in zip(_AXES[3 - nd:], centre):
+            child[f"clearance_{axis}"] = np.where(some, np.asarray(c, dtype=np.int64), -1) if nc else np.zeros(0, dtype=np.int64)
+        child["depth_sq_mean"] = np.array([math.nan if not s else math.inf if i else r[2] / r[0] for r, s, i in zip(rows, some, inf)],
+                                          dtype=np.float64)
+    inside = (a > 0) & (b > 0)
+    children_area = np.bincount(np.searchsorted(plabel, b[inside]), n[inside], npar).astype(np.int64)
+    table = {"label": plabel, "area": parea,
+             "num_children": np.bincount(where[parent > 0], minlength=npar).astype(np.int64), "children_area": children_area,
+             "children_fraction": _exact_div(children_area.astype(object), parea.astype(object)),
+             "tertiary_area": parea - children_area}
+    return child, table
+
+
+def _present_moments(lab, nd, spatial, nid, who):
+    """(label, area, sum1) of the objects present in `lab`, from one clx_region_moments call"""
+    if lab.numel() == 0 or nid == 1:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros((0, 3), dtype=np.uint64)
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    area_d, _, sum1_d, _ = _moments(lab, Z, Y, X, nid, who)
+    area = area_d.cpu().numpy()
+    area[0] = 0
+    present = np.flatnonzero(area > 0)
+    return present.astype(np.int64), area[present], sum1_d.cpu().numpy().view(np.uint64)[present]
+
+
+def _clearance_rows(la, lb, nd, spatial, nid_a, label, parent, edge, who):
+    """clx_label_distance_sq of the parents' map, then clx_region_clearance -> int64 (n, 3) rows of the children `label`"""
+    device = la.device
+    Z, Y, X = (1,) * (3 - nd) + spatial
+    dist = _distance_map(lb, nd, Z, Y, X, edge)
+    table = np.zeros(nid_a, dtype=np.int32)
+    table[label] = parent
+    parent_d = torch.from_numpy(table).to(device)
+    out = torch.empty((nid_a, 3), dtype=torch.int64, device=device)
+    bad = torch.empty(1, dtype=torch.int32, device=device)
+    _clx.call("clx_region_clearance", _clx.ptr(la), _clx.ptr(lb), _clx.ptr(dist), _clx.ptr(parent_d), la.numel(), nid_a, _clx.ptr(out),
+              _clx.ptr(bad), _clx.stream_ptr(device))
+    flags = int(bad.item())
+    if flags & _BAD_LABEL:
+        raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
+    if flags & _BAD_DISTANCE:
+        raise ValueError(f"{who}: the distance map changed under the measurement")
+    return out.cpu().numpy()[label]
+
+
+def relate(children, parents, device=None, clearance=False, edge=False):
+    """``(child_table, parent_table)`` of two label maps of one image (2-D or 3-D integers of one shape, arrays or device
+    tensors; the same types and range as ``region_table``): which parent every child lies in and how much of it, how many
+    children every parent holds and what they leave of it; ``relate_columns`` lists the columns, the module's docstring has
+    the definitions.  ``clearance=True`` adds how near every child comes to its parent's boundary, from the label-aware
+    distance map of ``parents``; ``edge`` has ``label_distance_sq``'s meaning there (True: the image edge counts as boundary).
+    Runs on a HIP device; there is no CPU path."""
+    la, lb, nid_a, nid_b, nd, spatial = _maps_on_device(children, parents, device, "relate")
+    a, b, n = _overlaps(la, lb, nid_a, nid_b, "relate")
+    child_moments = _present_moments(la, nd, spatial, nid_a, "relate")
+    parent_moments = _present_moments(lb, nd, spatial, nid_b, "relate")
+    rows = None
+    if clearance:
+        label, parent, _ = assign_parents(a, b, n)
+        rows = (_clearance_rows(la, lb, nd, spatial, nid_a, label, parent, edge, "relate") if len(label)
+                else np.zeros((0, 3), dtype=np.int64))
+    return relate_columns(a, b, n, child_moments, parent_moments, spatial, rows)
+
+
+def tertiary_labels(children, parents):
+    """The parents' map with every pixel under a child set to 0: the cytoplasm when the parents are cells and the children their
+    nuclei.  Arrays or tensors, 2-D or 3-D integers of one shape; the result has the type, dtype and device of ``parents``.
+    ``region_table`` of it measures the tertiary objects with everything the measure stage has."""
+    _check_maps(children, parents, "tertiary_labels")
+    if torch.is_tensor(parents):
+        under = torch.as_tensor(children, device=parents.device) > 0
+        return torch.where(under, torch.zeros_like(parents), parents)
+    return np.where(children > 0, np.zeros((), parents.dtype), parents)
+
+
+def _write_csv(path, header, lines):
+    with open(path, "w") as out:
+        out.write(",".join(header or ["sample"]) + "\n")
+        for line in lines:
+            out.write(line + "\n")
+
+
+def relate_stage(inference_config, children, parents, clearance=False, tertiary=None) -> None:
+    """For every bandwidth: ``relate``'s tables of all samples, with ``children`` and ``parents`` the names of two label
+    datasets ``[sample, bandwidth, ...]`` in ``segmentation_dataset_config.container_path`` (``segment()``'s output under the
+    two ``post_processing`` settings, say), as ``relate_children_bandwidth-<b>.csv`` and ``relate_parents_bandwidth-<b>.csv`` in
+    the working directory -- a header line, then ``sample`` and the table's columns, floats as ``%.17g``.  ``clearance=True``
+    adds the clearance columns (``edge=False``).  ``tertiary=NAME`` writes ``tertiary_labels`` of every sample and bandwidth
+    into a new uint16 dataset NAME of that container.  Rank 0 works alone under torch.distributed."""
+    from . import parallel
+    from .datasets.meta_data import DatasetMetaData
+    from .train import _require_hip_device
+    from .utils import zarr_io
+
+    for name, value in (("children", children), ("parents", parents)):
+        if not isinstance(value, str) or not value:
+            raise ValueError(f"relate_stage: {name} must be the name of a dataset, got {value!r}")
+    if children == parents:
+        raise ValueError(f"relate_stage: children and parents are the same dataset {children!r}")
+    if tertiary is not None and (not isinstance(tertiary, str) or not tertiary or tertiary in (children, parents)):
+        raise ValueError(f"relate_stage: tertiary must name a new dataset other than children and parents, got {tertiary!r}")
+    if parallel.rank() != 0:
+        return
+    meta = DatasetMetaData.from_dataset_config(inference_config.dataset_config)
+    nd = meta.num_spatial_dims
+    device = _require_hip_device(inference_config.device)
+    if parallel.world_size() > 1:
+        device = torch.device("cuda", torch.cuda.current_device())
+    f = zarr_io.open(inference_config.segmentation_dataset_config.container_path, "a" if tertiary else "r")
+    for name in (children, parents):
+        if name not in f:
+            raise ValueError(f"relate_stage: no dataset {name!r} in {inference_config.segmentation_dataset_config.container_path}")
+    ds_children, ds_parents = f[children], f[parents]
+    ds_tertiary = None
+    if tertiary:
+        ds_tertiary = f.create_dataset(tertiary, shape=(meta.num_samples, inference_config.num_bandwidths, *meta.spatial_array),
+                                       dtype=np.uint16)
+        ds_tertiary.attrs["axis_names"] = ["s", "c"] + ["t", "z", "y", "x"][-nd:]
+        ds_tertiary.attrs["resolution"] = (1,) * nd
+        ds_tertiary.attrs["offset"] = (0,) * nd
+    for bandwidth in range(inference_config.num_bandwidths):
+        headers, lines = [None, None], ([], [])
+        for sample in range(meta.num_samples):
+            a = ds_children[sample, bandwidth].astype(np.int32)
+            b = ds_parents[sample, bandwidth].astype(np.int32)
+            for k, table in enumerate(relate(a, b, device, clearance=clearance)):
+                headers[k] = headers[k] or ["sample"] + list(table)
+                columns = list(table.values())
+                for i in range(len(table["label"])):
+                    lines[k].append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
+            if ds_tertiary is not None:
+                ds_tertiary[sample, bandwidth] = tertiary_labels(a, b).astype(np.uint16)
+        _write_csv(f"relate_children_bandwidth-{bandwidth}.csv", headers[0], lines[0])
+        _write_csv(f"relate_parents_bandwidth-{bandwidth}.csv", headers[1], lines[1])
+
+
+if __name__ == "__main__":
+    from .cli import relate as _command
+
+    _command()

@@ -1260,6 +1260,47 @@ int clx_region_border_intensity(const int32_t* labels, const void* raw, int raw_
                                 int shift, unsigned long long* out /* [nid][7] */, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* "relate" stage: two label maps of one image (label_overlap.hip)           */
+/* ------------------------------------------------------------------------ */
+/* Overlaps: the sparse joint histogram of two label maps a and b of npix pixels each -- which object of b every object of a
+ * lies in and with how many pixels, where clx_joint_histogram fills a dense #a x #b table and needs ids below 2^16.
+ *   pair      every pixel p with (a[p], b[p]) != (0, 0) counts once for the key ((u64) a[p] << 32) | b[p]; no key is 0.
+ *             (i, 0): pixels of i over b's background; (0, j): pixels of j over a's.  The pixel counts |A_i| and |B_j| are the
+ *             row and column sums of the table
+ *   labels    a label outside [0, nid_a) resp. [0, nid_b) counts as 0, is never followed as an index and sets bit 0 (map a)
+ *             resp. bit 1 (map b) of info[0]
+ * Output: clx_region_contacts' open-addressing table of `capacity` slots (a power of two in [1024, 2^28]), under the same
+ * contract.
+ *   keys   [capacity]  (a << 32) | b; 0: empty slot
+ *   counts [capacity]  pixels of that pair
+ *   info   [2]         [0] bit 0 / bit 1: a label of a / b out of range; bit 2: a pair could not be placed -- the table is to be
+ *                      discarded and the call repeated with a larger capacity.  [1] occupied slots (<= capacity)
+ * The entry point initialises keys, counts and info itself.  The slot order is unspecified; the SET of (key, count) is
+ * determined by the maps: integer adds only.  Either the set is exact or bit 2 is set.  An insertion probes at most
+ * min(capacity, 4096) consecutive slots (modulo capacity) and then gives up with bit 2: it never spins and writes only
+ * keys[0, capacity) and counts[0, capacity).  A caller repeats while bit 2 is set.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, npix outside [1, 2^32), nid_a or nid_b outside [1, 2^24], capacity
+ * not a power of two in [1024, 2^28]. */
+int clx_label_overlaps(const int32_t* a, const int32_t* b, long long npix, int nid_a, int nid_b, int capacity,
+                       unsigned long long* keys, unsigned long long* counts, int32_t* info, clx_stream stream);
+/* Clearance: how near every object of a comes to the boundary of the object of b it was assigned to (a nucleus to its cell's
+ * membrane).  a, b and dist_sq: npix values each; dist_sq is clx_label_distance_sq's map of b.
+ *   parent [nid_a]  for every id of a the id of b it belongs to, or 0 (cellulus_amd.relate.assign_parents); parent[0] is not read
+ *   counted   a pixel p with i = a[p] in [1, nid_a), parent[i] > 0 and b[p] == parent[i].  Values of b and parent are only
+ *             compared, never followed as an index
+ *   out [nid_a][3], over the counted pixels of i:
+ *             [0] their number
+ *             [1] the smallest ((u64) dist_sq[p] << 32) | p: the smallest distance and the first pixel in raster order that
+ *                 attains it; all ones if there is none.  sqrt(out[i][1] >> 32) is the clearance; 1: i touches the boundary
+ *             [2] the sum of dist_sq
+ *   bad [1]   bit 0: a label of a outside [0, nid_a) -- never followed as an index, that pixel is skipped
+ *             bit 1: a dist_sq outside [0, CLX_DIST_INF] under a counted pixel; that pixel is skipped
+ * The entry point initialises out and bad itself.  Integer minima and adds only: the same bits in every run.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, npix outside [1, 2^32), nid_a outside [1, 2^24]. */
+int clx_region_clearance(const int32_t* a, const int32_t* b, const int32_t* dist_sq, const int32_t* parent,
+                         long long npix, int nid_a, unsigned long long* out, int32_t* bad, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
