@@ -30,10 +30,10 @@ import numpy as np
 import torch
 
 from . import _clx
-from .measure import (_AXES, _BAD_DISTANCE, _BAD_LABEL, _INFO_FULL, DIST_INF, MAX_CAPACITY, MAX_IDS, _distance_map, _exact_div,
-                      _format, _moments, _pair_capacity, _resolve_device, _sqrt_ratio, _to_device_labels)
+from .measure import (DISTANCE_CHANGED, FLAGS, LABELS_OUT_OF_RANGE, _call, _distance_map, _pair_capacity, _pair_table,
+                      _resolve_device, _Scene, _to_device_labels)
+from .measure_columns import _AXES, DIST_INF, _exact_div, _format, _sqrt_ratio
 
-_INFO_BAD_A, _INFO_BAD_B = 1, 2         # bits of clx_label_overlaps' info[0] (bit 2: _INFO_FULL, as clx_region_contacts')
 NO_PIXEL = (1 << 64) - 1                # clx_region_clearance's out[i][1] of an id without a counted pixel
 
 
@@ -51,49 +51,26 @@ def _check_maps(a, b, who, names=("children", "parents")):
     return a.ndim, tuple(int(v) for v in a.shape)
 
 
-def _maps_on_device(a, b, device, who, names=("children", "parents")):
-    """-> (a, b as flat int32 device tensors, nid_a, nid_b, nd, spatial) after the host checks"""
+def _scenes(a, b, device, who, names=("children", "parents")):
+    """-> the measure stage's scenes of the two maps after the host checks, their moments not taken yet"""
     nd, spatial = _check_maps(a, b, who, names)
     on_device = [m for m in (a, b) if torch.is_tensor(m) and m.is_cuda]
     device = _resolve_device(on_device[0] if on_device else a, device)
-    la = _to_device_labels(a, device, who).reshape(-1)
-    lb = _to_device_labels(b, device, who).reshape(-1)
+    la, lb = _to_device_labels(a, device, who), _to_device_labels(b, device, who)
     _clx.require_device(la, names[0])
     _clx.require_device(lb, names[1])
-    nid_a = int(la.max().item()) + 1 if la.numel() else 1
-    nid_b = int(lb.max().item()) + 1 if lb.numel() else 1
-    return la, lb, nid_a, nid_b, nd, spatial
+    return tuple(_Scene(who, m, device, nd, spatial, int(m.max().item()) + 1 if m.numel() else 1) for m in (la, lb))
 
 
-def _overlaps(la, lb, nid_a, nid_b, who):
-    """clx_label_overlaps, repeated with twice the table while it reports a pair it could not place -> (a, b, pixels) int64,
-    sorted by (a, b)"""
-    device = la.device
-    npix = la.numel()
-    if npix == 0 or (nid_a == 1 and nid_b == 1):             # no pixel, or background only in both maps: no pair
+def _overlaps(sa, sb):
+    """clx_label_overlaps of two scenes -> (a, b, pixels) int64, sorted by (a, b)"""
+    npix = sa.lab.numel()
+    if npix == 0 or (sa.nid == 1 and sb.nid == 1):           # no pixel, or background only in both maps: no pair
         return tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
     # an object overlaps one or two of the other map and the background: a few pairs per object, never more than pixels
-    capacity = _pair_capacity(min(nid_a - 1 + nid_b - 1, npix))
-    while True:
-        if capacity > MAX_CAPACITY:
-            raise ValueError(f"{who}: more id pairs than a table of {MAX_CAPACITY} slots holds")
-        keys = torch.empty(capacity, dtype=torch.int64, device=device)
-        counts = torch.empty(capacity, dtype=torch.int64, device=device)
-        info = torch.empty(2, dtype=torch.int32, device=device)
-        _clx.call("clx_label_overlaps", _clx.ptr(la), _clx.ptr(lb), npix, nid_a, nid_b, capacity, _clx.ptr(keys), _clx.ptr(counts),
-                  _clx.ptr(info), _clx.stream_ptr(device))
-        flags, used = info.tolist()
-        if flags & (_INFO_BAD_A | _INFO_BAD_B):
-            raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
-        if not flags & _INFO_FULL:
-            break
-        capacity *= 2
-    slot = torch.nonzero(keys).reshape(-1)
-    assert slot.numel() == used
-    k = keys[slot].cpu().numpy()
-    order = np.argsort(k, kind="stable")                     # keys are (a << 32) | b with a < 2^24: the (a, b) order
-    k = k[order]
-    return k >> 32, k & 0xFFFFFFFF, counts[slot].cpu().numpy()[order]
+    capacity = _pair_capacity(min(sa.nid - 1 + sb.nid - 1, npix))
+    return _pair_table(sa.device, sa.who, "clx_label_overlaps", {1 | 2: LABELS_OUT_OF_RANGE}, capacity, sa.lab, sb.lab, npix, sa.nid,
+                       sb.nid)
 
 
 def label_overlaps(a, b, device=None):
@@ -101,8 +78,7 @@ def label_overlaps(a, b, device=None):
     tensors; the same types and range as ``region_table``): ``(ids_a, ids_b, pixels)`` int64 arrays, one row per pair
     ``(a[p], b[p]) != (0, 0)`` that occurs, sorted by ``(a, b)``.  Rows with ``ids_b == 0`` are an object's pixels over the
     other map's background; an object's pixel count is the sum of its rows.  Runs on a HIP device; there is no CPU path."""
-    la, lb, nid_a, nid_b, _, _ = _maps_on_device(a, b, device, "label_overlaps", ("a", "b"))
-    return _overlaps(la, lb, nid_a, nid_b, "label_overlaps")
+    return _overlaps(*_scenes(a, b, device, "label_overlaps", ("a", "b")))
 
 
 def _rows(ids_a, ids_b, pixels, who):
@@ -213,35 +189,20 @@ def relate_columns(ids_a, ids_b, pixels, child_moments, parent_moments, shape, c
     return child, table
 
 
-def _present_moments(lab, nd, spatial, nid, who):
-    """(label, area, sum1) of the objects present in `lab`, from one clx_region_moments call"""
-    if lab.numel() == 0 or nid == 1:
-        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros((0, 3), dtype=np.uint64)
-    Z, Y, X = (1,) * (3 - nd) + spatial
-    area_d, _, sum1_d, _ = _moments(lab, Z, Y, X, nid, who)
-    area = area_d.cpu().numpy()
-    area[0] = 0
-    present = np.flatnonzero(area > 0)
-    return present.astype(np.int64), area[present], sum1_d.cpu().numpy().view(np.uint64)[present]
+def _present_moments(scene):
+    """(label, area, sum1) of the objects present in the scene's map, from one clx_region_moments call"""
+    scene.measured()
+    return scene.present.astype(np.int64), scene.area[scene.present], scene.sum1
 
 
-def _clearance_rows(la, lb, nd, spatial, nid_a, label, parent, edge, who):
+def _clearance_rows(sa, sb, label, parent, edge):
     """clx_label_distance_sq of the parents' map, then clx_region_clearance -> int64 (n, 3) rows of the children `label`"""
-    device = la.device
-    Z, Y, X = (1,) * (3 - nd) + spatial
-    dist = _distance_map(lb, nd, Z, Y, X, edge)
-    table = np.zeros(nid_a, dtype=np.int32)
+    dist = _distance_map(sb, edge)
+    table = np.zeros(sa.nid, dtype=np.int32)
     table[label] = parent
-    parent_d = torch.from_numpy(table).to(device)
-    out = torch.empty((nid_a, 3), dtype=torch.int64, device=device)
-    bad = torch.empty(1, dtype=torch.int32, device=device)
-    _clx.call("clx_region_clearance", _clx.ptr(la), _clx.ptr(lb), _clx.ptr(dist), _clx.ptr(parent_d), la.numel(), nid_a, _clx.ptr(out),
-              _clx.ptr(bad), _clx.stream_ptr(device))
-    flags = int(bad.item())
-    if flags & _BAD_LABEL:
-        raise ValueError(f"{who}: label ids must lie in [0, {MAX_IDS})")
-    if flags & _BAD_DISTANCE:
-        raise ValueError(f"{who}: the distance map changed under the measurement")
+    out = sa.ids(3)
+    _call(sa.device, sa.who, "clx_region_clearance", {1: LABELS_OUT_OF_RANGE, 2: DISTANCE_CHANGED}, sa.lab, sb.lab, dist,
+          torch.from_numpy(table).to(sa.device), sa.lab.numel(), sa.nid, out, FLAGS)
     return out.cpu().numpy()[label]
 
 
@@ -252,16 +213,14 @@ def relate(children, parents, device=None, clearance=False, edge=False):
     the definitions.  ``clearance=True`` adds how near every child comes to its parent's boundary, from the label-aware
     distance map of ``parents``; ``edge`` has ``label_distance_sq``'s meaning there (True: the image edge counts as boundary).
     Runs on a HIP device; there is no CPU path."""
-    la, lb, nid_a, nid_b, nd, spatial = _maps_on_device(children, parents, device, "relate")
-    a, b, n = _overlaps(la, lb, nid_a, nid_b, "relate")
-    child_moments = _present_moments(la, nd, spatial, nid_a, "relate")
-    parent_moments = _present_moments(lb, nd, spatial, nid_b, "relate")
+    sa, sb = _scenes(children, parents, device, "relate")
+    a, b, n = _overlaps(sa, sb)
+    child_moments, parent_moments = _present_moments(sa), _present_moments(sb)
     rows = None
     if clearance:
         label, parent, _ = assign_parents(a, b, n)
-        rows = (_clearance_rows(la, lb, nd, spatial, nid_a, label, parent, edge, "relate") if len(label)
-                else np.zeros((0, 3), dtype=np.int64))
-    return relate_columns(a, b, n, child_moments, parent_moments, spatial, rows)
+        rows = _clearance_rows(sa, sb, label, parent, edge) if len(label) else np.zeros((0, 3), dtype=np.int64)
+    return relate_columns(a, b, n, child_moments, parent_moments, sa.spatial, rows)
 
 
 def tertiary_labels(children, parents):

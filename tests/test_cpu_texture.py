@@ -241,11 +241,11 @@ def test_two_pixel_object():
 
 
 def test_python_int_route_agrees_with_int64(monkeypatch):
-    from cellulus_amd import measure
+    from cellulus_amd import measure, measure_columns
 
     _, counts = fixture_counts("2d", 8, 1)
     a = measure.texture_columns(counts, 2)
-    monkeypatch.setattr(measure, "_TEXTURE_INT64_MAX_T", 0)          # every numerator as Python ints
+    monkeypatch.setattr(measure_columns, "_TEXTURE_INT64_MAX_T", 0)          # every numerator as Python ints
     b = measure.texture_columns(counts, 2)
     assert all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
     # counts whose numerators do not fit int64: 2N = 2^31 in one cell pair

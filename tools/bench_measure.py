@@ -17,7 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cellulus_amd import _clx  # noqa: E402
-from cellulus_amd.measure import intensity_shift  # noqa: E402
+from cellulus_amd.measure_columns import intensity_shift  # noqa: E402
 
 PEAK_TBS = 8.0
 dev = torch.device("cuda:0")

@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_measure import dev, disc_map, time_legs  # noqa: E402
 from cellulus_amd import _clx  # noqa: E402
-from cellulus_amd.measure import intensity_shift, quantile_ranks  # noqa: E402
+from cellulus_amd.measure_columns import intensity_shift, quantile_ranks  # noqa: E402
 from cellulus_amd.segment import _RAW_F32, _RAW_I32, _decode_keys  # noqa: E402
 
 QS = (0.25, 0.5, 0.75)

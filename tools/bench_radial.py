@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from bench_inscribed import touching_map  # noqa: E402
 from bench_measure import dev, disc_map, time_legs  # noqa: E402
 from cellulus_amd import _clx  # noqa: E402
-from cellulus_amd.measure import intensity_shift  # noqa: E402
+from cellulus_amd.measure_columns import intensity_shift  # noqa: E402
 from radial_ref import ref_radial  # noqa: E402
 
 _RAW_F32 = 0

@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_inscribed import touching_map  # noqa: E402
 from bench_measure import dev, disc_map, time_legs  # noqa: E402
 from cellulus_amd import _clx  # noqa: E402
-from cellulus_amd.measure import _distance_map, _pair_capacity  # noqa: E402
+from cellulus_amd.measure import _pair_capacity, label_distance_sq  # noqa: E402
 from cellulus_amd.relate import assign_parents  # noqa: E402
 
 OVERLAPS, CLEARANCE = "clx_label_overlaps", "clx_region_clearance"
@@ -107,7 +107,7 @@ def bench(name, nuclei_h, cells_h, nobj, rounds, emit):
     table = np.zeros(nid, dtype=np.int32)
     table[label] = parent
     parent_d = torch.from_numpy(table).to(dev)
-    dist = _distance_map(b, 2, 1, size, size, False)
+    dist = label_distance_sq(b.reshape(size, size)).reshape(-1)
 
     def clearance(a=a, b=b, dist=dist):
         _clx.call(CLEARANCE, _clx.ptr(a), _clx.ptr(b), _clx.ptr(dist), _clx.ptr(parent_d), npix, nid, _clx.ptr(out), _clx.ptr(bad), st)

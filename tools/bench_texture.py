@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from bench_measure import dev, disc_map, time_legs  # noqa: E402
 from cellulus_amd import _clx  # noqa: E402
-from cellulus_amd.measure import intensity_shift  # noqa: E402
+from cellulus_amd.measure_columns import intensity_shift  # noqa: E402
 from cellulus_amd.segment import _RAW_F32  # noqa: E402
 from texture_ref import ref_cooccurrence  # noqa: E402
 
