@@ -101,13 +101,6 @@ __device__ void add_inscribed(int* keys, u64* ssum, u64* smax, u64* __restrict__
   }
 }
 
-__global__ void inscribed_init(u64* __restrict__ out, int* __restrict__ bad, int nid) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) *bad = 0;
-  if (i >= nid) return;
-  out[(size_t)i * 3] = 0; out[(size_t)i * 3 + 1] = 0; out[(size_t)i * 3 + 2] = 0;
-}
-
 __global__ __launch_bounds__(BLOCK) void inscribed_kernel(const int* __restrict__ lab, const int* __restrict__ dist,
                                                           int vec_lab, int vec_dist, long long npix, int nid, long long ntiles,
                                                           long long tiles_per_block, u64* __restrict__ out,
@@ -118,41 +111,28 @@ __global__ __launch_bounds__(BLOCK) void inscribed_kernel(const int* __restrict_
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * tiles_per_block;
-  const long long t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
+  const Tiles tiles = block_tiles(ntiles, tiles_per_block);
   int any_bad = 0;
-  for (long long t = t0; t < t1; ++t) {
-    const long long p0 = t * TILE + (long long)threadIdx.x * PPL;
+  for (long long t = tiles.t0; t < tiles.t1; ++t) {
+    const long long p0 = lane_pixel(t);
     int l[PPL], dv[PPL];
     load_labels(lab, vec_lab != 0, p0, npix, l);
     if (clamp_labels(l, nid)) any_bad |= 1;
     load_labels(dist, vec_dist != 0, p0, npix, dv);       // the same 4-pixel read; past the end: 0
     u64 key[PPL];
-    u64 s = 0, kmax = 0;
+    SumKey<true> v = {0, 0};                              // Σ d2 and the largest key
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
       if (l[k] > 0 && (unsigned int)dv[k] > DIST_INF) { l[k] = 0; any_bad |= 2; }       // the pixel is skipped
       key[k] = l[k] > 0 ? ((u64)(unsigned int)dv[k] << 32) | (u64)(0xFFFFFFFFu - (unsigned int)(p0 + k)) : 0ull;
-      if (l[k] > 0) s += (u64)(unsigned int)dv[k];
-      kmax = key[k] > kmax ? key[k] : kmax;
+      if (l[k] > 0) v.s += (u64)(unsigned int)dv[k];
+      v.k = key[k] > v.k ? key[k] : v.k;
     }
     const bool uni = l[0] > 0 && l[0] == l[1] && l[1] == l[2] && l[2] == l[3];
-    const int lprev = __shfl_up(l[0], 1);
-    const u64 unis = __ballot(uni);
-    const bool head = !uni || lane == 0 || !((unis >> (lane - 1)) & 1ull) || lprev != l[0];
-    const u64 heads = __ballot(head);
-    const int end = lane + run_lanes(heads, lane);
-    // segmented reduction: after the step with distance d a lane holds lanes [lane, min(lane + 2d, end)) of its run
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const u64 s2 = __shfl_down(s, d), k2 = __shfl_down(kmax, d);
-      if (lane + d < end) {
-        s += s2;
-        kmax = k2 > kmax ? k2 : kmax;
-      }
-    }
+    const Heads h = run_heads(uni, l, lane);
+    v = reduce_run(v, lane, lane + run_lanes(h.heads, lane));
     if (uni) {
-      if (head) add_inscribed(keys, ssum, smax, out, l[0], s, kmax);
+      if (h.head) add_inscribed(keys, ssum, smax, out, l[0], v.s, v.k);
     } else {
       int cur = 0;
       u64 cs = 0, ck = 0;
@@ -231,10 +211,10 @@ extern "C" int clx_region_inscribed(const int32_t* labels, const int32_t* dist_s
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_region_inscribed: nid must lie in [1, 2^24]");
   CLX_REQUIRE(npix > 0 && npix < (1ll << 32), "clx_region_inscribed: npix must lie in [1, 2^32)");
   hipStream_t st = (hipStream_t)stream;
-  inscribed_init<<<(nid + 255) / 256, 256, 0, st>>>(out, bad, nid);
+  launch_table_init<3>(out, bad, nid, st);
   const Tiling t = tiling_for(npix);
-  inscribed_kernel<<<t.grid, BLOCK, 0, st>>>(labels, dist_sq, ((uintptr_t)labels & 15) == 0, ((uintptr_t)dist_sq & 15) == 0, npix,
-                                             nid, t.ntiles, t.per_block, out, bad);
+  inscribed_kernel<<<t.grid, BLOCK, 0, st>>>(labels, dist_sq, aligned16(labels), aligned16(dist_sq), npix, nid, t.ntiles,
+                                             t.per_block, out, bad);
   inscribed_decode<<<(nid + 255) / 256, 256, 0, st>>>(out, nid);
   CLX_CHECK_LAUNCH("clx_region_inscribed");
   return CLX_OK;

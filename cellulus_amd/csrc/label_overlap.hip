@@ -38,12 +38,12 @@ __global__ __launch_bounds__(BLOCK) void overlaps_kernel(const int* __restrict__
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * tiles_per_block;
-  const long long t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
+  const Tiles tiles = block_tiles(ntiles, tiles_per_block);
+  const long long t0 = tiles.t0, t1 = tiles.t1;
   int any_bad = 0;
   int na[PPL], nb[PPL];                                   // the next trip's pixels: on their way while this trip's are counted
   if (t0 < t1) {
-    const long long p0 = t0 * TILE + (long long)threadIdx.x * PPL;
+    const long long p0 = lane_pixel(t0);
     load_labels(a, vec_a != 0, p0, npix, na);             // past the end of the maps: (0, 0), which is not counted
     load_labels(b, vec_b != 0, p0, npix, nb);
   }
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(BLOCK) void overlaps_kernel(const int* __restrict__
 #pragma unroll
     for (int k = 0; k < PPL; ++k) { la[k] = na[k]; lb[k] = nb[k]; }
     if (t + 1 < t1) {
-      const long long p1 = (t + 1) * TILE + (long long)threadIdx.x * PPL;
+      const long long p1 = lane_pixel(t + 1);
       load_labels(a, vec_a != 0, p1, npix, na);
       load_labels(b, vec_b != 0, p1, npix, nb);
     }
@@ -64,12 +64,9 @@ __global__ __launch_bounds__(BLOCK) void overlaps_kernel(const int* __restrict__
     if (__ballot((key[0] | key[1] | key[2] | key[3]) != 0ull) == 0ull) continue;
 
     const bool uni = key[0] != 0ull && key[0] == key[1] && key[1] == key[2] && key[2] == key[3];
-    const u64 kprev = __shfl_up(key[0], 1);
-    const u64 unis = __ballot(uni);
-    const bool head = !uni || lane == 0 || !((unis >> (lane - 1)) & 1ull) || kprev != key[0];
-    const u64 heads = __ballot(head);
+    const Heads h = run_heads(uni, key, lane);
     if (uni) {
-      if (head) add_pair(lkeys, lcnt, o, key[0], (unsigned int)(PPL * run_lanes(heads, lane)));
+      if (h.head) add_pair(lkeys, lcnt, o, key[0], (unsigned int)(PPL * run_lanes(h.heads, lane)));
     } else {
       u64 cur = 0ull;
       unsigned int n = 0;
@@ -108,13 +105,6 @@ __device__ void add_clearance(int* keys, u64* scnt, u64* ssum, u64* smin, u64* _
   }
 }
 
-__global__ void clearance_init(u64* __restrict__ out, int* __restrict__ bad, int nid) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) *bad = 0;
-  if (i >= nid) return;
-  out[(size_t)i * 3] = 0; out[(size_t)i * 3 + 1] = ~0ull; out[(size_t)i * 3 + 2] = 0;
-}
-
 __global__ __launch_bounds__(BLOCK) void clearance_kernel(const int* __restrict__ a, const int* __restrict__ b,
                                                           const int* __restrict__ dist, const int* __restrict__ parent, int vec_a,
                                                           int vec_b, int vec_dist, long long npix, int nid_a, long long ntiles,
@@ -125,18 +115,18 @@ __global__ __launch_bounds__(BLOCK) void clearance_kernel(const int* __restrict_
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * tiles_per_block;
-  const long long t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
+  const Tiles tiles = block_tiles(ntiles, tiles_per_block);
+  const long long t0 = tiles.t0, t1 = tiles.t1;
   int any_bad = 0;
   int na[PPL], nb[PPL], nd[PPL];                          // the next trip's pixels, as in overlaps_kernel
   if (t0 < t1) {
-    const long long p0 = t0 * TILE + (long long)threadIdx.x * PPL;
+    const long long p0 = lane_pixel(t0);
     load_labels(a, vec_a != 0, p0, npix, na);
     load_labels(b, vec_b != 0, p0, npix, nb);
     load_labels(dist, vec_dist != 0, p0, npix, nd);
   }
   for (long long t = t0; t < t1; ++t) {
-    const long long p0 = t * TILE + (long long)threadIdx.x * PPL;
+    const long long p0 = lane_pixel(t);
     int ia[PPL], lb[PPL], dv[PPL], l[PPL];                // l: the id of a counted pixel, or 0
 #pragma unroll
     for (int k = 0; k < PPL; ++k) { ia[k] = na[k]; lb[k] = nb[k]; dv[k] = nd[k]; }
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(BLOCK) void clearance_kernel(const int* __restrict_
     if (clamp_labels(ia, nid_a)) any_bad |= BAD_A;
     if (__ballot((ia[0] | ia[1] | ia[2] | ia[3]) != 0) == 0ull) continue; // no pixel of a in the wave
     u64 key[PPL];
-    u64 s = 0, kmin = ~0ull;
+    SumKey<false> v = {0, ~0ull};                         // Σ dist_sq and the smallest key
     int par = 0;
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
@@ -158,27 +148,15 @@ __global__ __launch_bounds__(BLOCK) void clearance_kernel(const int* __restrict_
       if (counted && (unsigned int)dv[k] > DIST_INF) { counted = false; any_bad |= BAD_DISTANCE; }     // the pixel is skipped
       l[k] = counted ? ia[k] : 0;
       key[k] = l[k] > 0 ? ((u64)(unsigned int)dv[k] << 32) | (u64)(unsigned int)(p0 + k) : ~0ull;
-      if (l[k] > 0) s += (u64)(unsigned int)dv[k];
-      kmin = key[k] < kmin ? key[k] : kmin;
+      if (l[k] > 0) v.s += (u64)(unsigned int)dv[k];
+      v.k = key[k] < v.k ? key[k] : v.k;
     }
     const bool uni = l[0] > 0 && l[0] == l[1] && l[1] == l[2] && l[2] == l[3];
-    const int lprev = __shfl_up(l[0], 1);
-    const u64 unis = __ballot(uni);
-    const bool head = !uni || lane == 0 || !((unis >> (lane - 1)) & 1ull) || lprev != l[0];
-    const u64 heads = __ballot(head);
-    const int run = run_lanes(heads, lane);
-    const int end = lane + run;
-    // segmented reduction: after the step with distance d a lane holds lanes [lane, min(lane + 2d, end)) of its run
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const u64 s2 = __shfl_down(s, d), k2 = __shfl_down(kmin, d);
-      if (lane + d < end) {
-        s += s2;
-        kmin = k2 < kmin ? k2 : kmin;
-      }
-    }
+    const Heads h = run_heads(uni, l, lane);
+    const int run = run_lanes(h.heads, lane);
+    v = reduce_run(v, lane, lane + run);
     if (uni) {
-      if (head) add_clearance(keys, scnt, ssum, smin, out, l[0], (u64)(PPL * run), s, kmin);
+      if (h.head) add_clearance(keys, scnt, ssum, smin, out, l[0], (u64)(PPL * run), v.s, v.k);
     } else {
       int cur = 0;
       u64 cn = 0, cs = 0, ck = ~0ull;
@@ -222,8 +200,7 @@ extern "C" int clx_label_overlaps(const int32_t* a, const int32_t* b, long long 
   const ContactsOut o = contacts_out(keys, counts, info, capacity);
   contacts_init<<<(capacity + 255) / 256, 256, 0, st>>>(o, capacity);
   const Tiling t = tiling_for(npix);
-  overlaps_kernel<<<t.grid, BLOCK, 0, st>>>(a, b, ((uintptr_t)a & 15) == 0, ((uintptr_t)b & 15) == 0, npix, nid_a, nid_b, t.ntiles,
-                                            t.per_block, o);
+  overlaps_kernel<<<t.grid, BLOCK, 0, st>>>(a, b, aligned16(a), aligned16(b), npix, nid_a, nid_b, t.ntiles, t.per_block, o);
   CLX_CHECK_LAUNCH("clx_label_overlaps");
   return CLX_OK;
 }
@@ -234,10 +211,10 @@ extern "C" int clx_region_clearance(const int32_t* a, const int32_t* b, const in
   CLX_REQUIRE(npix > 0 && npix < (1ll << 32), "clx_region_clearance: npix must lie in [1, 2^32)");
   CLX_REQUIRE(nid_a >= 1 && nid_a <= (1 << 24), "clx_region_clearance: nid_a must lie in [1, 2^24]");
   hipStream_t st = (hipStream_t)stream;
-  clearance_init<<<(nid_a + 255) / 256, 256, 0, st>>>(out, bad, nid_a);
+  launch_table_init<3, 1>(out, bad, nid_a, st);         // word 1 is a minimum
   const Tiling t = tiling_for(npix);
-  clearance_kernel<<<t.grid, BLOCK, 0, st>>>(a, b, dist_sq, parent, ((uintptr_t)a & 15) == 0, ((uintptr_t)b & 15) == 0,
-                                             ((uintptr_t)dist_sq & 15) == 0, npix, nid_a, t.ntiles, t.per_block, out, bad);
+  clearance_kernel<<<t.grid, BLOCK, 0, st>>>(a, b, dist_sq, parent, aligned16(a), aligned16(b), aligned16(dist_sq), npix, nid_a,
+                                             t.ntiles, t.per_block, out, bad);
   CLX_CHECK_LAUNCH("clx_region_clearance");
   return CLX_OK;
 }

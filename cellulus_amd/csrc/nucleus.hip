@@ -12,23 +12,9 @@
 //                          structure), everything not reached is instance; atomicMax into the
 //                          output reproduces "later ids overwrite earlier ones"
 // The 256-bin between-class-variance scan per instance stays on the host (numpy, a few µs).
-#include "clx_common.h"
+#include "region_sums.h"                // order_key
 
 namespace {
-
-enum { RAW_F32 = 0, RAW_F64 = 1, RAW_I32 = 2 };
-
-__device__ __forceinline__ unsigned long long order_key(float v) {
-  const unsigned int b = __float_as_uint(v);
-  return (unsigned long long)((b & 0x80000000u) ? ~b : (b | 0x80000000u));
-}
-__device__ __forceinline__ unsigned long long order_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ unsigned long long order_key(int v) {
-  return (unsigned long long)((unsigned int)v ^ 0x80000000u);
-}
 
 __global__ void stats_init(int* __restrict__ bbox, unsigned long long* __restrict__ vkey, int nid) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -197,13 +183,13 @@ extern "C" int clx_inst_stats(const int32_t* seg, const void* raw, int raw_type,
                               int32_t* bbox, unsigned long long* vkey, clx_stream stream) {
   CLX_REQUIRE(seg && raw && bbox && vkey, "clx_inst_stats: null pointer");
   CLX_REQUIRE(Z > 0 && Y > 0 && X > 0 && nid > 0, "clx_inst_stats: bad shape");
-  CLX_REQUIRE(raw_type >= RAW_F32 && raw_type <= RAW_I32, "clx_inst_stats: raw_type must be 0 (f32), 1 (f64) or 2 (i32)");
+  CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "clx_inst_stats: raw_type must be 0 (f32), 1 (f64) or 2 (i32)");
   hipStream_t st = (hipStream_t)stream;
   stats_init<<<(nid + 255) / 256, 256, 0, st>>>(bbox, vkey, nid);
   const long long npix = (long long)Z * Y * X;
   const int grid = grid_for(npix, 256);
-  if (raw_type == RAW_F32) stats_kernel<float><<<grid, 256, 0, st>>>(seg, (const float*)raw, Z, Y, X, nid, bbox, vkey);
-  else if (raw_type == RAW_F64) stats_kernel<double><<<grid, 256, 0, st>>>(seg, (const double*)raw, Z, Y, X, nid, bbox, vkey);
+  if (raw_type == CLX_RAW_F32) stats_kernel<float><<<grid, 256, 0, st>>>(seg, (const float*)raw, Z, Y, X, nid, bbox, vkey);
+  else if (raw_type == CLX_RAW_F64) stats_kernel<double><<<grid, 256, 0, st>>>(seg, (const double*)raw, Z, Y, X, nid, bbox, vkey);
   else stats_kernel<int><<<grid, 256, 0, st>>>(seg, (const int*)raw, Z, Y, X, nid, bbox, vkey);
   CLX_CHECK_LAUNCH("clx_inst_stats");
   return CLX_OK;
@@ -214,12 +200,12 @@ extern "C" int clx_inst_histogram(const int32_t* seg, const void* raw, int raw_t
                                   uint32_t* counts, clx_stream stream) {
   CLX_REQUIRE(seg && raw && slot && edges_or_min && counts, "clx_inst_histogram: null pointer");
   CLX_REQUIRE(npix > 0 && nid > 0 && nbins > 0, "clx_inst_histogram: bad sizes");
-  CLX_REQUIRE(raw_type >= RAW_F32 && raw_type <= RAW_I32, "clx_inst_histogram: raw_type must be 0 (f32), 1 (f64) or 2 (i32)");
+  CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "clx_inst_histogram: raw_type must be 0 (f32), 1 (f64) or 2 (i32)");
   hipStream_t st = (hipStream_t)stream;
   const int grid = grid_for(npix, 256);
-  if (raw_type == RAW_F32)
+  if (raw_type == CLX_RAW_F32)
     inst_hist_kernel<float><<<grid, 256, 0, st>>>(seg, (const float*)raw, npix, slot, nid, (const float*)edges_or_min, nbins, counts);
-  else if (raw_type == RAW_F64)
+  else if (raw_type == CLX_RAW_F64)
     inst_hist_kernel<double><<<grid, 256, 0, st>>>(seg, (const double*)raw, npix, slot, nid, (const double*)edges_or_min, nbins, counts);
   else
     inst_hist_int_kernel<<<grid, 256, 0, st>>>(seg, (const int*)raw, npix, slot, nid, (const int*)edges_or_min, nbins, counts);
@@ -234,13 +220,13 @@ extern "C" int clx_inst_refine(const int32_t* seg, const void* raw, int raw_type
   CLX_REQUIRE(seg && raw && out, "clx_inst_refine: null pointer");
   CLX_REQUIRE(Z > 0 && Y > 0 && X > 0 && n >= 0, "clx_inst_refine: bad shape");
   CLX_REQUIRE(ndim == 3 || (ndim == 2 && Z == 1), "clx_inst_refine: ndim must be 2 (Z == 1) or 3");
-  CLX_REQUIRE(raw_type >= RAW_F32 && raw_type <= RAW_I32, "clx_inst_refine: raw_type must be 0 (f32), 1 (f64) or 2 (i32)");
+  CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "clx_inst_refine: raw_type must be 0 (f32), 1 (f64) or 2 (i32)");
   if (n == 0) return CLX_OK;
   CLX_REQUIRE(ids && bbox && thr && scratch_off && scratch, "clx_inst_refine: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (raw_type == RAW_F32)
+  if (raw_type == CLX_RAW_F32)
     refine_kernel<float><<<n, 256, 0, st>>>(seg, (const float*)raw, ndim == 3, Y, X, ids, bbox, thr, scratch_off, scratch, out);
-  else if (raw_type == RAW_F64)
+  else if (raw_type == CLX_RAW_F64)
     refine_kernel<double><<<n, 256, 0, st>>>(seg, (const double*)raw, ndim == 3, Y, X, ids, bbox, thr, scratch_off, scratch, out);
   else
     refine_kernel<int><<<n, 256, 0, st>>>(seg, (const int*)raw, ndim == 3, Y, X, ids, bbox, thr, scratch_off, scratch, out);

@@ -1,4 +1,4 @@
-// The pair table the measure stage's SETS of id pairs are gathered in (measure.hip: clx_region_contacts; label_overlap.hip:
+// The pair table the measure stage's SETS of id pairs are gathered in (region_contacts.hip: clx_region_contacts; label_overlap.hip:
 // clx_label_overlaps), on top of the reading frame of region_scan.h: an open-addressing table in global memory keyed by a
 // 64-bit pair (never 0), filled through a block-private table in LDS that is flushed once.  A pair that finds no slot in
 // LDS goes straight to the global table; a pair that finds none there within `probes` tries sets bit 2 of info[0] and is

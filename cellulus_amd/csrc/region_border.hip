@@ -3,7 +3,7 @@
 // the image; clx_region_perimeter's definition, in 3-D too), and
 //   clx_region_border_intensity   per id the border pixels, and over those whose value fits: their number, Σq, the smallest
 //                                 and the largest order key and the exact Σq²
-// with q clx_region_intensity's quantised value.  The stencil is contacts_kernel's frame (measure.hip) looking both ways: a
+// with q clx_region_intensity's quantised value.  The stencil is contacts_kernel's frame (region_contacts.hip) looking both ways: a
 // lane holds its four labels, the same four in the rows y - 1 and y + 1 and, for nd = 3, in the slices z - 1 and z + 1 (16-byte
 // loads where the pointer is aligned and X, or Y·X, is a multiple of four; 4-byte loads otherwise), and takes the left and the
 // right neighbour of its ends from the lanes beside it by shuffle, with a load at the wave's two ends.  A flat index ± X or
@@ -70,15 +70,6 @@ __device__ void add_rim(int* keys, u64 (*acc)[SLOTS], u64* __restrict__ out, int
   }
 }
 
-__global__ void border_init(u64* __restrict__ out, int* __restrict__ bad, int nid) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) *bad = 0;
-  if (i >= nid) return;
-  u64* o = out + (size_t)i * NW;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) o[w] = w == W_MIN ? ~0ull : 0ull;
-}
-
 struct BorderArgs {
   const int* lab;
   long long npix, plane, ntiles, tiles_per_block, bound;
@@ -100,11 +91,10 @@ __global__ __launch_bounds__(BLOCK) void border_kernel(BorderArgs a, const T* __
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * a.tiles_per_block;
-  const long long t1 = t0 + a.tiles_per_block < a.ntiles ? t0 + a.tiles_per_block : a.ntiles;
+  const Tiles tiles = block_tiles(a.ntiles, a.tiles_per_block);
   int any_bad = 0;
-  for (long long t = t0; t < t1; ++t) {
-    const long long p0 = t * TILE + (long long)threadIdx.x * PPL;
+  for (long long t = tiles.t0; t < tiles.t1; ++t) {
+    const long long p0 = lane_pixel(t);
     int l[PPL], n[PPL], s[PPL], u[PPL], d[PPL];         // own pixels; the rows y - 1 and y + 1; the slices z - 1 and z + 1
     load_labels(a.lab, a.vec != 0, p0, a.npix, l);
     if (clamp_labels(l, a.nid)) any_bad |= BAD_LABEL;
@@ -132,12 +122,7 @@ __global__ __launch_bounds__(BLOCK) void border_kernel(BorderArgs a, const T* __
       right = p0 + PPL < a.npix ? a.lab[p0 + PPL] : 0;
       if ((unsigned)right >= (unsigned)a.nid) right = 0;
     }
-    // npix < 2^32: 32-bit divisions
-    const unsigned int pu = p0 < a.npix ? (unsigned int)p0 : 0u;
-    const unsigned int r = pu / (unsigned int)a.X;
-    int x = (int)(pu - r * (unsigned int)a.X);
-    int z = (int)(r / (unsigned int)a.Y);
-    int y = (int)(r - (unsigned int)z * (unsigned int)a.Y);
+    Pixel p = pixel_at(p0, a.npix, a.Y, a.X).p;
 
     bool border[PPL];
     bool any = false;
@@ -145,11 +130,11 @@ __global__ __launch_bounds__(BLOCK) void border_kernel(BorderArgs a, const T* __
     for (int k = 0; k < PPL; ++k) {
       const int c = l[k];                               // 0 past the end of the image
       const int lo = k == 0 ? left : l[(k + PPL - 1) & (PPL - 1)], hi = k == PPL - 1 ? right : l[(k + 1) & (PPL - 1)];
-      bool b = x == 0 || lo != c || x == a.X - 1 || hi != c || y == 0 || n[k] != c || y == a.Y - 1 || s[k] != c;
-      if (a.zfaces) b = b || z == 0 || u[k] != c || z == a.Z - 1 || d[k] != c;
+      bool b = p.x == 0 || lo != c || p.x == a.X - 1 || hi != c || p.y == 0 || n[k] != c || p.y == a.Y - 1 || s[k] != c;
+      if (a.zfaces) b = b || p.z == 0 || u[k] != c || p.z == a.Z - 1 || d[k] != c;
       border[k] = c > 0 && b;
       any |= border[k];
-      if (++x == a.X) { x = 0; if (++y == a.Y) { y = 0; ++z; } }
+      p = next_pixel(p, a.Y, a.X);
     }
     if (__ballot(any) == 0ull) continue;                // an interior or background wave: no raw value is read
     if (!any) continue;
@@ -218,18 +203,13 @@ extern "C" int clx_region_border_intensity(const int32_t* labels, const void* ra
   BorderArgs a;
   a.lab = labels;
   a.npix = npix; a.plane = (long long)Y * X; a.ntiles = t.ntiles; a.tiles_per_block = t.per_block;
-  a.bound = (1ll << 62) >> bit_length((unsigned long long)npix);
-  a.vec = ((uintptr_t)labels & 15) == 0; a.vec_y = a.vec && (X & 3) == 0; a.vec_z = a.vec && (a.plane & 3) == 0;
+  a.bound = value_bound(npix);
+  a.vec = aligned16(labels); a.vec_y = a.vec && (X & 3) == 0; a.vec_z = a.vec && (a.plane & 3) == 0;
   a.zfaces = nd == 3;
   a.Z = Z; a.Y = Y; a.X = X; a.nid = nid; a.shift = shift;
   a.out = out; a.bad = bad;
-  border_init<<<(nid + 255) / 256, 256, 0, st>>>(out, bad, nid);
-  if (raw_type == CLX_RAW_F32)
-    border_kernel<float><<<t.grid, BLOCK, 0, st>>>(a, (const float*)raw);
-  else if (raw_type == CLX_RAW_F64)
-    border_kernel<double><<<t.grid, BLOCK, 0, st>>>(a, (const double*)raw);
-  else
-    border_kernel<int><<<t.grid, BLOCK, 0, st>>>(a, (const int*)raw);
+  launch_table_init<NW, W_MIN>(out, bad, nid, st);
+  launch_for_raw(raw_type, [&](auto v) { border_kernel<decltype(v)><<<t.grid, BLOCK, 0, st>>>(a, (const decltype(v)*)raw); });
   CLX_CHECK_LAUNCH(who);
   return CLX_OK;
 }

@@ -28,7 +28,6 @@ namespace {
 constexpr int NW = 20;                  // words per id in the output and in the table
 constexpr int NS = 8;                   // 64-bit words: n Σa Σb n_both Σa|above_a Σb|above_b Σa|both Σb|both
 constexpr int NP = 6;                   // 128-bit sums, (lo, hi) from word NS on: Σaa Σbb Σab, then the three over `both`
-constexpr int INIT_GRID = 1024;
 // With thresholds a block's registers and its 41 KiB table let 3 blocks share a CU: on the 256 CUs of an MI355X 768 blocks run
 // at once, and MAX_GRID = 1024 of them would be one full round and a second one a third full.  (Without thresholds 4 fit.)
 constexpr int THR_GRID = 768;
@@ -97,12 +96,6 @@ __device__ void add_sums(int* keys, u64 (*acc)[SLOTS], u64* __restrict__ out, in
   }
 }
 
-__global__ void products_init(u64* __restrict__ out, int* __restrict__ bad, long long words) {
-  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i0 == 0) *bad = 0;
-  for (long long i = i0; i < words; i += (long long)gridDim.x * blockDim.x) out[i] = 0;
-}
-
 struct ProductsArgs {
   const int* lab;
   const long long* thr_a;
@@ -143,13 +136,13 @@ __global__ __launch_bounds__(BLOCK, THR ? 3 : 4) void products_kernel(ProductsAr
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * a.tiles_per_block;
-  const long long t1 = t0 + a.tiles_per_block < a.ntiles ? t0 + a.tiles_per_block : a.ntiles;
+  const Tiles tiles = block_tiles(a.ntiles, a.tiles_per_block);
+  const long long t0 = tiles.t0, t1 = tiles.t1;
   int tid = 0;                                          // the id whose thresholds the lane holds
   long long ta = 0, tb = 0;
   int any_bad = 0;
   // the loads of the next trip are issued before the work of this one: twice the bytes in flight a wave
-  Trip<T> next = load_trip<T>(a, raw_a, raw_b, t0 < t1 ? t0 * TILE + (long long)threadIdx.x * PPL : a.npix);
+  Trip<T> next = load_trip<T>(a, raw_a, raw_b, t0 < t1 ? lane_pixel(t0) : a.npix);
   for (long long t = t0; t < t1; ++t) {
     const Trip<T> now = next;
     int l[PPL];
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(BLOCK, THR ? 3 : 4) void products_kernel(ProductsAr
         thb[k] = tb;
       }
     }
-    next = load_trip<T>(a, raw_a, raw_b, t + 1 < t1 ? (t + 1) * TILE + (long long)threadIdx.x * PPL : a.npix);
+    next = load_trip<T>(a, raw_a, raw_b, t + 1 < t1 ? lane_pixel(t + 1) : a.npix);
     const Raw4<T>& ra = now.a;
     const Raw4<T>& rb = now.b;
     long long qa[PPL], qb[PPL];
@@ -190,10 +183,9 @@ __global__ __launch_bounds__(BLOCK, THR ? 3 : 4) void products_kernel(ProductsAr
       }
     }
     const bool uni = l[0] > 0 && l[0] == l[1] && l[1] == l[2] && l[2] == l[3];
-    const int lprev = __shfl_up(l[0], 1);
-    const u64 unis = __ballot(uni);
-    const bool head = !uni || lane == 0 || !((unis >> (lane - 1)) & 1ull) || lprev != l[0];
-    const u64 heads = __ballot(head);
+    const Heads h = run_heads(uni, l, lane);
+    const u64 heads = h.heads;
+    const bool head = h.head;
     const int run = run_lanes(heads, lane);
     Sums v;
     clear(v);
@@ -202,7 +194,7 @@ __global__ __launch_bounds__(BLOCK, THR ? 3 : 4) void products_kernel(ProductsAr
       for (int k = 0; k < PPL; ++k) add_pixel<THR>(v, qa[k], qb[k], ua[k], ub[k]);
     }
     if (heads != ~0ull) {                               // the same for the whole wave: some run is longer than a lane
-      // segmented reduction: after the step with distance d a lane holds lanes [lane, min(lane + 2d, end)) of its run
+      // segmented reduction, spelled out (not region_scan.h's reduce_run): which words cross the wave depends on THR
       const int end = lane + run;
 #pragma unroll
       for (int d = 1; d < 64; d <<= 1) {
@@ -270,27 +262,19 @@ extern "C" int clx_region_products(const int32_t* labels, const void* raw_a, con
   const char* who = "clx_region_products";
   CLX_REQUIRE(labels && raw_a && raw_b && out && bad, "%s: null pointer", who);
   CLX_REQUIRE((thr_a == nullptr) == (thr_b == nullptr), "%s: null pointer: thr_a and thr_b are given together or not at all", who);
-  CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "%s: raw_type must be 0 (f32), 1 (f64) or 2 (i32)", who);
-  CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "%s: nid must lie in [1, 2^24]", who);
+  if (require_raw_channel(who, raw_type, nid) != CLX_OK) return CLX_ERR_ARG;
   CLX_REQUIRE(npix > 0 && npix < (1ll << 32), "%s: npix must lie in [1, 2^32)", who);
   hipStream_t st = (hipStream_t)stream;
   const Tiling t = tiling_for(npix, thr_a ? THR_GRID : MAX_GRID);
   ProductsArgs a;
   a.lab = labels; a.thr_a = thr_a; a.thr_b = thr_b;
   a.npix = npix; a.ntiles = t.ntiles; a.tiles_per_block = t.per_block;
-  a.bound = (1ll << 62) >> bit_length((unsigned long long)npix);
-  a.vec_lab = ((uintptr_t)labels & 15) == 0; a.vec_a = ((uintptr_t)raw_a & 15) == 0; a.vec_b = ((uintptr_t)raw_b & 15) == 0;
+  a.bound = value_bound(npix);
+  a.vec_lab = aligned16(labels); a.vec_a = aligned16(raw_a); a.vec_b = aligned16(raw_b);
   a.nid = nid; a.shift_a = shift_a; a.shift_b = shift_b;
   a.out = out; a.bad = bad;
-  const long long words = (long long)nid * NW;
-  const long long iblocks = (words + 255) / 256;
-  products_init<<<(int)(iblocks < INIT_GRID ? iblocks : INIT_GRID), 256, 0, st>>>(out, bad, words);
-  if (raw_type == CLX_RAW_F32)
-    launch_products<float>(a, raw_a, raw_b, t.grid, st);
-  else if (raw_type == CLX_RAW_F64)
-    launch_products<double>(a, raw_a, raw_b, t.grid, st);
-  else
-    launch_products<int>(a, raw_a, raw_b, t.grid, st);
+  launch_table_init<NW>(out, bad, nid, st);
+  launch_for_raw(raw_type, [&](auto v) { launch_products<decltype(v)>(a, raw_a, raw_b, t.grid, st); });
   CLX_CHECK_LAUNCH(who);
   return CLX_OK;
 }

@@ -25,12 +25,11 @@
 // LDS: the sort buffer and the histograms share 32 KiB (SORT_MAX keys of 8 bytes = 32 groups x 256 bins x 4 bytes), so four
 // blocks (16 waves) fit the 160 KiB of a CU.  The number of launches does not depend on the objects or the ranks: init, gather, select,
 // and where total > BLOCK_MAX one list kernel and two kernels per pass.
-#include "region_scan.h"
+#include "region_sums.h"
 
 namespace {
 
-enum { RAW_F32 = 0, RAW_F64 = 1, RAW_I32 = 2 };
-enum { BAD_LABEL = 1, BAD_VALUE = 2, BAD_AREA = 4, BAD_RANK = 8 };
+enum { BAD_AREA = 4, BAD_RANK = 8 };    // beside BAD_LABEL and BAD_VALUE
 
 constexpr int MAX_NQ = 32;
 constexpr int BINS = 256;
@@ -41,23 +40,11 @@ constexpr int LOADS = 4;                // keys a thread has in flight in a hist
 constexpr int SELECT_GRID = 2048;
 constexpr int BIG_GRID = 2048;
 
-__device__ __forceinline__ u64 order_key(float v) {
-  const unsigned int b = __float_as_uint(v);
-  return (u64)((b & 0x80000000u) ? ~b : (b | 0x80000000u));
-}
-__device__ __forceinline__ u64 order_key(double v) {
-  const u64 b = (u64)__double_as_longlong(v);
-  return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ u64 order_key(int v) { return (u64)((unsigned int)v ^ 0x80000000u); }
-
 __device__ __forceinline__ bool finite_value(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 __device__ __forceinline__ bool finite_value(double v) {
   return ((u64)__double_as_longlong(v) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
 }
 __device__ __forceinline__ bool finite_value(int) { return true; }
-
-template <typename T> struct alignas(16) Raw4 { T v[PPL]; };
 
 // whether [base, base + area) lies inside the key buffer: area and seg_base are the caller's, nothing is indexed before this
 __device__ __forceinline__ bool segment_ok(u64 base, u64 area, u64 total) { return base <= total && area <= total - base; }
@@ -89,15 +76,14 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(const int* __restrict__ l
   __shared__ u64 tile_pos;
   static_assert(BLOCK / 64 == 4, "whole_tile compares four waves");
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * tiles_per_block;
-  const long long t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
+  const Tiles tiles = block_tiles(ntiles, tiles_per_block);
   int any_bad = 0;
-  for (long long t = t0; t < t1; ++t) {
-    const long long p0 = t * TILE + (long long)threadIdx.x * PPL;
+  for (long long t = tiles.t0; t < tiles.t1; ++t) {
+    const long long p0 = lane_pixel(t);
     int l[PPL];
     load_labels(lab, vec_lab != 0, p0, npix, l);
     if (clamp_labels(l, nid)) any_bad |= BAD_LABEL;
-    Raw4<T> rv;
+    Raw4<T> rv;                                         // load_raw spelled out: through the helper the int kernel ran 5 % slower
     if (vec_raw && p0 + PPL <= npix) {
       rv = *reinterpret_cast<const Raw4<T>*>(raw + p0);
     } else {
@@ -114,15 +100,14 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(const int* __restrict__ l
       }
     }
     const bool uni = l[0] > 0 && l[0] == l[1] && l[1] == l[2] && l[2] == l[3];
-    const int lprev = __shfl_up(l[0], 1);
-    const u64 unis = __ballot(uni);
-    const bool head = !uni || lane == 0 || !((unis >> (lane - 1)) & 1ull) || lprev != l[0];
-    const u64 heads = __ballot(head);
+    const Heads h = run_heads(uni, l, lane);
+    const u64 heads = h.heads;
+    const bool head = h.head;
     const int n = run_lanes(heads, lane);
     const int head_lane = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));     // lane 0 is always a head
     // a tile that is one id from end to end (the inside of a large object) reserves once for the block: on the map that is
     // one object everywhere every reservation goes to the same cursor, and they are what the pass waits for
-    const bool whole_wave = heads == 1ull && (unis & 1ull);
+    const bool whole_wave = heads == 1ull && (__ballot(uni) & 1ull);
     int* ids = wave_id[(int)(t & 1)];                     // two sets: a wave may be one tile ahead of the slowest
     if (lane == 0) ids[threadIdx.x >> 6] = whole_wave ? l[0] : 0;
     __syncthreads();
@@ -447,8 +432,7 @@ static int order_run(const int32_t* labels, const void* raw, int raw_type, long 
                      int nq, unsigned long long* out, void* workspace, size_t workspace_bytes, int32_t* bad, int phases,
                      const char* who, clx_stream stream) {
   CLX_REQUIRE(labels && raw && area && seg_base && rank && out && workspace && bad, "%s: null pointer", who);
-  CLX_REQUIRE(raw_type >= RAW_F32 && raw_type <= RAW_I32, "%s: raw_type must be 0 (f32), 1 (f64) or 2 (i32)", who);
-  CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "%s: nid must lie in [1, 2^24]", who);
+  if (require_raw_channel(who, raw_type, nid) != CLX_OK) return CLX_ERR_ARG;
   CLX_REQUIRE(npix > 0 && npix < (1ll << 32), "%s: npix must lie in [1, 2^32)", who);
   CLX_REQUIRE(nq >= 1 && nq <= MAX_NQ, "%s: nq must lie in [1, 32]", who);
   CLX_REQUIRE(total >= 0 && total <= npix, "%s: total must lie in [0, npix]", who);
@@ -468,19 +452,17 @@ static int order_run(const int32_t* labels, const void* raw, int raw_type, long 
   if (phases & 1)
     order_init<<<(int)(init_blocks < 4096 ? init_blocks : 4096), 256, 0, st>>>(out, nout, cursor, nid, bad);
   if (total > 0 && nid > 1 && (phases & 1)) {
-    const int vl = ((uintptr_t)labels & 15) == 0, vr = ((uintptr_t)raw & 15) == 0;
     const Tiling t = tiling_for(npix);
-#define CLX_GATHER(T, C)                                                                                                  \
-  gather_kernel<T, C><<<t.grid, BLOCK, 0, st>>>(labels, (const T*)raw, vl, vr, npix, nid, t.ntiles, t.per_block, area, seg_base, \
-                                                (u64)total, centre, cursor, keys, bad)
-    if (raw_type == RAW_F32) { if (centre) CLX_GATHER(float, true); else CLX_GATHER(float, false); }
-    else if (raw_type == RAW_F64) { if (centre) CLX_GATHER(double, true); else CLX_GATHER(double, false); }
-    else { if (centre) CLX_GATHER(int, true); else CLX_GATHER(int, false); }
-#undef CLX_GATHER
+    launch_for_raw(raw_type, [&](auto v) {
+      using T = decltype(v);
+      auto* gather = centre ? gather_kernel<T, true> : gather_kernel<T, false>;
+      gather<<<t.grid, BLOCK, 0, st>>>(labels, (const T*)raw, aligned16(labels), aligned16(raw), npix, nid, t.ntiles, t.per_block,
+                                       area, seg_base, (u64)total, centre, cursor, keys, bad);
+    });
   }
   if (total > 0 && nid > 1 && (phases & 2)) {
     // float32 / int32 keys lie in the low 32 bits; |v - centre| is a float64 whatever the raw type
-    const int first_shift = (raw_type == RAW_F64 || centre) ? 56 : 24;
+    const int first_shift = (raw_type == CLX_RAW_F64 || centre) ? 56 : 24;
     const int sgrid = nid - 1 < SELECT_GRID ? nid - 1 : SELECT_GRID;
     select_kernel<<<sgrid, BLOCK, 0, st>>>(keys, area, seg_base, cursor, rank, nq, nid, (u64)total, first_shift, counter, out, bad);
     if (L.max_big > 0) {

@@ -18,7 +18,7 @@
 // consecutive pixels of a row mostly share ring and wedge, so a ballot cuts the wave into runs of lanes whose 4 pixels lie in
 // one cell, a segmented wave reduction sums a run, and its first lane adds it to a table in LDS keyed by cell (open
 // addressing, RPROBES tries, then straight to global memory) that the block flushes once.  Integer adds only.
-#include "region_scan.h"
+#include "region_sums.h"
 
 namespace {
 
@@ -28,23 +28,7 @@ constexpr int MAX_RINGS = 32;
 constexpr int MAX_WIDTH = 32768;
 constexpr u64 D2_CUT = 1ull << 41;      // above (2^31 - 1) * 32^2: a larger D2 gives the same ring
 constexpr int INIT_GRID = 1024;
-enum { BAD_LABEL = 1, BAD_VALUE = 2, BAD_MAP = 4, BAD_ROW = 8 };
-
-template <typename T> struct alignas(16) Raw4 { T v[PPL]; };
-
-// q of one raw value as clx_region_intensity forms it; false: not finite, or |q| above the bound
-template <typename T>
-__device__ __forceinline__ bool quantise(T v, int shift, long long bound, long long* q) {
-  const double t = rint(ldexp((double)v, shift));       // NaN and ±Inf fail the comparison / exceed the bound
-  if (!(fabs(t) <= (double)bound)) return false;        // bound is a power of two: exact as a double
-  *q = (long long)t;
-  return true;
-}
-template <>
-__device__ __forceinline__ bool quantise<int>(int v, int, long long, long long* q) {
-  *q = (long long)v;
-  return true;
-}
+enum { BAD_MAP = 4, BAD_ROW = 8 };      // beside BAD_LABEL and BAD_VALUE
 
 // smallest k in [0, rings) with lhs <= (k + 1)^2 * scale; rings - 1 where none has (absolute mode's last ring)
 __device__ __forceinline__ int ring_of(u64 lhs, u64 scale, int rings) {
@@ -102,6 +86,13 @@ __device__ void add_cell(int* keys, unsigned int* scnt, u64* ssum, u64* __restri
   }
 }
 
+// what a run sums of its pixels
+struct Sum {
+  long long s;
+  __device__ __forceinline__ Sum shifted(int d) const { return {__shfl_down(s, d)}; }
+  __device__ __forceinline__ void take(const Sum& o) { s += o.s; }
+};
+
 __global__ void radial_init(u64* __restrict__ count, long long* __restrict__ isum, int* __restrict__ bad, long long cells) {
   const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i0 == 0) *bad = 0;
@@ -134,28 +125,20 @@ __global__ __launch_bounds__(BLOCK) void radial_kernel(RadialArgs a, const T* __
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * a.tiles_per_block;
-  const long long t1 = t0 + a.tiles_per_block < a.ntiles ? t0 + a.tiles_per_block : a.ntiles;
+  const Tiles tiles = block_tiles(a.ntiles, a.tiles_per_block);
   const bool relative = a.width == 0;
   const u64 rings_sq = (u64)(a.rings * a.rings), width_sq = (u64)a.width * (u64)a.width;
   IdInfo c;
   c.id = 0; c.row = -1; c.limit = 0; c.scale = 0; c.cy = 0; c.cx = 0; c.centre_ok = false;
   int any_bad = 0;
-  for (long long t = t0; t < t1; ++t) {
-    const long long p0 = t * TILE + (long long)threadIdx.x * PPL;
+  for (long long t = tiles.t0; t < tiles.t1; ++t) {
+    const long long p0 = lane_pixel(t);
     int l[PPL], dv[PPL];
     load_labels(a.lab, a.vec_lab != 0, p0, a.npix, l);
     if (clamp_labels(l, a.nid)) any_bad |= BAD_LABEL;
     load_labels(a.dist, a.vec_dist != 0, p0, a.npix, dv);     // the same 4-pixel read; past the end: 0
     Raw4<T> rv;
-    if (RAW) {
-      if (a.vec_raw && p0 + PPL <= a.npix) {
-        rv = *reinterpret_cast<const Raw4<T>*>(raw + p0);
-      } else {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) rv.v[k] = p0 + k < a.npix ? raw[p0 + k] : (T)0;
-      }
-    }
+    if (RAW) rv = load_raw<T>(raw, a.vec_raw != 0, p0, a.npix);
     int y = 0, x = 0;
     if (a.wedges == 8) {                                      // nd == 2, npix < 2^32: a 32-bit division
       const unsigned int pu = p0 < a.npix ? (unsigned int)p0 : 0u;
@@ -208,22 +191,11 @@ __global__ __launch_bounds__(BLOCK) void radial_kernel(RadialArgs a, const T* __
       if (++x == a.X) { x = 0; ++y; }                         // used with wedges == 8 only
     }
     const bool uni = cell[0] >= 0 && cell[0] == cell[1] && cell[1] == cell[2] && cell[2] == cell[3];
-    const int cprev = __shfl_up(cell[0], 1);
-    const u64 unis = __ballot(uni);
-    const bool head = !uni || lane == 0 || !((unis >> (lane - 1)) & 1ull) || cprev != cell[0];
-    const u64 heads = __ballot(head);
-    const int run = run_lanes(heads, lane);
-    if (RAW) {
-      // segmented reduction: after the step with distance d a lane holds lanes [lane, min(lane + 2d, end)) of its run
-      const int end = lane + run;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const long long s2 = __shfl_down(s, d);
-        if (lane + d < end) s += s2;
-      }
-    }
+    const Heads h = run_heads(uni, cell, lane);
+    const int run = run_lanes(h.heads, lane);
+    if (RAW) s = reduce_run(Sum{s}, lane, lane + run).s;
     if (uni) {
-      if (head) add_cell(keys, scnt, ssum, a.count, a.isum, cell[0], (unsigned int)(PPL * run), s);
+      if (h.head) add_cell(keys, scnt, ssum, a.count, a.isum, cell[0], (unsigned int)(PPL * run), s);
     } else {
       int cur = -1;
       unsigned int cn = 0;
@@ -249,12 +221,6 @@ __global__ __launch_bounds__(BLOCK) void radial_kernel(RadialArgs a, const T* __
     atomicAdd(a.count + (key - 1), (u64)scnt[s]);
     if (a.isum && ssum[s]) atomicAdd(reinterpret_cast<u64*>(a.isum) + (key - 1), ssum[s]);
   }
-}
-
-inline int bit_length(unsigned long long v) {
-  int n = 0;
-  while (v) { ++n; v >>= 1; }
-  return n;
 }
 
 }  // namespace
@@ -286,20 +252,16 @@ extern "C" int clx_region_radial(const int32_t* labels, const int32_t* dist_sq, 
   RadialArgs a;
   a.lab = labels; a.dist = dist_sq; a.inscribed = inscribed; a.row = row;
   a.npix = npix; a.ntiles = t.ntiles; a.tiles_per_block = t.per_block;
-  a.bound = (1ll << 62) >> bit_length((unsigned long long)npix);
-  a.vec_lab = ((uintptr_t)labels & 15) == 0; a.vec_dist = ((uintptr_t)dist_sq & 15) == 0; a.vec_raw = ((uintptr_t)raw & 15) == 0;
+  a.bound = value_bound(npix);
+  a.vec_lab = aligned16(labels); a.vec_dist = aligned16(dist_sq); a.vec_raw = aligned16(raw);
   a.X = X; a.nid = nid; a.nrows = nrows; a.rings = rings; a.width = width; a.wedges = wedges; a.shift = shift;
   a.count = count; a.isum = raw ? isum : nullptr; a.bad = bad;
   const long long iblocks = (cells + 255) / 256;
   radial_init<<<(int)(iblocks < 1 ? 1 : iblocks < INIT_GRID ? iblocks : INIT_GRID), 256, 0, st>>>(count, isum, bad, cells);
   if (!raw)
     radial_kernel<int, false><<<t.grid, BLOCK, 0, st>>>(a, nullptr);
-  else if (raw_type == CLX_RAW_F32)
-    radial_kernel<float, true><<<t.grid, BLOCK, 0, st>>>(a, (const float*)raw);
-  else if (raw_type == CLX_RAW_F64)
-    radial_kernel<double, true><<<t.grid, BLOCK, 0, st>>>(a, (const double*)raw);
   else
-    radial_kernel<int, true><<<t.grid, BLOCK, 0, st>>>(a, (const int*)raw);
+    launch_for_raw(raw_type, [&](auto v) { radial_kernel<decltype(v), true><<<t.grid, BLOCK, 0, st>>>(a, (const decltype(v)*)raw); });
   CLX_CHECK_LAUNCH(who);
   return CLX_OK;
 }

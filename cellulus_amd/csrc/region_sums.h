@@ -1,6 +1,7 @@
-// What the measure stage's value reductions share on top of the reading frame of region_scan.h (region_coloc.hip,
-// region_weighted.hip, region_border.hip): clx_region_intensity's quantisation of a raw value, the order-preserving keys of
-// measure.hip, a lane's four raw values, and the 128-bit sums: __int128 in registers, two 64-bit words (lo, hi), two's
+// What the measure stage's value reductions share on top of the reading frame of region_scan.h (region_moments.hip,
+// region_coloc.hip, region_weighted.hip, region_border.hip, region_radial.hip, region_order.hip): the checks and the launch
+// by type of a raw channel, clx_region_intensity's quantisation of a raw value and its order-preserving keys, a lane's four
+// raw values, and the 128-bit sums: __int128 in registers, two 64-bit words (lo, hi), two's
 // complement, in LDS and in global memory, where an add is two 64-bit atomic adds: the low limbs first, whose returned old
 // value says whether they wrapped, then the high limbs plus that carry.
 #pragma once
@@ -28,7 +29,7 @@ __device__ __forceinline__ bool quantise<int>(int v, int, long long, long long* 
   return true;
 }
 
-// the keys of measure.hip: unsigned order is the order of the values (-0.0 below +0.0)
+// the keys of clx_region_intensity: unsigned order is the order of the values (-0.0 below +0.0)
 __device__ __forceinline__ u64 order_key(float v) {
   const unsigned int b = __float_as_uint(v);
   return (u64)((b & 0x80000000u) ? ~b : (b | 0x80000000u));
@@ -71,6 +72,23 @@ inline int bit_length(unsigned long long v) {
   int n = 0;
   while (v) { ++n; v >>= 1; }
   return n;
+}
+// the largest |q| of one pixel: a sum of npix of them stays below 2^62
+inline long long value_bound(long long npix) { return (1ll << 62) >> bit_length((unsigned long long)npix); }
+
+// what every entry point that reads a raw channel asks of raw_type and nid
+inline int require_raw_channel(const char* who, int raw_type, int nid) {
+  CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "%s: raw_type must be 0 (f32), 1 (f64) or 2 (i32)", who);
+  CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "%s: nid must lie in [1, 2^24]", who);
+  return CLX_OK;
+}
+
+// launch(T()) with T the element type that a checked raw_type names
+template <typename F>
+inline void launch_for_raw(int raw_type, F launch) {
+  if (raw_type == CLX_RAW_F32) launch(float());
+  else if (raw_type == CLX_RAW_F64) launch(double());
+  else launch(int());
 }
 
 }  // namespace

@@ -43,9 +43,8 @@ constexpr int NW = 21;                  // words per id: n, Σq, peak, then nine
 constexpr int NM = 9;                   // Σq·z Σq·y Σq·x Σq·zz Σq·yy Σq·xx Σq·zy Σq·zx Σq·yx
 constexpr int NM2 = 5;                  // a 2-D map (Z == 1) has z = 0: Σq·y Σq·x Σq·yy Σq·xx Σq·yx are all there is to sum
 constexpr int W_PEAK = 2, W_SUMS = 3;
-constexpr int INIT_GRID = 1024;
 constexpr int GRID_3D = 768;            // three blocks a CU (the table), 256 CUs; a 2-D table lets four share one: MAX_GRID
-constexpr u64 NO_PEAK = ~0ull;
+constexpr u64 NO_PEAK = ~0ull;          // what table_init leaves in word W_PEAK
 
 // the sums a block's table keeps: all nine in 3-D, in 2-D the five without z; `sum_of` says which of the nine the j-th is
 template <bool Z3> struct Table {
@@ -59,6 +58,9 @@ struct Piece {
   u64 n;
   long long s0;
   i128 s1, s2;
+  // for reduce_run; n does not cross the wave: it is 4 pixels a lane, the run's length gives it
+  __device__ __forceinline__ Piece shifted(int d) const { return {n, __shfl_down(s0, d), shfl_down128(s1, d), shfl_down128(s2, d)}; }
+  __device__ __forceinline__ void take(const Piece& o) { s0 += o.s0; s1 += o.s1; s2 += o.s2; }
 };
 
 __device__ __forceinline__ void add_pixel(Piece& v, long long q, int x) {
@@ -117,12 +119,6 @@ __device__ void add_peak(int* keys, u64 (*acc)[SLOTS], u64* __restrict__ out, in
   }
 }
 
-__global__ void weighted_init(u64* __restrict__ out, int* __restrict__ bad, long long words) {
-  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i0 == 0) *bad = 0;
-  for (long long i = i0; i < words; i += (long long)gridDim.x * blockDim.x) out[i] = i % NW == W_PEAK ? NO_PEAK : 0ull;
-}
-
 struct WeightedArgs {
   const int* lab;
   const u64* peak_keys;
@@ -159,15 +155,15 @@ __global__ __launch_bounds__(BLOCK, Z3 ? 3 : 4) void weighted_kernel(WeightedArg
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
-  const long long t0 = (long long)blockIdx.x * a.tiles_per_block;
-  const long long t1 = t0 + a.tiles_per_block < a.ntiles ? t0 + a.tiles_per_block : a.ntiles;
+  const Tiles tiles = block_tiles(a.ntiles, a.tiles_per_block);
+  const long long t0 = tiles.t0, t1 = tiles.t1;
   int kid = 0;                                          // the id whose largest key the lane holds
   u64 kmax = NO_PEAK;
   int any_bad = 0;
   // the loads of the next trip are issued before the work of this one: twice the bytes in flight a wave
-  Trip<T> next = load_trip<T>(a, raw, t0 < t1 ? t0 * TILE + (long long)threadIdx.x * PPL : a.npix);
+  Trip<T> next = load_trip<T>(a, raw, t0 < t1 ? lane_pixel(t0) : a.npix);
   for (long long t = t0; t < t1; ++t) {
-    const long long p0 = t * TILE + (long long)threadIdx.x * PPL;
+    const long long p0 = lane_pixel(t);
     const Trip<T> now = next;
     int l[PPL];
 #pragma unroll
@@ -184,7 +180,7 @@ __global__ __launch_bounds__(BLOCK, Z3 ? 3 : 4) void weighted_kernel(WeightedArg
       }
       pk[k] = kmax;
     }
-    next = load_trip<T>(a, raw, t + 1 < t1 ? (t + 1) * TILE + (long long)threadIdx.x * PPL : a.npix);
+    next = load_trip<T>(a, raw, t + 1 < t1 ? lane_pixel(t + 1) : a.npix);
     long long q[PPL];
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
@@ -194,44 +190,26 @@ __global__ __launch_bounds__(BLOCK, Z3 ? 3 : 4) void weighted_kernel(WeightedArg
         else if (a.peak_keys && order_key(now.r.v[k]) == pk[k]) add_peak(keys, acc, a.out, l[k], (u64)(p0 + k));
       }
     }
-    // npix < 2^32: 32-bit divisions
-    const unsigned int pu = p0 < a.npix ? (unsigned int)p0 : 0u;
-    const unsigned int r = pu / (unsigned int)a.X;
-    int x = (int)(pu - r * (unsigned int)a.X);
-    int z = (int)(r / (unsigned int)a.Y);
-    int y = (int)(r - (unsigned int)z * (unsigned int)a.Y);
+    const PixelInRow at = pixel_at(p0, a.npix, a.Y, a.X);
+    Pixel p = at.p;
 
     // a run never continues into the next image row: z and y are constants of a run inside one row only
-    const bool uni = l[0] > 0 && l[0] == l[1] && l[1] == l[2] && l[2] == l[3] && x + PPL <= a.X;
-    const int lprev = __shfl_up(l[0], 1);
-    const unsigned int rprev = __shfl_up(r, 1);
-    const u64 unis = __ballot(uni);
-    const bool head = !uni || lane == 0 || !((unis >> (lane - 1)) & 1ull) || lprev != l[0] || rprev != r;
-    const u64 heads = __ballot(head);
-    const int run = run_lanes(heads, lane);
+    const bool uni = l[0] > 0 && l[0] == l[1] && l[1] == l[2] && l[2] == l[3] && p.x + PPL <= a.X;
+    const Heads h = run_heads(uni, l, at.row, lane);
+    const int run = run_lanes(h.heads, lane);
     Piece v = {0ull, 0ll, 0, 0};
     if (uni) {
 #pragma unroll
-      for (int k = 0; k < PPL; ++k) add_pixel(v, q[k], x + k);
+      for (int k = 0; k < PPL; ++k) add_pixel(v, q[k], p.x + k);
     }
-    if (heads != ~0ull) {                               // the same for the whole wave: some run is longer than a lane
-      // segmented reduction: after the step with distance d a lane holds lanes [lane, min(lane + 2d, end)) of its run
-      const int end = lane + run;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const bool take = lane + d < end;
-        const long long o0 = __shfl_down(v.s0, d);      // n is 4 pixels a lane: the run's length gives it
-        const i128 o1 = shfl_down128(v.s1, d), o2 = shfl_down128(v.s2, d);
-        if (take) { v.s0 += o0; v.s1 += o1; v.s2 += o2; }
-      }
-    }
+    if (h.heads != ~0ull) v = reduce_run(v, lane, lane + run);   // the same for the whole wave: some run is longer than a lane
     // One door for nearly every piece: a run's head brings the run, a lane on an edge the first piece of its walk; only the
     // second and later pieces of such a lane (two objects and a gap inside four pixels, a row's end) leave on their own.
     // Each pass through add_piece costs a wave its LDS round trips, whichever lanes take part.
-    int alabel = 0, az = z, ay = y;
+    int alabel = 0, az = p.z, ay = p.y;
     Piece first = v;
     if (uni) {
-      if (head) {
+      if (h.head) {
         first.n = (u64)(PPL * run);
         alabel = l[0];
       }
@@ -240,16 +218,16 @@ __global__ __launch_bounds__(BLOCK, Z3 ? 3 : 4) void weighted_kernel(WeightedArg
       v = {0ull, 0ll, 0, 0};
 #pragma unroll
       for (int k = 0; k < PPL; ++k) {
-        if (l[k] != cur || x == 0) {
+        if (l[k] != cur || p.x == 0) {
           if (cur > 0) {
             if (alabel == 0) { first = v; alabel = cur; az = cz; ay = cy; }
             else add_piece<Z3>(keys, acc, a.out, cur, v, cz, cy);
           }
-          cur = l[k]; cz = z; cy = y;
+          cur = l[k]; cz = p.z; cy = p.y;
           v = {0ull, 0ll, 0, 0};
         }
-        if (cur > 0) add_pixel(v, q[k], x);
-        if (++x == a.X) { x = 0; if (++y == a.Y) { y = 0; ++z; } }
+        if (cur > 0) add_pixel(v, q[k], p.x);
+        p = next_pixel(p, a.Y, a.X);
       }
       if (cur > 0) {
         if (alabel == 0) { first = v; alabel = cur; az = cz; ay = cy; }
@@ -290,8 +268,7 @@ extern "C" int clx_region_weighted(const int32_t* labels, const void* raw, int r
                                    clx_stream stream) {
   const char* who = "clx_region_weighted";
   CLX_REQUIRE(labels && raw && out && bad, "%s: null pointer", who);
-  CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "%s: raw_type must be 0 (f32), 1 (f64) or 2 (i32)", who);
-  CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "%s: nid must lie in [1, 2^24]", who);
+  if (require_raw_channel(who, raw_type, nid) != CLX_OK) return CLX_ERR_ARG;
   CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "%s: bad shape", who);
   const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
   CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "%s: Z * Y * X must be below 2^32", who);
@@ -301,19 +278,12 @@ extern "C" int clx_region_weighted(const int32_t* labels, const void* raw, int r
   WeightedArgs a;
   a.lab = labels; a.peak_keys = peak_keys;
   a.npix = npix; a.ntiles = t.ntiles; a.tiles_per_block = t.per_block;
-  a.bound = (1ll << 62) >> bit_length((unsigned long long)npix);
-  a.vec_lab = ((uintptr_t)labels & 15) == 0; a.vec_raw = ((uintptr_t)raw & 15) == 0;
+  a.bound = value_bound(npix);
+  a.vec_lab = aligned16(labels); a.vec_raw = aligned16(raw);
   a.Y = Y; a.X = X; a.nid = nid; a.shift = shift;
   a.out = out; a.bad = bad;
-  const long long words = (long long)nid * NW;
-  const long long iblocks = (words + 255) / 256;
-  weighted_init<<<(int)(iblocks < INIT_GRID ? iblocks : INIT_GRID), 256, 0, st>>>(out, bad, words);
-  if (raw_type == CLX_RAW_F32)
-    launch_weighted<float>(a, raw, Z > 1, t.grid, st);
-  else if (raw_type == CLX_RAW_F64)
-    launch_weighted<double>(a, raw, Z > 1, t.grid, st);
-  else
-    launch_weighted<int>(a, raw, Z > 1, t.grid, st);
+  launch_table_init<NW, W_PEAK>(out, bad, nid, st);
+  launch_for_raw(raw_type, [&](auto v) { launch_weighted<decltype(v)>(a, raw, Z > 1, t.grid, st); });
   CLX_CHECK_LAUNCH(who);
   return CLX_OK;
 }

@@ -1,7 +1,7 @@
 """Measure stage: the per-object table users take from ``skimage.measure.regionprops`` on the host —
 area, bounding box, centroid, covariance, equivalent diameter and mean / min / max intensity per raw
 channel — from integer sums gathered in one pass over the label map on the device
-(``csrc/measure.hip``: ``clx_region_moments``, ``clx_region_intensity``).  The sums are exact integers, so
+(``csrc/region_moments.hip``: ``clx_region_moments``, ``clx_region_intensity``).  The sums are exact integers, so
 the only rounding in a column is its final division.  On request also what an object's BOUNDARY gives: the faces it
 shares with every other object (``contact_pairs``: the region adjacency graph), with the background and the image edge,
 and in 2-D its border pixels and perimeter (``clx_region_contacts``, ``clx_region_perimeter``), all integer counts too.

@@ -47,6 +47,16 @@ def test_kernel_sources_have_no_preprocessor_conditionals():
     assert not found, "\n".join(found)
 
 
+def test_measure_helpers_are_defined_once():
+    # the value helpers and the run rule of the measure kernels have one copy (region_sums.h, region_scan.h)
+    csrc = os.path.join(ROOT, "cellulus_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    text = {n: open(os.path.join(csrc, n), encoding="utf-8").read() for n in names}
+    for piece in ("order_key(float", "struct alignas(16) Raw4", "bool quantise(T", "int bit_length(", "__shfl_up(l[0]"):
+        assert [n for n in names if piece in text[n]] in (["region_sums.h"], ["region_scan.h"]), piece
+    assert [n for n in names if "enum { RAW_F32" in text[n]] == []
+
+
 def test_compile_command_ignores_the_environment(monkeypatch):
     from cellulus_amd import _build
 

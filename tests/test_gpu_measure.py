@@ -129,7 +129,7 @@ def _cases():
     touching[2:, 2:5, 1:6] = 2                      # labels meet across z, y and x
     c["3d_5x6x7"] = (touching, 3)
     c["3d_3x40x70"] = (_blobs((3, 40, 70), 12, 3), 13)
-    # the grid is capped at 1024 blocks of 1024 pixels per trip (MAX_GRID, TILE in csrc/measure.hip): 1030 x 1031 =
+    # the grid is capped at 1024 blocks of 1024 pixels per trip (MAX_GRID, TILE in csrc/region_scan.h): 1030 x 1031 =
     # 1 061 930 pixels are 1038 tiles, so blocks take two tiles each
     c["second_trip_1030x1031"] = (_blobs((1030, 1031), 300, 4), 301)
     return c

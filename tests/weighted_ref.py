@@ -19,7 +19,7 @@ MOMENTS = ("sum_qz", "sum_qy", "sum_qx", "sum_qzz", "sum_qyy", "sum_qxx", "sum_q
 
 
 def ref_keys(raw):
-    """measure.hip's order keys of the values as uint64"""
+    """region_sums.h's order keys of the values as uint64"""
     raw = np.ascontiguousarray(raw).reshape(-1)
     if raw.dtype == np.int32:
         return (raw.view(np.uint32) ^ np.uint32(0x80000000)).astype(np.uint64)
