@@ -2,7 +2,8 @@
 (``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]
 [--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]
 [--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity]``) and the ``relate`` command
-(``python -m cellulus_amd.relate <toml> --children NAME --parents NAME [--clearance] [--tertiary NAME]``)."""
+(``python -m cellulus_amd.relate <toml> --children NAME --parents NAME [--clearance] [--tertiary NAME]``) and the ``expand``
+command (``python -m cellulus_amd.expand <toml> --source NAME [--distance D --output NAME] [--neighbours [--limit D]]``)."""
 
 import click
 import tomli
@@ -98,3 +99,22 @@ def relate(config_file, children, parents, clearance, tertiary):
     from .relate import relate_stage
 
     relate_stage(ExperimentConfig(**_load(config_file)).inference_config, children, parents, clearance=clearance, tertiary=tertiary)
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
+@click.option("--source", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose objects are grown (the nuclei)")
+@click.option("--distance", default=None, metavar="D", type=click.FloatRange(0.0),
+              help="grow every object by D pixels (Euclidean, inclusive) without letting neighbours merge; needs --output")
+@click.option("--output", default=None, metavar="NAME", help="write the grown objects (the cells) into a new dataset NAME")
+@click.option("--neighbours", is_flag=True,
+              help="write zones_bandwidth-<b>.csv and zone_pairs_bandwidth-<b>.csv: every object's zone (the pixels nearest to it), "
+                   "its reach and its neighbours, touching or not")
+@click.option("--limit", default=None, metavar="D", type=click.FloatRange(0.0),
+              help="with --neighbours: a zone reaches at most D pixels from its object [default: no limit]")
+def expand(config_file, source, distance, output, neighbours, limit):
+    from .expand import expand_stage
+
+    expand_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output=output, distance=distance,
+                 neighbours=neighbours, limit=limit)

@@ -1301,6 +1301,34 @@ int clx_region_clearance(const int32_t* a, const int32_t* b, const int32_t* dist
                          long long npix, int nid_a, unsigned long long* out, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* "expand" stage: which object is nearest (label_nearest.hip)               */
+/* ------------------------------------------------------------------------ */
+/* Nearest object: the exact Euclidean feature transform of a label map [Z][Y][X] of int32 -- for every pixel which object is
+ * nearest and how far it is: scipy's distance_transform_edt(labels == 0, return_indices=True) with a stated choice among
+ * equidistant objects, skimage's expand_labels, the Voronoi zones of the objects.  nd == 2 needs Z == 1.
+ *   object pixel  q with 0 < labels[q] < nid.  A label outside [0, nid) counts as background, is never followed as an index
+ *             and sets bit 0 of bad[0] (value 1, as in the measure kernels)
+ *   dist_sq   [Z][Y][X] int32: the smallest |p - q|^2 over the object pixels q, between pixel centres at unit spacing
+ *   nearest   [Z][Y][X] int32: the SMALLEST label among the object pixels at that distance.  An object pixel gets its own
+ *             label and 0.  The result is a function of the map alone: transposing the map transposes it
+ *   limit_sq  -1: no limit.  >= 0: a pixel whose smallest squared distance exceeds limit_sq gets nearest 0 and dist_sq
+ *             CLX_DIST_INF, as every pixel of a map without object pixels does
+ *   bad [1]   cleared by the call
+ *   workspace at least clx_label_nearest_workspace(Z*Y*X) bytes (a host-only function; 0: npix outside [1, 2^32)), 4-byte
+ *             aligned: two more int32 maps, the other side of the passes' ping-pong
+ * Every element of nearest and dist_sq is written.  Separable and exact: a pixel carries the key (d2 << 32) | id, a scan
+ * along x and min-plus passes along y (and z) take the unsigned minimum.  Integers only: the same bits in every run.
+ * The passes along y and z search outwards: their cost grows with the distance to the nearest object (at most
+ * sqrt(limit_sq)); a map with one small object and no limit is the slow case.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent, nid
+ * outside [1, 2^24], limit_sq outside [-1, 2^30), Z*Y*X >= 2^32, (Z-1)^2 + (Y-1)^2 + (X-1)^2 >= 2^30, workspace_bytes below
+ * clx_label_nearest_workspace(Z*Y*X), a workspace that is not 4-byte aligned. */
+size_t clx_label_nearest_workspace(long long npix);
+int clx_label_nearest(const int32_t* labels, int nd, int Z, int Y, int X, int nid, int limit_sq,
+                      int32_t* nearest, int32_t* dist_sq, int32_t* bad,
+                      void* workspace, size_t workspace_bytes, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
