@@ -3,7 +3,8 @@
 [--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]
 [--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity]``) and the ``relate`` command
 (``python -m cellulus_amd.relate <toml> --children NAME --parents NAME [--clearance] [--tertiary NAME]``) and the ``expand``
-command (``python -m cellulus_amd.expand <toml> --source NAME [--distance D --output NAME] [--neighbours [--limit D]]``)."""
+command (``python -m cellulus_amd.expand <toml> --source NAME [--distance D --output NAME] [--neighbours [--limit D]]``) and the
+``split`` command (``python -m cellulus_amd.split <toml> --source NAME --output NAME [--depth D] [--edge]``)."""
 
 import click
 import tomli
@@ -118,3 +119,18 @@ def expand(config_file, source, distance, output, neighbours, limit):
 
     expand_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output=output, distance=distance,
                  neighbours=neighbours, limit=limit)
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
+@click.option("--source", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose touching objects are cut apart")
+@click.option("--output", required=True, metavar="NAME", help="write the pieces into a new dataset NAME")
+@click.option("--depth", default=1.0, show_default=True, metavar="D", type=click.FloatRange(0.0),
+              help="merge a basin of the distance map into a higher neighbour where its peak stands less than D pixels above the "
+                   "neck between them; 0 keeps every basin")
+@click.option("--edge", is_flag=True, help="the image edge counts as background for the distance map")
+def split(config_file, source, output, depth, edge):
+    from .split import split_stage
+
+    split_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output, depth=depth, edge=edge)

@@ -2,7 +2,8 @@
 // clx_label_overlaps), on top of the reading frame of region_scan.h: an open-addressing table in global memory keyed by a
 // 64-bit pair (never 0), filled through a block-private table in LDS that is flushed once.  A pair that finds no slot in
 // LDS goes straight to the global table; a pair that finds none there within `probes` tries sets bit 2 of info[0] and is
-// dropped, and the caller discards the table.
+// dropped, and the caller discards the table.  What a pair's word gathers is the table's combining operation: the sum of
+// the counts (PairAdd: contacts, overlaps) or the largest value (PairMax: label_basins.hip's passes).
 #pragma once
 #include "region_scan.h"
 
@@ -25,9 +26,18 @@ __device__ __forceinline__ u64 mix64(u64 k) {   // MurmurHash3's finaliser: ids 
   return k ^ (k >> 33);
 }
 
-// n counts of `key` into the global table.  Bounded: at most o.probes slots, all inside [0, capacity); a pair that finds
+// how a value joins a pair's word, in LDS and in global memory alike
+struct PairAdd {
+  static __device__ __forceinline__ void combine(u64* word, u64 v) { atomicAdd(word, v); }
+};
+struct PairMax {
+  static __device__ __forceinline__ void combine(u64* word, u64 v) { atomicMax(word, v); }
+};
+
+// n counts (Op = PairMax: the value n) of `key` into the global table.  Bounded: at most o.probes slots, all inside [0, capacity); a pair that finds
 // neither its key nor an empty slot sets bit 2 and is dropped (the caller discards the table).  A stale read of a key
 // can only show 0 for a claimed slot, which the compare-and-swap corrects; a claimed key never changes.
+template <typename Op = PairAdd>
 __device__ void pair_to_global(const ContactsOut& o, u64 key, u64 n, u64 h) {
   unsigned int s = (unsigned int)(h >> 32) & o.mask;
   for (unsigned int i = 0; i < o.probes; ++i) {
@@ -36,22 +46,23 @@ __device__ void pair_to_global(const ContactsOut& o, u64 key, u64 n, u64 h) {
       k = atomicCAS(&o.keys[s], 0ull, key);
       if (k == 0) atomicAdd(o.info + 1, 1);
     }
-    if (k == 0 || k == key) { atomicAdd(&o.counts[s], n); return; }
+    if (k == 0 || k == key) { Op::combine(&o.counts[s], n); return; }
     s = (s + 1) & o.mask;
   }
   atomicOr(o.info, 4);
 }
 
+template <typename Op = PairAdd>
 __device__ void add_pair(u64* lkeys, u64* lcnt, const ContactsOut& o, u64 key, unsigned int n) {
   const u64 h = mix64(key);
   int s = (int)(h & (CSLOTS - 1));
   for (int i = 0; i < CPROBES; ++i) {
     u64 k = __hip_atomic_load(&lkeys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (k == 0) k = atomicCAS(&lkeys[s], 0ull, key);
-    if (k == 0 || k == key) { atomicAdd(&lcnt[s], (u64)n); return; }
+    if (k == 0 || k == key) { Op::combine(&lcnt[s], (u64)n); return; }
     s = (s + 1) & (CSLOTS - 1);
   }
-  pair_to_global(o, key, n, h);
+  pair_to_global<Op>(o, key, n, h);
 }
 
 __global__ void contacts_init(ContactsOut o, long long capacity) {

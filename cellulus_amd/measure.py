@@ -303,10 +303,10 @@ def _pair_capacity(objects):
     return max(MIN_CAPACITY, 1 << max(0, 8 * int(objects) - 1).bit_length())
 
 
-def _pair_table(device, who, name, messages, capacity, *args):
-    """A library call that fills a table of id pairs (``args``, then the slots, keys, counts and info), repeated with twice the
-    table while it reports a pair it could not place -> (a, b, count) int64, sorted by (a, b).  `capacity`: the slots of the
-    first table, ``_pair_capacity`` of the object count or of a bound on it"""
+def _pair_slots(device, who, name, messages, capacity, *args):
+    """A library call that fills a table of 64-bit pairs (``args``, then the slots, keys, values and info), repeated with twice the
+    table while it reports a pair it could not place -> (keys uint64, values int64) of the occupied slots, in slot order.
+    `capacity`: the slots of the first table, ``_pair_capacity`` of the object count or of a bound on it"""
     import torch
 
     while True:
@@ -320,10 +320,16 @@ def _pair_table(device, who, name, messages, capacity, *args):
         capacity *= 2
     slot = torch.nonzero(keys).reshape(-1)
     assert slot.numel() == used
-    k = keys[slot].cpu().numpy()
+    return keys[slot].cpu().numpy().view(np.uint64), counts[slot].cpu().numpy()
+
+
+def _pair_table(device, who, name, messages, capacity, *args):
+    """``_pair_slots`` of a table of id pairs -> (a, b, count) int64, sorted by (a, b)"""
+    k, counts = _pair_slots(device, who, name, messages, capacity, *args)
+    k = k.view(np.int64)
     order = np.argsort(k, kind="stable")                     # keys are (a << 32) | b with a < 2^24: the (a, b) order
     k = k[order]
-    return k >> 32, k & 0xFFFFFFFF, counts[slot].cpu().numpy()[order]
+    return k >> 32, k & 0xFFFFFFFF, counts[order]
 
 
 def _contacts(scene, objects):

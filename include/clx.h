@@ -1329,6 +1329,63 @@ int clx_label_nearest(const int32_t* labels, int nd, int Z, int Y, int X, int ni
                       void* workspace, size_t workspace_bytes, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* "split" stage: basins of the distance map (label_basins.hip)              */
+/* ------------------------------------------------------------------------ */
+/* Basins: a watershed of a label map [Z][Y][X] of int32 on its distance map dist_sq (clx_label_distance_sq's, or any int32 map
+ * in [0, CLX_DIST_INF]) without a flood queue -- the declumping of touching objects by shape.  nd == 2 needs Z == 1.
+ *   object pixel  p with labels[p] != 0 (negative values are objects, as in clx_label_distance_sq) and dist_sq[p] in
+ *             [0, CLX_DIST_INF].  An object pixel with another dist_sq counts as background and sets bit 1 of info[0].  Labels
+ *             are only compared with each other, never followed as an index
+ *   neighbours  the 8 (nd == 2) or 26 pixels around p that lie inside the map and are object pixels of p's label; the ends of
+ *             rows and slices never wrap
+ *   key(p)    ((u64) dist_sq[p] << 32) | (2^32 - 1 - p), p the raster index: the larger distance is higher, among equal ones
+ *             the smaller index.  No two pixels share a key
+ *   up(p)     the neighbour with the largest key if that exceeds key(p), else p: a summit
+ *   root      [Z][Y][X]: the raster index (as uint32) of the summit the chain p, up(p), up(up(p)), ... ends at;
+ *             CLX_BASIN_NONE on pixels that are no object pixels.  Every element is written
+ *   summits   [capacity]: the raster indices of the summits, in NO stated order (the caller sorts); capacity in [1, 2^30]
+ *   info [2]  cleared by the call.  [0] bit 1: a dist_sq out of range under a label; bit 2: more summits than capacity -- the
+ *             list holds `capacity` of them, root and the count are right.  [1] the exact number of summits (uint32)
+ *   workspace at least clx_label_basins_workspace(Z*Y*X) bytes (a host-only function; 0: npix outside [1, 2^32)), 4-byte
+ *             aligned: 16 status words and one more int32 map
+ * One stencil launch and seven root launches, all queued on the stream: a root launch follows at most 64 links per pixel
+ * between two buffers (no launch reads a word it writes), which multiplies the resolved length of every chain by 65, and
+ * 65^7 > 2^32; a status word lets the launches after the last needed one return at once.  Integers only: the same bits in
+ * every run, the order of the summit list aside.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent,
+ * Z*Y*X >= 2^32, capacity outside [1, 2^30], workspace_bytes below clx_label_basins_workspace(Z*Y*X), a workspace that is not
+ * 4-byte aligned. */
+#define CLX_BASIN_NONE (-1)
+size_t clx_label_basins_workspace(long long npix);
+int clx_label_basins(const int32_t* labels, const int32_t* dist_sq, int nd, int Z, int Y, int X, int capacity,
+                     int32_t* root, int32_t* summits, int32_t* info,
+                     void* workspace, size_t workspace_bytes, clx_stream stream);
+/* Passes: for every two basins of one label that have neighbouring pixels the height of the pass between them.
+ *   pair      neighbouring pixels p, q (8 / 26, inside the map) with labels[p] == labels[q], root[p] != root[q] and neither root
+ *             CLX_BASIN_NONE; every such pair is visited once, through the 4 / 13 forward offsets
+ *   key       ((u64) min(root[p], root[q]) << 32) | max(root[p], root[q]); never 0, as the larger root is >= 1
+ *   value     the maximum over the pair's pixel pairs of min(dist_sq[p], dist_sq[q])
+ * Output: clx_region_contacts' open-addressing table of `capacity` slots (a power of two in [1024, 2^28]) under the same
+ * contract, with the maximum in place of the count: keys [capacity] (0: empty slot), values [capacity], info [2] ([0] bit 2: a
+ * pair could not be placed -- discard the table and repeat with a larger capacity; [1] occupied slots).  The entry point
+ * initialises all three.  root is clx_label_basins' of the same labels and dist_sq; its values are compared and never
+ * followed.  The set of (key, value) is determined by the maps: integer maxima only.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent,
+ * Z*Y*X >= 2^32, capacity not a power of two in [1024, 2^28]. */
+int clx_basin_passes(const int32_t* labels, const int32_t* dist_sq, const int32_t* root, int nd, int Z, int Y, int X,
+                     int capacity, unsigned long long* keys, unsigned long long* values, int32_t* info, clx_stream stream);
+/* Relabel: out[p] = ids[i] where root[p] == summits[i], 0 where root[p] is CLX_BASIN_NONE.  (summits, ids, n): per summit the
+ * id (>= 1) the caller gave it, n in [0, 2^30]; the list is scattered into a map of npix int32 in the workspace first.
+ *   bad [1]   cleared by the call.  bit 0: a summit outside [0, npix), not followed; bit 1: a root that is no summit of the list
+ *             or lies outside the map; that pixel gets 0
+ *   workspace at least clx_label_basins_workspace(npix) bytes, 4-byte aligned
+ * Every element of out is written.
+ * Refused (CLX_ERR_ARG) before any launch: null pointers (summits and ids may be null with n == 0), npix outside [1, 2^32), n
+ * outside [0, 2^30], workspace_bytes below clx_label_basins_workspace(npix), a workspace that is not 4-byte aligned. */
+int clx_basin_relabel(const int32_t* root, long long npix, const int32_t* summits, const int32_t* ids, int n,
+                      int32_t* out, int32_t* bad, void* workspace, size_t workspace_bytes, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
