@@ -134,3 +134,25 @@ def split(config_file, source, output, depth, edge):
     from .split import split_stage
 
     split_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output, depth=depth, edge=edge)
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
+@click.option("--seeds", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose objects are grown (the nuclei)")
+@click.option("--output", required=True, metavar="NAME", help="write the territories into a new dataset NAME")
+@click.option("--mask", default=None, metavar="NAME",
+              help="dataset of the segmentation container whose non-zero pixels the seeds may grow into [default: everywhere]")
+@click.option("--channel", default=None, metavar="K", type=click.IntRange(0),
+              help="channel of the raw dataset that guides the growth: a step costs the difference in grey levels [default: flat]")
+@click.option("--levels", default=256, show_default=True, metavar="N", type=click.IntRange(2, 65536),
+              help="with --channel: grey levels between the smallest and the largest value under the mask and the seeds")
+@click.option("--regularisation", default=1, show_default=True, metavar="R", type=click.IntRange(0, 65535),
+              help="price of distance: a step costs R times 3, 4 or 5 (face, edge, corner) plus the difference in grey levels")
+@click.option("--limit", default=None, metavar="COST", type=click.IntRange(0, 2 ** 30 - 1),
+              help="a territory reaches no pixel whose cheapest path costs more than COST [default: no limit]")
+def propagate(config_file, seeds, output, mask, channel, levels, regularisation, limit):
+    from .propagate import propagate_stage
+
+    propagate_stage(ExperimentConfig(**_load(config_file)).inference_config, seeds, output, mask=mask, channel=channel, levels=levels,
+                    regularisation=regularisation, limit=limit)

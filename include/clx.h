@@ -1386,6 +1386,53 @@ int clx_basin_relabel(const int32_t* root, long long npix, const int32_t* summit
                       int32_t* out, int32_t* bad, void* workspace, size_t workspace_bytes, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* "propagate" stage: seeds grown inside a mask, guided by an image          */
+/* (label_propagate.hip)                                                     */
+/* ------------------------------------------------------------------------ */
+/* Propagation: for every pixel of three maps [Z][Y][X] the seed that reaches it on the cheapest path and that path's cost --
+ * CellProfiler's IdentifySecondaryObjects "Propagation", skimage's watershed(image, markers, mask=...), without a flood queue
+ * and with a stated choice among equal costs.  nd == 2 needs Z == 1.
+ *   seeds     int32.  A pixel with 0 < seeds[p] < nid is a SEED pixel.  An id outside [0, nid) counts as a non-seed pixel of
+ *             label 0, is never followed as an index and sets bit 0 of info[0] (value 1)
+ *   mask      uint8, or NULL (all allowed).  A non-seed pixel is ALLOWED iff mask[p] != 0.  Seed pixels are always sources and
+ *             keep their label, in or out of the mask
+ *   weight    int32 in [0, 65535], or NULL (flat): the image in grey levels.  A weight outside that range under an allowed or
+ *             seed pixel makes the pixel impassable -- no source and not allowed -- and sets bit 1 of info[0] (value 2)
+ *   neighbours  the 8 (nd == 2) or 26 pixels around p inside the map; the ends of rows and slices never wrap
+ *   step      from p to a neighbour q that is an allowed non-seed pixel: reg * a(p, q) + |weight[p] - weight[q]|, a = 3 for a
+ *             face neighbour, 4 for an edge neighbour, 5 for a corner neighbour (the <3, 4, 5> chamfer); reg in [0, 65535]
+ *   path      starts at a seed pixel and makes steps; its cost is their sum.  Paths costlier than `limit` do not exist; limit in
+ *             [0, 2^30), -1: 2^30 - 1
+ *   key       every pixel holds the key (cost, id) of its best path: the smaller cost wins, among equal costs the smaller seed
+ *             id.  A seed pixel has (0, its label); a pixel that no path reaches has owner 0 and cost CLX_COST_INF.  Zero-cost
+ *             steps are legal.  The keys are the least fixed point of key[q] = min(key[q], key[p] + step(p, q)): a function of
+ *             the inputs alone; transposing the inputs transposes them
+ *   owner, cost  [Z][Y][X] int32: the key.  While info[1] != 0 they hold an intermediate state
+ *   rounds    1 .. 64: the relaxation rounds this call queues on the stream at most, without any host synchronisation
+ *   resume    0: the call initialises owner, cost and the workspace from the seeds.  1: it continues from the state a call
+ *             with the same other arguments left in owner, cost and workspace, and initialises nothing but info
+ *   info [3]  cleared by the call.  [0] the two bits above (resume == 0 only).  [1] the tiles that changed in the last round of
+ *             the call: 0 means the fixed point is reached and owner / cost hold the result.  [2] the rounds of this call in
+ *             which some tile changed; summed over the calls it is the same in every run, whatever `rounds` each call was given
+ *   workspace at least clx_label_propagate_workspace(nd, Z, Y, X) bytes (a host-only function; 0: a shape the call would
+ *             refuse), 4-byte aligned: 16 head words, 64 round counters, two more int32 maps and two flag bytes per tile
+ * A round is one launch: a block takes a tile of 1024 pixels (64 x 16, or 16 x 8 x 8) with a halo of one pixel, relaxes it in
+ * LDS on whole 64-bit keys, at most 32 sweeps, and writes its interior to the other pair of planes (owner / cost and the
+ * workspace's alternate: no launch reads a word it writes).  A tile works only if it or a neighbour tile changed in the round
+ * before; the rounds after the fixed point return at once.  No block waits for another.  Integer minima only: the same bits
+ * and the same rounds in every run.  cost <= 2^30 and a step < 2^19: a candidate fits 32 bits.
+ * Refused (CLX_ERR_ARG) before any launch: null seeds, owner, cost, info or workspace, nd not 2 or 3, nd == 2 with Z != 1, a
+ * non-positive extent, nid outside [1, 2^24], reg outside [0, 65535], limit outside [-1, 2^30), rounds outside [1, 64], resume
+ * not 0 or 1, Z*Y*X >= 2^32, workspace_bytes below clx_label_propagate_workspace(nd, Z, Y, X), a workspace that is not 4-byte
+ * aligned. */
+#define CLX_COST_INF CLX_DIST_INF
+size_t clx_label_propagate_workspace(int nd, int Z, int Y, int X);
+int clx_label_propagate(const int32_t* seeds, const uint8_t* mask, const int32_t* weight,
+                        int nd, int Z, int Y, int X, int nid, int reg, int limit, int rounds, int resume,
+                        int32_t* owner, int32_t* cost, int32_t* info,
+                        void* workspace, size_t workspace_bytes, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
