@@ -347,9 +347,13 @@ __global__ __launch_bounds__(256) void ms_iterate_grid_kernel(
 #pragma unroll
     for (int c = 0; c < ND; ++c) sum[c] = 0.0;
     int cnt = 0;
-    const int cx = (int)floor((mean[0] - ox) * inv_h);
-    const int cy = (int)floor((mean[1] - oy) * inv_h);
-    const int cz = (ND == 3) ? (int)floor((mean[2] - oz) * inv_h) : 0;
+    // the mean's cell, held to [-2, n + 1] BEFORE the conversion: a mean far outside the grid (a seed at 1e300, +inf) would
+    // convert to INT_MAX, and cy + 1 below would overflow — the compiler, free to assume it does not, tested cy > -2
+    // instead of cy + 1 >= 0 and let the row INT_MIN through to cell_start.  Cells -2 and n + 1 have no neighbour in the grid.
+    auto cell_of = [](double v, int n) { return (int)fmin(fmax(floor(v), -2.0), (double)n + 1.0); };
+    const int cx = cell_of((mean[0] - ox) * inv_h, nx);
+    const int cy = cell_of((mean[1] - oy) * inv_h, ny);
+    const int cz = (ND == 3) ? cell_of((mean[2] - oz) * inv_h, nz) : 0;
     const int x0 = max(cx - 1, 0), x1 = min(cx + 1, nx - 1);
     if (x0 <= x1) {
       for (int zz = (ND == 3 ? cz - 1 : 0); zz <= (ND == 3 ? cz + 1 : 0); ++zz) {

@@ -668,7 +668,8 @@ int clx_ms_iterate(const double* fit, int nfit, const double* seeds, int nseeds,
 /* Same as clx_ms_iterate with the fit points bucketed in a uniform grid (for large
  * nfit): fit_sorted is sorted by cell id ((z*ny + y)*nx + x, cell coordinate =
  * floor((p - origin) / cell) per dim, cell >= bandwidth), cell_start (nx*ny*nz + 1)
- * holds each cell's first row.  `origin` is a HOST pointer to ND doubles. */
+ * holds each cell's first row.  `origin` is a HOST pointer to ND doubles.  A seed may lie
+ * outside the grid, at any distance (beyond `bandwidth` of every point: count 0, centre = seed). */
 int clx_ms_iterate_grid(const double* fit_sorted, int nfit, const int* cell_start,
                         const double* origin, double cell, int nx, int ny, int nz,
                         const double* seeds, int nseeds, int ND, double bandwidth,
