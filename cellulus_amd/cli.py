@@ -138,6 +138,20 @@ def split(config_file, source, output, depth, edge):
 
 @click.command()
 @click.argument("config_file", type=click.Path(exists=True))
+@click.option("--source", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose objects' holes are closed")
+@click.option("--output", required=True, metavar="NAME", help="write the repaired objects into a new dataset NAME")
+@click.option("--max-size", default=None, metavar="N", type=click.IntRange(0),
+              help="leave holes of more than N pixels open; 0 fills nothing and only lists the holes [default: no cap]")
+@click.option("--planewise", is_flag=True, help="3-D: fill every slice as a 2-D map of its own (cavities open along z)")
+def fill(config_file, source, output, max_size, planewise):
+    from .fill import fill_stage
+
+    fill_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output, max_size=max_size, planewise=planewise)
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
 @click.option("--seeds", required=True, metavar="NAME",
               help="label dataset of the segmentation container whose objects are grown (the nuclei)")
 @click.option("--output", required=True, metavar="NAME", help="write the territories into a new dataset NAME")

@@ -12,48 +12,9 @@
 // made by the values returned from the atomics).
 #include <stdlib.h>
 #include "clx_common.h"
+#include "union_find.h"                 // uf_find, uf_find_halve, uf_union
 
 namespace {
-
-
-__device__ __forceinline__ int uf_find(const int* L, int a) {
-  int p = L[a];
-  while (p != a) { a = p; p = L[a]; }
-  return a;
-}
-
-// find with path halving: every visited node is re-pointed at its grandparent.  A plain store is
-// enough: only non-roots are written (a root is changed by the atomicMin of a union alone), and any
-// ancestor is a valid parent, so a lost or stale write merely leaves a longer path.
-__device__ __forceinline__ int uf_find_halve(int* L, int a) {
-  int p = L[a];
-  while (p != a) {
-    const int gp = L[p];
-    if (gp != p) L[a] = gp;
-    a = p;
-    p = gp;
-  }
-  return a;
-}
-
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-  bool done;
-  do {
-    a = uf_find_halve(L, a);
-    b = uf_find_halve(L, b);
-    if (a < b) {
-      const int old = atomicMin(&L[b], a);
-      done = (old == b);
-      b = old;
-    } else if (b < a) {
-      const int old = atomicMin(&L[a], b);
-      done = (old == a);
-      a = old;
-    } else {
-      done = true;
-    }
-  } while (!done);
-}
 
 // Wave w of the grid owns 64 consecutive pixels of one row ("segment").  Returns the pixel index
 // of lane 0, the row's first pixel index and x of this lane; valid = inside the row.

@@ -1434,6 +1434,50 @@ int clx_label_propagate(const int32_t* seeds, const uint8_t* mask, const int32_t
                         void* workspace, size_t workspace_bytes, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* "fill" stage: holes inside the objects of a label map, closed             */
+/* (label_holes.hip)                                                         */
+/* ------------------------------------------------------------------------ */
+/* Holes: CellProfiler's FillObjects / centrosome's fill_labeled_holes ("surrounded by a single object") on a stored label map,
+ * for all objects in one call, with a census of the holes.
+ *   input     one int32 map [Z][Y][X], 2-D (nd == 2, Z == 1) or 3-D.  Every non-zero value is an OBJECT pixel; the value is
+ *             compared and never used as an index, so no nid argument is needed.  Value 0 is BACKGROUND
+ *   neighbours and components  background pixels are FACE neighbours (4 in 2-D, 6 in 3-D): the complement of the 8 /
+ *             26-connectivity the objects have in clx_cc_label_filter.  The ends of rows and slices never wrap.  A COMPONENT
+ *             is a maximal face-connected set of background pixels
+ *   planewise  with planewise == 1 (3-D only) z neighbours do not exist, and every slice is a 2-D map of its own
+ *             (CellProfiler's planewise fill): the useful mode for stacks whose cavities are open along z
+ *   reaching the border  a component REACHES THE BORDER iff one of its pixels has x in {0, X-1} or y in {0, Y-1}; in 3-D
+ *             without planewise, z in {0, Z-1} counts as well
+ *   hole      a component is a HOLE of label L iff it does not reach the border and every object pixel that is a face neighbour
+ *             of one of its pixels carries the same value L.  Edge and corner neighbours do not count (centrosome's
+ *             fill_labeled_holes rule: "surrounded by a single object")
+ *   not a hole  a gap that touches two labels is not a hole and stays background; so does a ring between an object and a
+ *             different object nested inside it.  A hole's FIRST pixel is its smallest raster index, its AREA its pixel count
+ *   out       [Z][Y][X] int32, every element written: out[p] = labels[p] on object pixels; on a background pixel L if the
+ *             pixel's component is a hole of L with area <= max_size (max_size == -1: no cap), otherwise 0.  With
+ *             max_size == 0 nothing changes and the call is a census of the holes
+ *   holes     [capacity][4] int32: for every hole, capped or not, one row (first, owner, area, kept); kept = 1: the hole
+ *             exceeded max_size and was left open.  The order of the rows is unspecified; the host sorts them by first
+ *   info [4]  cleared by the call.  [0] the number of holes found: it may exceed capacity -- rows beyond capacity are dropped,
+ *             out is complete regardless.  [1] the number of pixels filled.  [2] the number of background components.
+ *             [3] reserved, 0
+ *   workspace at least clx_label_holes_workspace(nd, Z, Y, X) bytes (a host-only function; 0: a shape the call refuses), 4-byte
+ *             aligned: 16 bytes per pixel -- the parent plane of a union-find over the background's horizontal runs, and at
+ *             a component's root its area with the border bit, and the smallest and largest value among its face neighbours
+ * Five plain launches on the stream and no host synchronisation: runs, link (lock-free atomicMin unions; only overlap in x
+ * links, never a diagonal), flatten (with the border bits), reduce (the attributes of the components off the border), fill.  No
+ * block waits for another; integers only; ids are 32-bit raster indices.  out, info and the set of rows are a function of the
+ * input alone.
+ * Refused (CLX_ERR_ARG) before any launch: null labels, out, info or workspace, null holes with capacity > 0, nd not 2 or 3,
+ * nd == 2 with Z != 1, planewise not 0 or 1 or set with nd == 2, a non-positive extent, Z*Y*X >= 2^31, max_size < -1,
+ * capacity < 0, workspace_bytes below clx_label_holes_workspace(nd, Z, Y, X), a workspace that is not 4-byte aligned,
+ * out == labels. */
+size_t clx_label_holes_workspace(int nd, int Z, int Y, int X);
+int clx_label_holes(const int32_t* labels, int nd, int Z, int Y, int X, int planewise, long long max_size,
+                    int capacity, int32_t* out, int32_t* holes, int32_t* info,
+                    void* workspace, size_t workspace_bytes, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
