@@ -4,7 +4,10 @@
 [--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity]``) and the ``relate`` command
 (``python -m cellulus_amd.relate <toml> --children NAME --parents NAME [--clearance] [--tertiary NAME]``) and the ``expand``
 command (``python -m cellulus_amd.expand <toml> --source NAME [--distance D --output NAME] [--neighbours [--limit D]]``) and the
-``split`` command (``python -m cellulus_amd.split <toml> --source NAME --output NAME [--depth D] [--edge]``)."""
+``split`` command (``python -m cellulus_amd.split <toml> --source NAME --output NAME [--depth D] [--edge]``) and the ``fill``
+command (``python -m cellulus_amd.fill <toml> --source NAME --output NAME [--max-size N] [--planewise]``) and the ``propagate``
+command (``python -m cellulus_amd.propagate <toml> --seeds NAME --output NAME [--mask NAME] [--channel K [--levels 256]]
+[--regularisation 1] [--limit COST]``)."""
 
 import click
 import tomli

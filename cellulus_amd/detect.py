@@ -13,19 +13,12 @@ import torch
 from tqdm import tqdm
 
 from . import parallel
+from ._stage import _create
 from .configs.inference_config import InferenceConfig
 from .datasets.meta_data import DatasetMetaData
 from .utils import zarr_io
 from .utils.mean_shift import mean_shift_on_device
 from .utils.otsu import threshold_otsu
-
-
-def _create(f, name, shape, dtype, nd):
-    ds = f.create_dataset(name, shape=shape, dtype=dtype)
-    ds.attrs["axis_names"] = ["s", "c"] + ["t", "z", "y", "x"][-nd:]
-    ds.attrs["resolution"] = (1,) * nd
-    ds.attrs["offset"] = (0,) * nd
-    return ds
 
 
 def peak_local_max(image):

@@ -26,55 +26,32 @@ stage's files.
 """
 
 import math
-import numbers
-from fractions import Fraction
 
 import numpy as np
 import torch
 
-from . import _clx
-from .measure import DISTANCE_CHANGED, FLAGS, LABELS_CHANGED, LABELS_OUT_OF_RANGE, _contacts, _scene, _Scene
-from .measure_columns import _AXES, DIST_INF, _exact_div, _format, _sqrt_ratio
-from .relate import _write_csv
+from . import _stage
+from .measure import FLAGS, LABELS_OUT_OF_RANGE, _check_map, _contacts, _in_type_of, _inscribed_of, _result_scene, _scene, _workspace
+from .measure_columns import DIST_INF, _exact_div, _extents, _raster_columns, _real_fraction, _sqrt_ratio
 
 
 def _limit_sq(limit, who, name="limit"):
     """``floor(limit²)``, formed exactly, of a real distance >= 0; -1 (no limit) for None"""
-    if limit is None:
+    exact = _real_fraction(limit, who, name, none=True)
+    if exact is None:
         return -1
-    if isinstance(limit, bool) or not isinstance(limit, (numbers.Real, np.integer, np.floating)):
-        raise TypeError(f"{who}: {name} must be a real number or None, got {type(limit).__name__}")
-    if isinstance(limit, (float, np.floating)) and not math.isfinite(limit):
-        raise ValueError(f"{who}: {name} must be finite, got {limit!r}")
-    exact = Fraction(float(limit)) if isinstance(limit, np.floating) else Fraction(limit)
-    if exact < 0:
-        raise ValueError(f"{who}: {name} must be >= 0, got {limit!r}")
     limit_sq = math.floor(exact ** 2)
     if limit_sq >= DIST_INF:
         raise ValueError(f"{who}: the square of {name} must be below 2^30, got {limit!r}")
     return limit_sq
 
 
-def _check_map(labels, who):
-    """the checks on a label map that need no device: an array or a tensor of integers, 2-D or 3-D"""
-    if not torch.is_tensor(labels) and not isinstance(labels, np.ndarray):
-        raise TypeError(f"{who}: labels must be an array or a tensor, got {type(labels).__name__}")
-    if ((labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool) if torch.is_tensor(labels)
-            else labels.dtype.kind not in "ui"):
-        raise TypeError(f"{who}: labels must be integers, got {labels.dtype}")
-    if labels.ndim not in (2, 3):
-        raise ValueError(f"{who}: labels must be 2-D or 3-D, got {labels.ndim} dimensions")
-
-
 def _nearest_maps(scene, limit_sq):
     """one clx_label_nearest call -> (nearest, dist_sq), flat int32 device tensors"""
     npix = scene.lab.numel()
-    nbytes = int(_clx.load().clx_label_nearest_workspace(npix))
-    if nbytes == 0:
-        raise ValueError(f"{scene.who}: the map must have fewer than 2^32 pixels")
+    workspace, nbytes = _workspace(scene, "clx_label_nearest_workspace", npix)
     nearest = torch.empty(npix, dtype=torch.int32, device=scene.device)
     dist = torch.empty(npix, dtype=torch.int32, device=scene.device)
-    workspace = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=scene.device)
     scene.call("clx_label_nearest", {1: LABELS_OUT_OF_RANGE}, scene.lab, scene.nd, scene.Z, scene.Y, scene.X, scene.nid, limit_sq,
                nearest, dist, FLAGS, workspace, nbytes)
     return nearest, dist
@@ -113,9 +90,7 @@ def expand_labels(labels, distance, device=None):
     if distance is None:
         raise TypeError("expand_labels: distance must be a real number, got None")
     scene, maps = _nearest(labels, distance, device, "expand_labels", "distance")
-    if torch.is_tensor(labels):
-        return labels.clone() if maps is None else maps[0].reshape(scene.spatial).to(device=labels.device, dtype=labels.dtype)
-    return labels.copy() if maps is None else maps[0].reshape(scene.spatial).cpu().numpy().astype(labels.dtype)
+    return _in_type_of(labels, scene, None if maps is None else maps[0])
 
 
 def zone_columns(label, area, zone_area, rows, a, b, faces, edge_faces, shape):
@@ -131,9 +106,7 @@ def zone_columns(label, area, zone_area, rows, a, b, faces, edge_faces, shape):
     pair: ``label_a``, ``label_b``, ``faces``: the rows given, sorted by (a, b).
     Host only; the module's docstring has the definitions."""
     who = "zone_columns"
-    nd = len(shape)
-    if nd not in (2, 3):
-        raise ValueError(f"{who}: shape must have 2 or 3 extents, got {nd}")
+    _extents(shape, who)
     label, area, zone_area, edge_faces = (np.asarray(v).astype(np.int64).reshape(-1) for v in (label, area, zone_area, edge_faces))
     a, b, faces = (np.asarray(v).astype(np.int64).reshape(-1) for v in (a, b, faces))
     n = len(label)
@@ -163,10 +136,7 @@ def zone_columns(label, area, zone_area, rows, a, b, faces, edge_faces, shape):
     table = {"label": label, "area": area, "zone_area": zone_area,
              "zone_fraction": _exact_div(area.astype(object), zone_area.astype(object)),
              "zone_reach": np.array([_sqrt_ratio(r[0], 1) for r in rows], dtype=np.float64)}
-    index = np.array([r[1] for r in rows], dtype=np.int64)
-    where = np.unravel_index(index, tuple(int(v) for v in shape)) if n else (np.zeros(0, dtype=np.int64),) * nd
-    for axis, c in zip(_AXES[3 - nd:], where):
-        table[f"zone_reach_{axis}"] = np.asarray(c, dtype=np.int64)
+    table.update(_raster_columns("zone_reach", np.array([r[1] for r in rows], dtype=np.int64), shape, who))
     table["zone_dist_sq_mean"] = _exact_div([r[2] for r in rows], zone_area.astype(object))
     table.update({"num_neighbours": neighbours, "zone_border": border, "zone_border_open": towards_none - edge_faces})
     return table, {"label_a": a, "label_b": b, "faces": faces}
@@ -195,11 +165,8 @@ def zone_table(labels, limit=None, device=None):
         return zone_columns(none, none, none, np.zeros((0, 3), dtype=np.int64), none, none, none, none, scene.spatial)
     nearest, dist = maps
     present = scene.present
-    zones = _Scene(scene.who, nearest, scene.device, scene.nd, scene.spatial, scene.nid).measured()
-    if not np.array_equal(zones.present, present):
-        raise ValueError(LABELS_CHANGED.format(who=scene.who))
-    rows = zones.ids(3)
-    zones.call("clx_region_inscribed", {1: LABELS_OUT_OF_RANGE, 2: DISTANCE_CHANGED}, nearest, dist, nearest.numel(), scene.nid, rows, FLAGS)
+    zones = _result_scene(scene, nearest)
+    rows = _inscribed_of(zones, dist)
     pairs = _contacts(zones, len(present))
     return zone_columns(present, scene.area[present], zones.area[present], rows.cpu().numpy()[present], *pairs,
                         _edge_faces(nearest, scene)[present], scene.spatial)
@@ -213,11 +180,6 @@ def expand_stage(inference_config, source, output=None, distance=None, neighbour
     ``zones_bandwidth-<b>.csv`` and ``zone_pairs_bandwidth-<b>.csv`` in the working directory -- a header line, then ``sample``
     and the table's columns, floats as ``%.17g``; the pair file has the pairs of two zones (``label_a > 0``).  At least one of
     the two is asked for.  Rank 0 works alone under torch.distributed."""
-    from . import parallel
-    from .datasets.meta_data import DatasetMetaData
-    from .train import _require_hip_device
-    from .utils import zarr_io
-
     who = "expand_stage"
     if not isinstance(source, str) or not source:
         raise ValueError(f"{who}: source must be the name of a dataset, got {source!r}")
@@ -231,40 +193,22 @@ def expand_stage(inference_config, source, output=None, distance=None, neighbour
         raise ValueError(f"{who}: limit belongs to neighbours")
     _limit_sq(distance, who, "distance")
     _limit_sq(limit, who)
-    if parallel.rank() != 0:
+    stage = _stage.begin(who, inference_config)
+    if stage is None:
         return
-    meta = DatasetMetaData.from_dataset_config(inference_config.dataset_config)
-    nd = meta.num_spatial_dims
-    device = _require_hip_device(inference_config.device)
-    if parallel.world_size() > 1:
-        device = torch.device("cuda", torch.cuda.current_device())
-    path = inference_config.segmentation_dataset_config.container_path
-    f = zarr_io.open(path, "a" if output else "r")
-    if source not in f:
-        raise ValueError(f"{who}: no dataset {source!r} in {path}")
-    if output is not None and output in f:
-        raise ValueError(f"{who}: a dataset {output!r} exists in {path} already")
-    ds_source, ds_output = f[source], None
-    if output:
-        ds_output = f.create_dataset(output, shape=(meta.num_samples, inference_config.num_bandwidths, *meta.spatial_array), dtype=np.uint16)
-        ds_output.attrs["axis_names"] = ["s", "c"] + ["t", "z", "y", "x"][-nd:]
-        ds_output.attrs["resolution"] = (1,) * nd
-        ds_output.attrs["offset"] = (0,) * nd
-    for bandwidth in range(inference_config.num_bandwidths):
-        headers, lines = [None, None], ([], [])
-        for sample in range(meta.num_samples):
-            labels = ds_source[sample, bandwidth].astype(np.int32)
-            if ds_output is not None:
-                ds_output[sample, bandwidth] = expand_labels(labels, distance, device).astype(np.uint16)
-            for k, table in enumerate(zone_table(labels, limit, device) if neighbours else ()):
-                headers[k] = headers[k] or ["sample"] + list(table)
-                columns = list(table.values())
-                for i in range(len(columns[0])):
-                    if k == 0 or columns[0][i] > 0:
-                        lines[k].append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
-        if neighbours:
-            _write_csv(f"zones_bandwidth-{bandwidth}.csv", headers[0], lines[0])
-            _write_csv(f"zone_pairs_bandwidth-{bandwidth}.csv", headers[1], lines[1])
+    stage.open("a" if output else "r", source)
+    if output is not None:
+        stage.refuse_existing(output)
+    ds_source = stage.f[source]
+    ds_output = stage.create(output) if output else None
+
+    def per_sample(sample, bandwidth):
+        labels = ds_source[sample, bandwidth].astype(np.int32)
+        if ds_output is not None:
+            ds_output[sample, bandwidth] = expand_labels(labels, distance, stage.device).astype(np.uint16)
+        return zone_table(labels, limit, stage.device) if neighbours else ()
+
+    stage.run(per_sample, ("zones", "zone_pairs") if neighbours else (), keep={"zone_pairs": lambda pairs: pairs["label_a"] > 0})
 
 
 if __name__ == "__main__":

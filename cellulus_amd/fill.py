@@ -31,12 +31,9 @@ import numbers
 import numpy as np
 import torch
 
-from . import _clx
-from .expand import _check_map
-from .measure import LABELS_CHANGED, _scene, _Scene
-from .measure_columns import _AXES, _format
-from .relate import _write_csv
-from .split import _in_type_of
+from . import _clx, _stage
+from .measure import _check_map, _in_type_of, _result_scene, _scene, _workspace
+from .measure_columns import _extents, _raster_columns
 
 MAX_HOLES = (1 << 31) - 1               # clx_label_holes: capacity is an int
 
@@ -65,22 +62,14 @@ def hole_columns(first, owner, area, kept, shape):
     around the hole), ``first_z/_y/_x`` (2-D: y and x; the hole's first pixel in raster order), ``area`` and ``filled`` (0: the
     hole exceeded ``max_size`` and was left open); int64.  ``shape`` is the map's 2 or 3 extents.  Host only."""
     who = "hole_columns"
-    nd = len(shape)
-    if nd not in (2, 3):
-        raise ValueError(f"{who}: shape must have 2 or 3 extents, got {nd}")
+    _extents(shape, who)
     first, owner, area, kept = (np.asarray(v).astype(np.int64).reshape(-1) for v in (first, owner, area, kept))
     n = len(first)
     if not len(owner) == len(area) == len(kept) == n:
         raise ValueError(f"{who}: first, owner, area and kept must have one row per hole")
     if n and (first.min() < 0 or first.max() >= int(np.prod(shape)) or area.min() < 1 or np.any(owner == 0) or np.any((kept != 0) & (kept != 1))):
         raise ValueError(f"{who}: needs first pixels inside a map of shape {tuple(shape)}, owners != 0, area >= 1 and kept in {{0, 1}}")
-    table = {"owner": owner}
-    where = np.unravel_index(first, tuple(int(v) for v in shape)) if n else (np.zeros(0, dtype=np.int64),) * nd
-    for axis, c in zip(_AXES[3 - nd:], where):
-        table[f"first_{axis}"] = np.asarray(c, dtype=np.int64)
-    table["area"] = area
-    table["filled"] = 1 - kept
-    return table
+    return {"owner": owner, **_raster_columns("first", first, shape, who), "area": area, "filled": 1 - kept}
 
 
 def fill_columns(label, area_before, owner, hole_area, kept):
@@ -117,11 +106,8 @@ def _holes(scene, max_size, planewise):
     short) -> (the repaired map, flat int32 on the device; the rows (first, owner, area, kept), int64 (n, 4) sorted by first, on
     the host; info as a list)"""
     npix = scene.lab.numel()
-    nbytes = int(_clx.load().clx_label_holes_workspace(scene.nd, scene.Z, scene.Y, scene.X))
-    if nbytes == 0:
-        raise ValueError(f"{scene.who}: the map must have fewer than 2^31 pixels")
+    workspace, nbytes = _workspace(scene, "clx_label_holes_workspace", scene.nd, scene.Z, scene.Y, scene.X, below="2^31")
     out = torch.empty(npix, dtype=torch.int32, device=scene.device)
-    workspace = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=scene.device)
     info = torch.empty(4, dtype=torch.int32, device=scene.device)
     capacity = min(npix, max(1024, npix // 64))
     while True:
@@ -157,9 +143,7 @@ def _fill(labels, max_size, planewise, device, who, tables=False):
         return scene, out, (hole_table_, fill_columns(none, none, none, none, none))
     present = scene.present
     table = fill_columns(present, scene.area[present], rows[:, 1], rows[:, 2], rows[:, 3])
-    after = scene if out is None else _Scene(who, out, scene.device, scene.nd, scene.spatial, scene.nid).measured()
-    if not np.array_equal(after.present, present):
-        raise ValueError(LABELS_CHANGED.format(who=who))
+    after = scene if out is None else _result_scene(scene, out)
     assert np.array_equal(after.area[present], table["area"]), f"{who}: area != area_before + filled_area"
     return scene, out, (hole_table_, table)
 
@@ -197,11 +181,6 @@ def fill_stage(inference_config, source, output, max_size=None, planewise=False)
     uint16 dataset ``output`` of that container, ``fill_table``'s rows of all samples as ``fill_bandwidth-<b>.csv`` and
     ``hole_table``'s as ``holes_bandwidth-<b>.csv`` in the working directory -- a header line, then ``sample`` and the table's
     columns, floats as ``%.17g``.  Rank 0 works alone under torch.distributed."""
-    from . import parallel
-    from .datasets.meta_data import DatasetMetaData
-    from .train import _require_hip_device
-    from .utils import zarr_io
-
     who = "fill_stage"
     if not isinstance(source, str) or not source:
         raise ValueError(f"{who}: source must be the name of a dataset, got {source!r}")
@@ -210,38 +189,21 @@ def fill_stage(inference_config, source, output, max_size=None, planewise=False)
     _max_size(max_size, who)
     if not isinstance(planewise, (bool, np.bool_)):
         raise TypeError(f"{who}: planewise must be a bool, got {type(planewise).__name__}")
-    if parallel.rank() != 0:
+    stage = _stage.begin(who, inference_config)
+    if stage is None:
         return
-    meta = DatasetMetaData.from_dataset_config(inference_config.dataset_config)
-    nd = meta.num_spatial_dims
-    _planewise(planewise, nd, who)
-    device = _require_hip_device(inference_config.device)
-    if parallel.world_size() > 1:
-        device = torch.device("cuda", torch.cuda.current_device())
-    path = inference_config.segmentation_dataset_config.container_path
-    f = zarr_io.open(path, "a")
-    if source not in f:
-        raise ValueError(f"{who}: no dataset {source!r} in {path}")
-    if output in f:
-        raise ValueError(f"{who}: a dataset {output!r} exists in {path} already")
-    ds_source = f[source]
-    ds_output = f.create_dataset(output, shape=(meta.num_samples, inference_config.num_bandwidths, *meta.spatial_array), dtype=np.uint16)
-    ds_output.attrs["axis_names"] = ["s", "c"] + ["t", "z", "y", "x"][-nd:]
-    ds_output.attrs["resolution"] = (1,) * nd
-    ds_output.attrs["offset"] = (0,) * nd
-    for bandwidth in range(inference_config.num_bandwidths):
-        headers, lines = [None, None], [[], []]
-        for sample in range(meta.num_samples):
-            labels = ds_source[sample, bandwidth].astype(np.int32)
-            scene, out, tables = _fill(labels, max_size, planewise, device, who, tables=True)
-            ds_output[sample, bandwidth] = _in_type_of(labels, scene, out).astype(np.uint16)
-            for t, table in enumerate(tables):
-                headers[t] = headers[t] or ["sample"] + list(table)
-                columns = list(table.values())
-                for i in range(len(columns[0])):
-                    lines[t].append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
-        _write_csv(f"holes_bandwidth-{bandwidth}.csv", headers[0], lines[0])
-        _write_csv(f"fill_bandwidth-{bandwidth}.csv", headers[1], lines[1])
+    _planewise(planewise, stage.nd, who)
+    stage.open("a", source)
+    stage.refuse_existing(output)
+    ds_source, ds_output = stage.f[source], stage.create(output)
+
+    def per_sample(sample, bandwidth):
+        labels = ds_source[sample, bandwidth].astype(np.int32)
+        scene, out, tables = _fill(labels, max_size, planewise, stage.device, who, tables=True)
+        ds_output[sample, bandwidth] = _in_type_of(labels, scene, out).astype(np.uint16)
+        return tables
+
+    stage.run(per_sample, ("holes", "fill"))
 
 
 if __name__ == "__main__":

@@ -37,7 +37,8 @@ def fused_stages(model, inference_config, normalization_factor, device):
     numpy for the mean-shift sub-sampling), so interleaving them changes no random number."""
     from concurrent.futures import ThreadPoolExecutor
 
-    from .detect import _create, _labels_to_host, detect_sample
+    from ._stage import _create
+    from .detect import _labels_to_host, detect_sample
     from .predict import PredictScan
     from .segment import segment_sample
     from .utils import zarr_io

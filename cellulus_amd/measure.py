@@ -67,7 +67,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _clx
+from . import _clx, _stage
 # every name of the host half stays importable from here (its two patchable constants aside: a copy would not be read)
 from .measure_columns import (BORDER_WORDS, DIST_INF, MAX_LEVELS, MAX_QUANTILES, MAX_RADIAL_WIDTH, MAX_RINGS,  # noqa: F401
                               MAX_TEXTURE_DISTANCE, MIN_LEVELS, NO_PEAK, PERIMETER_WEIGHTS, PRODUCT_WORDS, RADIAL_WEDGES,
@@ -85,6 +85,7 @@ MIN_CAPACITY, MAX_CAPACITY = 1 << 10, 1 << 28       # clx_region_contacts: slots
 TEXTURE_TABLE_BYTES = 1 << 28           # the counts table of one clx_region_cooccurrence call stays below this
 RADIAL_TABLE_BYTES = 1 << 28            # the count and isum tables of one clx_region_radial call stay below this together
 _PAIRS_FULL = 4                         # bit of info[0] of clx_region_contacts and clx_label_overlaps: a pair found no slot
+_CONTACTS_HEADER = ("sample", "label_a", "label_b", "faces")         # of contacts_bandwidth-<b>.csv, with or without rows
 
 # What a call's flag bits say.  Which bit says what is the kernel's and differs per entry point: every call has its own
 # {bit: message} table beside it, in the order its bits are looked at.
@@ -239,11 +240,61 @@ class _Scene:
         """-> (the label-aware distance map, flat int32; clx_region_inscribed's rows, int64 (nid, 3)), both on the device and
         formed once; None for a map without objects"""
         if self._inscribed is None and not self.empty:
-            dist, out = _distance_map(self, edge), self.ids(3)
-            self.call("clx_region_inscribed", {1: LABELS_OUT_OF_RANGE, 2: DISTANCE_CHANGED}, self.lab, dist, self.lab.numel(), self.nid,
-                      out, FLAGS, who="region_table")
-            self._inscribed = dist, out
+            dist = _distance_map(self, edge)
+            self._inscribed = dist, _inscribed_of(self, dist, who="region_table")
         return self._inscribed
+
+
+def _inscribed_of(scene, values, who=None):
+    """clx_region_inscribed of the scene's map and a map of ``values`` (flat int32 on the device): per id the largest value,
+    the first pixel that attains it and the sum -> int64 (nid, 3) on the device"""
+    rows = scene.ids(3)
+    scene.call("clx_region_inscribed", {1: LABELS_OUT_OF_RANGE, 2: DISTANCE_CHANGED}, scene.lab, values, scene.lab.numel(), scene.nid,
+               rows, FLAGS, who=who)
+    return rows
+
+
+def _check_map(labels, who, name="labels"):
+    """the checks on a label map that need no device: an array or a tensor of integers, 2-D or 3-D"""
+    import torch
+
+    if not torch.is_tensor(labels) and not isinstance(labels, np.ndarray):
+        raise TypeError(f"{who}: {name} must be an array or a tensor, got {type(labels).__name__}")
+    if ((labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool) if torch.is_tensor(labels)
+            else labels.dtype.kind not in "ui"):
+        raise TypeError(f"{who}: {name} must be integers, got {labels.dtype}")
+    if labels.ndim not in (2, 3):
+        raise ValueError(f"{who}: {name} must be 2-D or 3-D, got {labels.ndim} dimensions")
+
+
+def _in_type_of(labels, scene, out):
+    """a result map ``out`` of ``scene`` (flat on the device; None: the map came through unchanged) in the type, dtype and
+    device of ``labels``, the map the scene was made of"""
+    import torch
+
+    if torch.is_tensor(labels):
+        return labels.clone() if out is None else out.reshape(scene.spatial).to(device=labels.device, dtype=labels.dtype)
+    return labels.copy() if out is None else out.reshape(scene.spatial).cpu().numpy().astype(labels.dtype)
+
+
+def _workspace(scene, entry, *args, below="2^32"):
+    """the scratch an entry point asks for through its ``clx_*_workspace`` function ``entry(*args)`` -> (an int32 device
+    tensor of at least that many bytes, the bytes); 0 bytes say that the map has ``below`` pixels or more"""
+    import torch
+
+    nbytes = int(getattr(_clx.load(), entry)(*args))
+    if nbytes == 0:
+        raise ValueError(f"{scene.who}: the map must have fewer than {below} pixels")
+    return torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=scene.device), nbytes
+
+
+def _result_scene(scene, lab):
+    """a map ``lab`` made of the scene's (flat int32 on the device, the same ids) as a measured scene of its own, which must
+    hold the objects the scene holds"""
+    result = _Scene(scene.who, lab, scene.device, scene.nd, scene.spatial, scene.nid).measured()
+    if not np.array_equal(result.present, scene.present):
+        raise ValueError(LABELS_CHANGED.format(who=scene.who))
+    return result
 
 
 def _scene(labels, device, who):
@@ -930,48 +981,28 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
     arguments); ``weighted=True`` the intensity-weighted centroid, covariance, mass displacement, integrated intensity and peak
     position of every channel, ``border_intensity=True`` the intensity columns over every object's border pixels
     (``region_table``'s arguments, ``edge=False``).  Rank 0 works alone under torch.distributed."""
-    import torch
-
-    from . import parallel
-    from .datasets.meta_data import DatasetMetaData
-    from .train import _require_hip_device
     from .utils import zarr_io
 
-    if parallel.rank() != 0:
+    stage = _stage.begin("measure", inference_config)
+    if stage is None:
         return
+    stage.open("r")
     dataset_config = inference_config.dataset_config
-    meta = DatasetMetaData.from_dataset_config(dataset_config)
-    device = _require_hip_device(inference_config.device)
-    if parallel.world_size() > 1:
-        device = torch.device("cuda", torch.cuda.current_device())
-    seg_config = inference_config.segmentation_dataset_config
-    ds_seg = zarr_io.open(seg_config.container_path, "r")[seg_config.dataset_name]
+    ds_seg = stage.f[inference_config.segmentation_dataset_config.dataset_name]
     ds_raw = zarr_io.open(dataset_config.container_path, "r")[dataset_config.dataset_name]
-    for bandwidth in range(inference_config.num_bandwidths):
-        header, lines, pair_lines = None, [], []
-        for sample in range(meta.num_samples):
-            labels = ds_seg[sample, bandwidth].astype(np.int32)
-            table, pairs = _region_table(labels, ds_raw[sample], device, contacts, topology=topology, hull=hull, inscribed=inscribed,
-                                         quantiles=quantiles, mad=mad, texture=texture, texture_levels=texture_levels,
-                                         texture_distance=texture_distance, radial=radial, radial_rings=radial_rings,
-                                         radial_width=radial_width, radial_wedges=radial_wedges, std=std,
-                                         colocalization=colocalization, coloc_threshold=coloc_threshold, weighted=weighted,
-                                         border_intensity=border_intensity)
-            if contacts:
-                pair_lines += [f"{sample},{a},{b},{n}" for a, b, n in zip(*pairs) if a > 0]
-            header = header or ["sample"] + list(table)
-            columns = list(table.values())
-            for i in range(len(table["label"])):
-                lines.append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
-        with open(f"measurements_bandwidth-{bandwidth}.csv", "w") as out:
-            out.write(",".join(header or ["sample"]) + "\n")
-            for line in lines:
-                out.write(line + "\n")
-        if contacts:
-            with open(f"contacts_bandwidth-{bandwidth}.csv", "w") as out:
-                out.write("sample,label_a,label_b,faces\n")
-                for line in pair_lines:
-                    out.write(line + "\n")
+
+    def per_sample(sample, bandwidth):
+        labels = ds_seg[sample, bandwidth].astype(np.int32)
+        table, pairs = _region_table(labels, ds_raw[sample], stage.device, contacts, topology=topology, hull=hull, inscribed=inscribed,
+                                     quantiles=quantiles, mad=mad, texture=texture, texture_levels=texture_levels,
+                                     texture_distance=texture_distance, radial=radial, radial_rings=radial_rings,
+                                     radial_width=radial_width, radial_wedges=radial_wedges, std=std,
+                                     colocalization=colocalization, coloc_threshold=coloc_threshold, weighted=weighted,
+                                     border_intensity=border_intensity)
+        return (table, dict(zip(_CONTACTS_HEADER[1:], pairs))) if contacts else (table,)
+
+    stage.run(per_sample, ("measurements", "contacts") if contacts else ("measurements",), keep={"contacts": lambda t: t["label_a"] > 0},
+              headers={"contacts": list(_CONTACTS_HEADER)})
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ device or imports torch; ``measure.py`` has the device half, its docstring the d
 this module's names."""
 
 import math
+import numbers
 from fractions import Fraction
 
 import numpy as np
@@ -703,6 +704,36 @@ def border_intensity_columns(table, shift=0, raw_type=None, k=None):
 def _check_weighted(weighted, border_intensity, raw, who="region_table"):
     if (weighted or border_intensity) and raw is None:
         raise ValueError(f"{who}: weighted and border_intensity need raw")
+
+
+def _extents(shape, who):
+    """-> the number of extents of a map's ``shape``, which must be 2 or 3"""
+    if len(shape) not in (2, 3):
+        raise ValueError(f"{who}: shape must have 2 or 3 extents, got {len(shape)}")
+    return len(shape)
+
+
+def _raster_columns(prefix, index, shape, who, mask=None):
+    """the pixels of the raster indices ``index`` (checked to lie inside the map) in a map of ``shape``, as the int64 columns
+    ``<prefix>_z/_y/_x`` (2-D: y and x); -1 where ``mask`` is given and false"""
+    nd = _extents(shape, who)
+    where = np.unravel_index(index, tuple(int(v) for v in shape)) if len(index) else (np.zeros(0, dtype=np.int64),) * nd
+    where = [np.asarray(c, dtype=np.int64) for c in where]
+    return {f"{prefix}_{axis}": c if mask is None else np.where(mask, c, -1) for axis, c in zip(_AXES[3 - nd:], where)}
+
+
+def _real_fraction(value, who, name, none=False):
+    """a real number >= 0 as an exact Fraction; None stays None where ``none`` allows it"""
+    if value is None and none:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (numbers.Real, np.integer, np.floating)):
+        raise TypeError(f"{who}: {name} must be a real number{' or None' if none else ''}, got {type(value).__name__}")
+    if isinstance(value, (float, np.floating)) and not math.isfinite(value):
+        raise ValueError(f"{who}: {name} must be finite, got {value!r}")
+    exact = Fraction(float(value)) if isinstance(value, np.floating) else Fraction(value)
+    if exact < 0:
+        raise ValueError(f"{who}: {name} must be >= 0, got {value!r}")
+    return exact
 
 
 def _format(value):

@@ -33,11 +33,9 @@ import numbers
 import numpy as np
 import torch
 
-from . import _clx
-from .expand import _check_map
-from .measure import DISTANCE_CHANGED, FLAGS, LABELS_CHANGED, LABELS_OUT_OF_RANGE, _scene, _Scene
-from .measure_columns import _AXES, DIST_INF, _exact_div, _format
-from .relate import _write_csv
+from . import _clx, _stage
+from .measure import LABELS_OUT_OF_RANGE, _check_map, _in_type_of, _inscribed_of, _result_scene, _scene, _workspace
+from .measure_columns import DIST_INF, _exact_div, _extents, _raster_columns
 
 COST_INF = DIST_INF                     # CLX_COST_INF: the cost of a pixel that no path reaches
 MAX_WEIGHT = 65535                      # clx_label_propagate: weight and reg lie in [0, 65535]
@@ -139,12 +137,9 @@ def _propagate(scene, mask_d, weight_d, reg, limit):
     """the clx_label_propagate calls of one map, ROUNDS_PER_CALL rounds each, until no tile changes -> (owner, cost), flat int32
     device tensors"""
     npix = scene.lab.numel()
-    nbytes = int(_clx.load().clx_label_propagate_workspace(scene.nd, scene.Z, scene.Y, scene.X))
-    if nbytes == 0:
-        raise ValueError(f"{scene.who}: the map must have fewer than 2^32 pixels")
+    workspace, nbytes = _workspace(scene, "clx_label_propagate_workspace", scene.nd, scene.Z, scene.Y, scene.X)
     owner = torch.empty(npix, dtype=torch.int32, device=scene.device)
     cost = torch.empty(npix, dtype=torch.int32, device=scene.device)
-    workspace = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=scene.device)
     info = torch.empty(3, dtype=torch.int32, device=scene.device)
     total, resume = 0, 0
     while True:
@@ -216,9 +211,7 @@ def propagate_labels(seeds, mask=None, image=None, levels=256, value_range=None,
     who = "propagate_labels"
     weight = _weight_of(seeds, mask, image, levels, value_range, who)
     scene, maps, _ = _front(seeds, mask, weight, regularisation, limit, device, who)
-    if torch.is_tensor(seeds):
-        return seeds.clone() if maps is None else maps[0].reshape(scene.spatial).to(device=seeds.device, dtype=seeds.dtype)
-    return seeds.copy() if maps is None else maps[0].reshape(scene.spatial).cpu().numpy().astype(seeds.dtype)
+    return _in_type_of(seeds, scene, None if maps is None else maps[0])
 
 
 def propagate_columns(label, seed_area, area, rows, unreached, shape):
@@ -230,9 +223,7 @@ def propagate_columns(label, seed_area, area, rows, unreached, shape):
     pixel in raster order that attains it), ``cost_mean`` (one correctly rounded division of exact integers) and ``unreached``
     (the same number in every row); int64 but ``cost_mean``.  Host only."""
     who = "propagate_columns"
-    nd = len(shape)
-    if nd not in (2, 3):
-        raise ValueError(f"{who}: shape must have 2 or 3 extents, got {nd}")
+    _extents(shape, who)
     label, seed_area, area = (np.asarray(v).astype(np.int64).reshape(-1) for v in (label, seed_area, area))
     n = len(label)
     rows = [[int(v) for v in r] for r in np.asarray(rows).reshape(-1, 3)]
@@ -246,10 +237,7 @@ def propagate_columns(label, seed_area, area, rows, unreached, shape):
     if unreached < 0:
         raise ValueError(f"{who}: unreached must be >= 0, got {unreached}")
     table = {"label": label, "seed_area": seed_area, "area": area, "reach_cost": np.array([r[0] for r in rows], dtype=np.int64)}
-    index = np.array([r[1] for r in rows], dtype=np.int64)
-    where = np.unravel_index(index, tuple(int(v) for v in shape)) if n else (np.zeros(0, dtype=np.int64),) * nd
-    for axis, c in zip(_AXES[3 - nd:], where):
-        table[f"reach_{axis}"] = np.asarray(c, dtype=np.int64)
+    table.update(_raster_columns("reach", np.array([r[1] for r in rows], dtype=np.int64), shape, who))
     table["cost_mean"] = _exact_div([r[2] for r in rows], area.astype(object))
     table["unreached"] = np.full(n, unreached, dtype=np.int64)
     return table
@@ -263,11 +251,8 @@ def _table(scene, maps, mask_d):
         return propagate_columns(none, none, none, np.zeros((0, 3), dtype=np.int64), 0, scene.spatial)
     owner, cost = maps
     present = scene.present
-    grown = _Scene(scene.who, owner, scene.device, scene.nd, scene.spatial, scene.nid).measured()
-    if not np.array_equal(grown.present, present):
-        raise ValueError(LABELS_CHANGED.format(who=scene.who))
-    rows = grown.ids(3)
-    grown.call("clx_region_inscribed", {1: LABELS_OUT_OF_RANGE, 2: DISTANCE_CHANGED}, owner, cost, owner.numel(), scene.nid, rows, FLAGS)
+    grown = _result_scene(scene, owner)
+    rows = _inscribed_of(grown, cost)
     nobody = owner == 0
     unreached = int((nobody if mask_d is None else nobody & (mask_d != 0)).sum().item())
     return propagate_columns(present, scene.area[present], grown.area[present], rows.cpu().numpy()[present], unreached, scene.spatial)
@@ -290,9 +275,6 @@ def propagate_stage(inference_config, seeds, output, mask=None, channel=None, le
     the container whose non-zero pixels are allowed (``segment()``'s label map, say), or None; ``channel``: the channel of the
     raw dataset that is the image, in ``levels`` grey levels between its smallest and largest value under the mask and the
     seeds, or None (flat).  Rank 0 works alone under torch.distributed."""
-    from . import parallel
-    from .datasets.meta_data import DatasetMetaData
-    from .train import _require_hip_device
     from .utils import zarr_io
 
     who = "propagate_stage"
@@ -309,47 +291,30 @@ def propagate_stage(inference_config, seeds, output, mask=None, channel=None, le
         raise ValueError(f"{who}: levels must lie in [2, {MAX_WEIGHT + 1}], got {levels!r}")
     _integer(regularisation, who, "regularisation", MAX_WEIGHT)
     _integer(limit, who, "limit", COST_INF - 1, none=-1)
-    if parallel.rank() != 0:
+    stage = _stage.begin(who, inference_config)
+    if stage is None:
         return
-    dataset_config = inference_config.dataset_config
-    meta = DatasetMetaData.from_dataset_config(dataset_config)
-    nd = meta.num_spatial_dims
-    device = _require_hip_device(inference_config.device)
-    if parallel.world_size() > 1:
-        device = torch.device("cuda", torch.cuda.current_device())
-    path = inference_config.segmentation_dataset_config.container_path
-    f = zarr_io.open(path, "a")
-    for name in (seeds, mask):
-        if name is not None and name not in f:
-            raise ValueError(f"{who}: no dataset {name!r} in {path}")
-    if output in f:
-        raise ValueError(f"{who}: a dataset {output!r} exists in {path} already")
+    stage.open("a", seeds, mask)
+    stage.refuse_existing(output)
     ds_raw = None
     if channel is not None:
+        dataset_config = inference_config.dataset_config
         ds_raw = zarr_io.open(dataset_config.container_path, "r")[dataset_config.dataset_name]
         if channel >= ds_raw.shape[1]:
             raise ValueError(f"{who}: no channel {channel} in a raw dataset of {ds_raw.shape[1]} channels")
-    ds_seeds, ds_mask = f[seeds], f[mask] if mask is not None else None
-    ds_output = f.create_dataset(output, shape=(meta.num_samples, inference_config.num_bandwidths, *meta.spatial_array), dtype=np.uint16)
-    ds_output.attrs["axis_names"] = ["s", "c"] + ["t", "z", "y", "x"][-nd:]
-    ds_output.attrs["resolution"] = (1,) * nd
-    ds_output.attrs["offset"] = (0,) * nd
-    for bandwidth in range(inference_config.num_bandwidths):
-        header, lines = None, []
-        for sample in range(meta.num_samples):
-            labels = ds_seeds[sample, bandwidth].astype(np.int32)
-            allowed = None if ds_mask is None else np.asarray(ds_mask[sample, bandwidth]) != 0
-            image = None if ds_raw is None else np.asarray(ds_raw[sample][channel])
-            weight = _weight_of(labels, allowed, image, levels, None, who)
-            scene, maps, mask_d = _front(labels, allowed, weight, regularisation, limit, device, who)
-            grown = labels if maps is None else maps[0].reshape(scene.spatial).cpu().numpy()
-            ds_output[sample, bandwidth] = grown.astype(np.uint16)
-            table = _table(scene, maps, mask_d)
-            header = header or ["sample"] + list(table)
-            columns = list(table.values())
-            for i in range(len(columns[0])):
-                lines.append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
-        _write_csv(f"propagate_bandwidth-{bandwidth}.csv", header, lines)
+    ds_seeds, ds_mask = stage.f[seeds], stage.f[mask] if mask is not None else None
+    ds_output = stage.create(output)
+
+    def per_sample(sample, bandwidth):
+        labels = ds_seeds[sample, bandwidth].astype(np.int32)
+        allowed = None if ds_mask is None else np.asarray(ds_mask[sample, bandwidth]) != 0
+        image = None if ds_raw is None else np.asarray(ds_raw[sample][channel])
+        weight = _weight_of(labels, allowed, image, levels, None, who)
+        scene, maps, mask_d = _front(labels, allowed, weight, regularisation, limit, stage.device, who)
+        ds_output[sample, bandwidth] = _in_type_of(labels, scene, None if maps is None else maps[0]).astype(np.uint16)
+        return (_table(scene, maps, mask_d),)
+
+    stage.run(per_sample, ("propagate",))
 
 
 if __name__ == "__main__":

@@ -29,10 +29,10 @@ import math
 import numpy as np
 import torch
 
-from . import _clx
-from .measure import (DISTANCE_CHANGED, FLAGS, LABELS_OUT_OF_RANGE, _call, _distance_map, _pair_capacity, _pair_table,
+from . import _clx, _stage
+from .measure import (DISTANCE_CHANGED, FLAGS, LABELS_OUT_OF_RANGE, _call, _check_map, _distance_map, _pair_capacity, _pair_table,
                       _resolve_device, _Scene, _to_device_labels)
-from .measure_columns import _AXES, DIST_INF, _exact_div, _format, _sqrt_ratio
+from .measure_columns import DIST_INF, _exact_div, _extents, _raster_columns, _sqrt_ratio
 
 NO_PIXEL = (1 << 64) - 1                # clx_region_clearance's out[i][1] of an id without a counted pixel
 
@@ -40,12 +40,7 @@ NO_PIXEL = (1 << 64) - 1                # clx_region_clearance's out[i][1] of an
 def _check_maps(a, b, who, names=("children", "parents")):
     """the checks on a pair of label maps that need no device: integers, 2-D or 3-D, of one shape -> (nd, spatial)"""
     for name, m in zip(names, (a, b)):
-        if not torch.is_tensor(m) and not isinstance(m, np.ndarray):
-            raise TypeError(f"{who}: {name} must be an array or a tensor, got {type(m).__name__}")
-        if (m.dtype.is_floating_point or m.dtype.is_complex or m.dtype == torch.bool) if torch.is_tensor(m) else m.dtype.kind not in "ui":
-            raise TypeError(f"{who}: {name} must be integers, got {m.dtype}")
-        if m.ndim not in (2, 3):
-            raise ValueError(f"{who}: {name} must be 2-D or 3-D, got {m.ndim} dimensions")
+        _check_map(m, who, name)
     if tuple(a.shape) != tuple(b.shape):
         raise ValueError(f"{who}: {names[0]} has shape {tuple(a.shape)}, {names[1]} {tuple(b.shape)}")
     return a.ndim, tuple(int(v) for v in a.shape)
@@ -134,9 +129,7 @@ def relate_columns(ids_a, ids_b, pixels, child_moments, parent_moments, shape, c
     parent: ``label``, ``area``, ``num_children``, ``children_area``, ``children_fraction``, ``tertiary_area``.
     Host only; the module's docstring has the definitions."""
     who = "relate_columns"
-    nd = len(shape)
-    if nd not in (2, 3):
-        raise ValueError(f"{who}: shape must have 2 or 3 extents, got {nd}")
+    nd = _extents(shape, who)
     a, b, n = _rows(ids_a, ids_b, pixels, who)
     clabel, carea, csum = _moments_arg(child_moments, who, "child_moments")
     plabel, parea, psum = _moments_arg(parent_moments, who, "parent_moments")
@@ -175,9 +168,7 @@ def relate_columns(ids_a, ids_b, pixels, child_moments, parent_moments, shape, c
         index = np.array([r[1] & 0xFFFFFFFF if s else 0 for r, s in zip(rows, some)], dtype=np.int64)
         if len(index) and index.max() >= int(np.prod(shape)):
             raise ValueError(f"{who}: a clearance row points outside a map of shape {tuple(shape)}")
-        centre = np.unravel_index(index, tuple(int(v) for v in shape)) if nc else (np.zeros(0, dtype=np.int64),) * nd
-        for axis, c in zip(_AXES[3 - nd:], centre):
-            child[f"clearance_{axis}"] = np.where(some, np.asarray(c, dtype=np.int64), -1) if nc else np.zeros(0, dtype=np.int64)
+        child.update(_raster_columns("clearance", index, shape, who, mask=some))
         child["depth_sq_mean"] = np.array([math.nan if not s else math.inf if i else r[2] / r[0] for r, s, i in zip(rows, some, inf)],
                                           dtype=np.float64)
     inside = (a > 0) & (b > 0)
@@ -234,13 +225,6 @@ def tertiary_labels(children, parents):
     return np.where(children > 0, np.zeros((), parents.dtype), parents)
 
 
-def _write_csv(path, header, lines):
-    with open(path, "w") as out:
-        out.write(",".join(header or ["sample"]) + "\n")
-        for line in lines:
-            out.write(line + "\n")
-
-
 def relate_stage(inference_config, children, parents, clearance=False, tertiary=None) -> None:
     """For every bandwidth: ``relate``'s tables of all samples, with ``children`` and ``parents`` the names of two label
     datasets ``[sample, bandwidth, ...]`` in ``segmentation_dataset_config.container_path`` (``segment()``'s output under the
@@ -248,11 +232,6 @@ def relate_stage(inference_config, children, parents, clearance=False, tertiary=
     the working directory -- a header line, then ``sample`` and the table's columns, floats as ``%.17g``.  ``clearance=True``
     adds the clearance columns (``edge=False``).  ``tertiary=NAME`` writes ``tertiary_labels`` of every sample and bandwidth
     into a new uint16 dataset NAME of that container.  Rank 0 works alone under torch.distributed."""
-    from . import parallel
-    from .datasets.meta_data import DatasetMetaData
-    from .train import _require_hip_device
-    from .utils import zarr_io
-
     for name, value in (("children", children), ("parents", parents)):
         if not isinstance(value, str) or not value:
             raise ValueError(f"relate_stage: {name} must be the name of a dataset, got {value!r}")
@@ -260,39 +239,22 @@ def relate_stage(inference_config, children, parents, clearance=False, tertiary=
         raise ValueError(f"relate_stage: children and parents are the same dataset {children!r}")
     if tertiary is not None and (not isinstance(tertiary, str) or not tertiary or tertiary in (children, parents)):
         raise ValueError(f"relate_stage: tertiary must name a new dataset other than children and parents, got {tertiary!r}")
-    if parallel.rank() != 0:
+    stage = _stage.begin("relate_stage", inference_config)
+    if stage is None:
         return
-    meta = DatasetMetaData.from_dataset_config(inference_config.dataset_config)
-    nd = meta.num_spatial_dims
-    device = _require_hip_device(inference_config.device)
-    if parallel.world_size() > 1:
-        device = torch.device("cuda", torch.cuda.current_device())
-    f = zarr_io.open(inference_config.segmentation_dataset_config.container_path, "a" if tertiary else "r")
-    for name in (children, parents):
-        if name not in f:
-            raise ValueError(f"relate_stage: no dataset {name!r} in {inference_config.segmentation_dataset_config.container_path}")
-    ds_children, ds_parents = f[children], f[parents]
-    ds_tertiary = None
-    if tertiary:
-        ds_tertiary = f.create_dataset(tertiary, shape=(meta.num_samples, inference_config.num_bandwidths, *meta.spatial_array),
-                                       dtype=np.uint16)
-        ds_tertiary.attrs["axis_names"] = ["s", "c"] + ["t", "z", "y", "x"][-nd:]
-        ds_tertiary.attrs["resolution"] = (1,) * nd
-        ds_tertiary.attrs["offset"] = (0,) * nd
-    for bandwidth in range(inference_config.num_bandwidths):
-        headers, lines = [None, None], ([], [])
-        for sample in range(meta.num_samples):
-            a = ds_children[sample, bandwidth].astype(np.int32)
-            b = ds_parents[sample, bandwidth].astype(np.int32)
-            for k, table in enumerate(relate(a, b, device, clearance=clearance)):
-                headers[k] = headers[k] or ["sample"] + list(table)
-                columns = list(table.values())
-                for i in range(len(table["label"])):
-                    lines[k].append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
-            if ds_tertiary is not None:
-                ds_tertiary[sample, bandwidth] = tertiary_labels(a, b).astype(np.uint16)
-        _write_csv(f"relate_children_bandwidth-{bandwidth}.csv", headers[0], lines[0])
-        _write_csv(f"relate_parents_bandwidth-{bandwidth}.csv", headers[1], lines[1])
+    stage.open("a" if tertiary else "r", children, parents)
+    ds_children, ds_parents = stage.f[children], stage.f[parents]
+    ds_tertiary = stage.create(tertiary) if tertiary else None      # one that exists: the container's ContainsArrayError
+
+    def per_sample(sample, bandwidth):
+        a = ds_children[sample, bandwidth].astype(np.int32)
+        b = ds_parents[sample, bandwidth].astype(np.int32)
+        tables = relate(a, b, stage.device, clearance=clearance)
+        if ds_tertiary is not None:
+            ds_tertiary[sample, bandwidth] = tertiary_labels(a, b).astype(np.uint16)
+        return tables
+
+    stage.run(per_sample, ("relate_children", "relate_parents"))
 
 
 if __name__ == "__main__":

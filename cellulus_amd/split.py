@@ -26,17 +26,14 @@ writes ``split_labels`` of every sample and bandwidth of ``NAME`` into a new dat
 """
 
 import math
-import numbers
-from fractions import Fraction
 
 import numpy as np
 import torch
 
-from . import _clx
-from .expand import _check_map
-from .measure import FLAGS, _call, _distance_map, _pair_capacity, _pair_slots, _scene, _Scene
-from .measure_columns import _AXES, DIST_INF, _format, _sqrt_ratio
-from .relate import _write_csv
+from . import _stage
+from .measure import (FLAGS, _call, _check_map, _distance_map, _in_type_of, _pair_capacity, _pair_slots, _scene, _Scene,
+                      _workspace)
+from .measure_columns import DIST_INF, _extents, _raster_columns, _real_fraction, _sqrt_ratio
 
 MAX_SUMMITS = 1 << 30                   # clx_label_basins: capacity of the summit list; clx_basin_relabel: n
 BASIN_NONE = -1                         # CLX_BASIN_NONE: root of a pixel of no basin
@@ -46,14 +43,7 @@ _ROOTS_CHANGED = "{who}: the roots changed under the relabelling"
 
 def _depth(depth, who):
     """``depth`` as an exact Fraction: a real number >= 0"""
-    if isinstance(depth, bool) or not isinstance(depth, (numbers.Real, np.integer, np.floating)):
-        raise TypeError(f"{who}: depth must be a real number, got {type(depth).__name__}")
-    if isinstance(depth, (float, np.floating)) and not math.isfinite(depth):
-        raise ValueError(f"{who}: depth must be finite, got {depth!r}")
-    exact = Fraction(float(depth)) if isinstance(depth, np.floating) else Fraction(depth)
-    if exact < 0:
-        raise ValueError(f"{who}: depth must be >= 0, got {depth!r}")
-    return exact
+    return _real_fraction(depth, who, "depth")
 
 
 def shallower(top_d2, pass_d2, depth):
@@ -134,19 +124,14 @@ def split_columns(parent, top, top_d2, pass_d2, area, shape):
     the half-width of the widest neck to another piece of the same object (NaN: none), ``pieces_of_parent`` and ``area``; int64
     but the two radii, each of which is one correctly rounded root of an exact integer.  Host only."""
     who = "split_columns"
-    nd = len(shape)
-    if nd not in (2, 3):
-        raise ValueError(f"{who}: shape must have 2 or 3 extents, got {nd}")
+    _extents(shape, who)
     parent, top, top_d2, pass_d2, area = (np.asarray(v).astype(np.int64).reshape(-1) for v in (parent, top, top_d2, pass_d2, area))
     n = len(parent)
     if not len(top) == len(top_d2) == len(pass_d2) == len(area) == n:
         raise ValueError(f"{who}: parent, top, top_d2, pass_d2 and area must have one row per piece")
     if n and (top.min() < 0 or top.max() >= int(np.prod(shape)) or top_d2.min() < 0 or np.any(pass_d2 > top_d2) or area.min() < 1):
         raise ValueError(f"{who}: needs tops inside a map of shape {tuple(shape)}, pass_d2 <= top_d2 and area >= 1")
-    table = {"label": np.arange(1, n + 1, dtype=np.int64), "parent": parent}
-    where = np.unravel_index(top, tuple(int(v) for v in shape)) if n else (np.zeros(0, dtype=np.int64),) * nd
-    for axis, c in zip(_AXES[3 - nd:], where):
-        table[f"summit_{axis}"] = np.asarray(c, dtype=np.int64)
+    table = {"label": np.arange(1, n + 1, dtype=np.int64), "parent": parent, **_raster_columns("summit", top, shape, who)}
     table["summit_radius"] = np.array([_sqrt_ratio(v, 1) for v in top_d2.tolist()], dtype=np.float64)
     table["pass_radius"] = np.array([_sqrt_ratio(v, 1) if v >= 0 else math.nan for v in pass_d2.tolist()], dtype=np.float64)
     _, inverse, counts = np.unique(parent, return_inverse=True, return_counts=True)
@@ -160,18 +145,11 @@ def _as_roots(values):
     return torch.from_numpy(np.asarray(values, dtype=np.int64).astype(np.uint32).view(np.int32))
 
 
-def _workspace(scene):
-    nbytes = int(_clx.load().clx_label_basins_workspace(scene.lab.numel()))
-    if nbytes == 0:
-        raise ValueError(f"{scene.who}: the map must have fewer than 2^32 pixels")
-    return torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=scene.device), nbytes
-
-
 def _basins(scene, dist):
     """one clx_label_basins call (a second one where the first list was too short) -> (root, flat int32 on the device; the
     summits' raster indices, int64 ascending on the host)"""
     npix = scene.lab.numel()
-    workspace, nbytes = _workspace(scene)
+    workspace, nbytes = _workspace(scene, "clx_label_basins_workspace", scene.lab.numel())
     root = torch.empty(npix, dtype=torch.int32, device=scene.device)
     capacity = min(npix, max(1024, npix // 64))
     while True:
@@ -246,7 +224,7 @@ def _split(labels, depth, edge, device, who, table=False, fits=None):
     if fits is not None:
         fits(len(pieces["top"]))
     out = torch.empty_like(scene.lab)
-    workspace, nbytes = _workspace(scene)
+    workspace, nbytes = _workspace(scene, "clx_label_basins_workspace", scene.lab.numel())
     scene.call("clx_basin_relabel", {1 | 2: _ROOTS_CHANGED}, root, scene.lab.numel(), _as_roots(summits).to(scene.device),
                torch.from_numpy(piece.astype(np.int32)).to(scene.device), len(summits), out, FLAGS, workspace, nbytes)
     if not table:
@@ -254,12 +232,6 @@ def _split(labels, depth, edge, device, who, table=False, fits=None):
     n = len(pieces["top"])
     new = _Scene(who, out, scene.device, scene.nd, scene.spatial, n + 1).measured()
     return scene, out, split_columns(pieces["parent"], pieces["top"], pieces["top_d2"], pieces["pass_d2"], new.area[1:], scene.spatial)
-
-
-def _in_type_of(labels, scene, out):
-    if torch.is_tensor(labels):
-        return labels.clone() if out is None else out.reshape(scene.spatial).to(device=labels.device, dtype=labels.dtype)
-    return labels.copy() if out is None else out.reshape(scene.spatial).cpu().numpy().astype(labels.dtype)
 
 
 def _dtype_max(labels):
@@ -296,51 +268,30 @@ def split_stage(inference_config, source, output, depth=1, edge=False) -> None:
     uint16 dataset ``output`` of that container and ``split_table``'s rows of all samples as ``split_bandwidth-<b>.csv`` in the
     working directory -- a header line, then ``sample`` and the table's columns, floats as ``%.17g``.  Rank 0 works alone under
     torch.distributed."""
-    from . import parallel
-    from .datasets.meta_data import DatasetMetaData
-    from .train import _require_hip_device
-    from .utils import zarr_io
-
     who = "split_stage"
     if not isinstance(source, str) or not source:
         raise ValueError(f"{who}: source must be the name of a dataset, got {source!r}")
     if not isinstance(output, str) or not output or output == source:
         raise ValueError(f"{who}: output must name a new dataset other than source, got {output!r}")
     _depth(depth, who)
-    if parallel.rank() != 0:
+    stage = _stage.begin(who, inference_config)
+    if stage is None:
         return
-    meta = DatasetMetaData.from_dataset_config(inference_config.dataset_config)
-    nd = meta.num_spatial_dims
-    device = _require_hip_device(inference_config.device)
-    if parallel.world_size() > 1:
-        device = torch.device("cuda", torch.cuda.current_device())
-    path = inference_config.segmentation_dataset_config.container_path
-    f = zarr_io.open(path, "a")
-    if source not in f:
-        raise ValueError(f"{who}: no dataset {source!r} in {path}")
-    if output in f:
-        raise ValueError(f"{who}: a dataset {output!r} exists in {path} already")
-    ds_source = f[source]
-    ds_output = f.create_dataset(output, shape=(meta.num_samples, inference_config.num_bandwidths, *meta.spatial_array), dtype=np.uint16)
-    ds_output.attrs["axis_names"] = ["s", "c"] + ["t", "z", "y", "x"][-nd:]
-    ds_output.attrs["resolution"] = (1,) * nd
-    ds_output.attrs["offset"] = (0,) * nd
+    stage.open("a", source)
+    stage.refuse_existing(output)
+    ds_source, ds_output = stage.f[source], stage.create(output)
 
     def fits(n):
         if n > np.iinfo(np.uint16).max:
             raise ValueError(f"{who}: {n} pieces do not fit uint16")
 
-    for bandwidth in range(inference_config.num_bandwidths):
-        header, lines = None, []
-        for sample in range(meta.num_samples):
-            labels = ds_source[sample, bandwidth].astype(np.int32)
-            scene, out, table = _split(labels, depth, edge, device, who, table=True, fits=fits)
-            ds_output[sample, bandwidth] = _in_type_of(labels, scene, out).astype(np.uint16)
-            header = header or ["sample"] + list(table)
-            columns = list(table.values())
-            for i in range(len(columns[0])):
-                lines.append(",".join([str(sample)] + [_format(c[i]) for c in columns]))
-        _write_csv(f"split_bandwidth-{bandwidth}.csv", header, lines)
+    def per_sample(sample, bandwidth):
+        labels = ds_source[sample, bandwidth].astype(np.int32)
+        scene, out, table = _split(labels, depth, edge, stage.device, who, table=True, fits=fits)
+        ds_output[sample, bandwidth] = _in_type_of(labels, scene, out).astype(np.uint16)
+        return (table,)
+
+    stage.run(per_sample, ("split",))
 
 
 if __name__ == "__main__":
