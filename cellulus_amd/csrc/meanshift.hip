@@ -5,10 +5,9 @@
 //
 // Replaces cellulus/utils/mean_shift.py:6-121 -> sklearn.cluster.MeanShift
 // (fit: _mean_shift_single_seed per seed; predict: nearest centre).
-#include <stdlib.h>
-
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "clx_common.h"
@@ -143,6 +142,30 @@ __global__ __launch_bounds__(256) void ms_flags_kernel(const TIn* __restrict__ s
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
+// A wave-tile's G * PXL ballot words as ms_flags_kernel left them (wave-uniform: scalar loads), and what the two
+// readers make of them: per 16-byte group g, the set bits in front of this lane's pixels and the set bits of the group.
+template <int G, int PXL>
+struct TileFlags {
+  unsigned long long B[G][PXL];
+  __device__ __forceinline__ TileFlags(const unsigned long long* __restrict__ flags, int wt) {
+    const unsigned long long* tf = flags + (long long)wt * G * PXL;
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int e = 0; e < PXL; ++e) B[g][e] = tf[g * PXL + e];
+  }
+  __device__ __forceinline__ bool set(int g, int e, int lane) const { return (B[g][e] >> lane) & 1ull; }
+  __device__ __forceinline__ void count(int g, int lane, int& bef, int& cnt) const {
+    const unsigned long long lower = (1ull << lane) - 1ull;
+    bef = cnt = 0;
+#pragma unroll
+    for (int e = 0; e < PXL; ++e) {
+      bef += __popcll(B[g][e] & lower);
+      cnt += __popcll(B[g][e]);
+    }
+  }
+};
+
 template <int ND, typename TIn, int G, bool WB, int BLOCKS>
 __global__ __launch_bounds__(256, BLOCKS) void ms_scatter_kernel(TIn* __restrict__ emb, FastDiv dX, FastDiv dY, int Y, int X,
                                                                  long long npix, int vec, int nwt,
@@ -156,7 +179,6 @@ __global__ __launch_bounds__(256, BLOCKS) void ms_scatter_kernel(TIn* __restrict
   constexpr int PXL = Vec16<TIn>::N;
   constexpr int WT = 64 * G * PXL;
   const int lane = threadIdx.x & 63;
-  const unsigned long long lower = (1ull << lane) - 1ull;
   for (int wt = blockIdx.x * 4 + (threadIdx.x >> 6); wt < nwt; wt += gridDim.x * 4) {
     const long long base = (long long)wt * WT;
     // points in front of this tile = the chunks of the flags pass in front of its chunk (summed by the block) + the
@@ -168,12 +190,7 @@ __global__ __launch_bounds__(256, BLOCKS) void ms_scatter_kernel(TIn* __restrict
     for (int j = threadIdx.x; j < chunk; j += 256) before += chunk_counts[j];
     int inside = 0;
     for (int t = chunk_first + lane; t < wt; t += 64) inside += counts[t];
-    const unsigned long long* tf = flags + (long long)wt * G * PXL;
-    unsigned long long B[G][PXL];            // wave-uniform: this tile's ballot words
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int e = 0; e < PXL; ++e) B[g][e] = tf[g * PXL + e];
+    const TileFlags<G, PXL> tile(flags, wt);
     // the tile's embedding values: every load in flight before the first is used
     V ev[G][ND];
 #pragma unroll
@@ -181,7 +198,7 @@ __global__ __launch_bounds__(256, BLOCKS) void ms_scatter_kernel(TIn* __restrict
       const long long i = base + (long long)(g * 64 + lane) * PXL;
       bool any = WB;
 #pragma unroll
-      for (int e = 0; e < PXL; ++e) any = any || ((B[g][e] >> lane) & 1ull);
+      for (int e = 0; e < PXL; ++e) any = any || tile.set(g, e, lane);
       if (i < npix && any) {
         if (vec) {
 #pragma unroll
@@ -208,13 +225,10 @@ __global__ __launch_bounds__(256, BLOCKS) void ms_scatter_kernel(TIn* __restrict
     for (int g = 0; g < G; ++g) {
       const long long i = base + (long long)(g * 64 + lane) * PXL;
       unsigned int gb = 0u;
-      int bef = 0, cnt = 0;
+      int bef, cnt;
+      tile.count(g, lane, bef, cnt);
 #pragma unroll
-      for (int e = 0; e < PXL; ++e) {
-        gb |= (unsigned int)((B[g][e] >> lane) & 1ull) << e;
-        bef += __popcll(B[g][e] & lower);
-        cnt += __popcll(B[g][e]);
-      }
+      for (int e = 0; e < PXL; ++e) gb |= (unsigned int)tile.set(g, e, lane) << e;
       if (i < npix && (WB || gb != 0u)) {
         int pos = run + bef;
         const unsigned int t = fdiv((unsigned int)i, dX);
@@ -258,11 +272,61 @@ __global__ __launch_bounds__(256, BLOCKS) void ms_scatter_kernel(TIn* __restrict
   }
 }
 
+// A uniform grid of cells of edge h over the points (x fastest): built once on the host, inv = 1 / h the host's quotient.
+struct Grid {
+  double ox, oy, oz, h, inv;
+  int nx, ny, nz;
+};
+
+// the cell of coordinate v along an axis of n cells that starts at o; points outside the grid count to its faces
+__device__ __forceinline__ int clamp_cell(double v, double o, double inv, int n) {
+  return min(max((int)floor((v - o) * inv), 0), n - 1);
+}
+
+// Which fit points a wavefront looks at for one mean: visit() calls member(j) for this lane's share of them.
+// AllPoints: every fit point, lanes striding over the array.
+struct AllPoints {
+  int nfit;
+  template <int ND, typename F>
+  __device__ __forceinline__ void visit(const double (&)[ND], int lane, F&& member) const {
+    for (int j = lane; j < nfit; j += 64) member(j);
+  }
+};
+
+// CellsAround: the fit points bucketed into cells of edge h >= bandwidth (sorted by cell id, x fastest): the members of
+// a query lie in the 3^ND cells around it, and the 3 x-adjacent cells of one (z, y) row are one contiguous run of the
+// sorted array.  Cuts the pair evaluations from nseeds*nfit to nseeds*(points in 3^ND cells) per iteration.
+struct CellsAround {
+  const int* __restrict__ cell_start;
+  Grid g;
+  template <int ND, typename F>
+  __device__ __forceinline__ void visit(const double (&mean)[ND], int lane, F&& member) const {
+    // the mean's cell, held to [-2, n + 1] BEFORE the conversion: a mean far outside the grid (a seed at 1e300, +inf) would
+    // convert to INT_MAX, and cy + 1 below would overflow — the compiler, free to assume it does not, tested cy > -2
+    // instead of cy + 1 >= 0 and let the row INT_MIN through to cell_start.  Cells -2 and n + 1 have no neighbour in the grid.
+    auto cell_of = [](double v, int n) { return (int)fmin(fmax(floor(v), -2.0), (double)n + 1.0); };
+    const int cx = cell_of((mean[0] - g.ox) * g.inv, g.nx);
+    const int cy = cell_of((mean[1] - g.oy) * g.inv, g.ny);
+    const int cz = (ND == 3) ? cell_of((mean[ND - 1] - g.oz) * g.inv, g.nz) : 0;
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
+    if (x0 > x1) return;
+    for (int zz = (ND == 3 ? cz - 1 : 0); zz <= (ND == 3 ? cz + 1 : 0); ++zz) {
+      if (zz < 0 || zz >= g.nz) continue;
+      for (int yy = cy - 1; yy <= cy + 1; ++yy) {
+        if (yy < 0 || yy >= g.ny) continue;
+        const long long row = ((long long)zz * g.ny + yy) * g.nx;
+        const int lo = cell_start[row + x0], hi = cell_start[row + x1 + 1];
+        for (int j = lo + lane; j < hi; j += 64) member(j);
+      }
+    }
+  }
+};
+
 // One wavefront per seed: sklearn _mean_shift_single_seed.
 //   loop: members = fit points with |x - mean|^2 <= bw^2 ; if none: stop
 //         new = mean(members); if |new - mean| <= 1e-3 bw or it == max_iter: stop
-template <int ND>
-__global__ __launch_bounds__(256) void ms_iterate_kernel(const double* __restrict__ fit, int nfit,
+template <int ND, typename Source>
+__global__ __launch_bounds__(256) void ms_iterate_kernel(const double* __restrict__ fit, Source source,
                                                          const double* __restrict__ seeds, int nseeds,
                                                          double bw, int max_iter,
                                                          double* __restrict__ centers,
@@ -282,7 +346,7 @@ __global__ __launch_bounds__(256) void ms_iterate_kernel(const double* __restric
 #pragma unroll
     for (int c = 0; c < ND; ++c) sum[c] = 0.0;
     int cnt = 0;
-    for (int j = lane; j < nfit; j += 64) {
+    source.visit(mean, lane, [&](int j) {
       double x[ND], d2 = 0.0;
 #pragma unroll
       for (int c = 0; c < ND; ++c) {
@@ -295,90 +359,7 @@ __global__ __launch_bounds__(256) void ms_iterate_kernel(const double* __restric
 #pragma unroll
         for (int c = 0; c < ND; ++c) sum[c] += x[c];
       }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      cnt += __shfl_xor(cnt, o, 64);
-#pragma unroll
-      for (int c = 0; c < ND; ++c) sum[c] += __shfl_xor(sum[c], o, 64);
-    }
-    members = cnt;
-    if (cnt == 0) break;
-    double shift2 = 0.0;
-#pragma unroll
-    for (int c = 0; c < ND; ++c) {
-      const double nm = sum[c] / (double)cnt;
-      const double df = nm - mean[c];
-      shift2 += df * df;
-      mean[c] = nm;
-    }
-    if (sqrt(shift2) <= stop || completed == max_iter) break;
-    ++completed;
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < ND; ++c) centers[(long long)seed * ND + c] = mean[c];
-    counts[seed] = members;
-    iters[seed] = completed;
-  }
-}
-
-// Same iteration with the fit points bucketed into cells of edge h >= bandwidth (sorted by
-// cell id, x fastest): the members of a query lie in the 3^ND cells around it, and the 3
-// x-adjacent cells of one (z, y) row are one contiguous run of the sorted array.  Cuts the
-// pair evaluations from nseeds*nfit to nseeds*(points in 3^ND cells) per iteration.
-template <int ND>
-__global__ __launch_bounds__(256) void ms_iterate_grid_kernel(
-    const double* __restrict__ fit, const int* __restrict__ cell_start, double ox, double oy,
-    double oz, double inv_h, int nx, int ny, int nz, const double* __restrict__ seeds, int nseeds,
-    double bw, int max_iter, double* __restrict__ centers, int* __restrict__ counts,
-    int* __restrict__ iters) {
-  const int lane = threadIdx.x & 63;
-  const int seed = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (seed >= nseeds) return;
-  const double bw2 = bw * bw;
-  const double stop = 1e-3 * bw;
-  double mean[ND];
-#pragma unroll
-  for (int c = 0; c < ND; ++c) mean[c] = seeds[(long long)seed * ND + c];
-  int completed = 0, members = 0;
-  while (true) {
-    double sum[ND];
-#pragma unroll
-    for (int c = 0; c < ND; ++c) sum[c] = 0.0;
-    int cnt = 0;
-    // the mean's cell, held to [-2, n + 1] BEFORE the conversion: a mean far outside the grid (a seed at 1e300, +inf) would
-    // convert to INT_MAX, and cy + 1 below would overflow — the compiler, free to assume it does not, tested cy > -2
-    // instead of cy + 1 >= 0 and let the row INT_MIN through to cell_start.  Cells -2 and n + 1 have no neighbour in the grid.
-    auto cell_of = [](double v, int n) { return (int)fmin(fmax(floor(v), -2.0), (double)n + 1.0); };
-    const int cx = cell_of((mean[0] - ox) * inv_h, nx);
-    const int cy = cell_of((mean[1] - oy) * inv_h, ny);
-    const int cz = (ND == 3) ? cell_of((mean[2] - oz) * inv_h, nz) : 0;
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, nx - 1);
-    if (x0 <= x1) {
-      for (int zz = (ND == 3 ? cz - 1 : 0); zz <= (ND == 3 ? cz + 1 : 0); ++zz) {
-        if (zz < 0 || zz >= nz) continue;
-        for (int yy = cy - 1; yy <= cy + 1; ++yy) {
-          if (yy < 0 || yy >= ny) continue;
-          const long long row = ((long long)zz * ny + yy) * nx;
-          const int lo = cell_start[row + x0], hi = cell_start[row + x1 + 1];
-          for (int j = lo + lane; j < hi; j += 64) {
-            double x[ND], d2 = 0.0;
-#pragma unroll
-            for (int c = 0; c < ND; ++c) {
-              x[c] = fit[(long long)j * ND + c];
-              const double df = x[c] - mean[c];
-              d2 += df * df;
-            }
-            if (d2 <= bw2) {
-              ++cnt;
-#pragma unroll
-              for (int c = 0; c < ND; ++c) sum[c] += x[c];
-            }
-          }
-        }
-      }
-    }
+    });
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       cnt += __shfl_xor(cnt, o, 64);
@@ -556,68 +537,28 @@ __global__ __launch_bounds__(256) void bucket_order_big_kernel(const double* __r
 // until the candidate is closer than that or the block is the whole grid (rare: pixels cluster
 // around their centre by construction).  Cuts nfg x ncentres pair evaluations to
 // nfg x (centres in 3^ND cells).
-template <int ND>
-__global__ __launch_bounds__(256) void ms_assign_grid_kernel(
-    const double* __restrict__ X, const int* __restrict__ index, int nfg, const double* __restrict__ centers,
-    int ncenters, const int* __restrict__ order, const int* __restrict__ cell_start, double ox, double oy,
-    double oz, double h, int nx, int ny, int nz, int* __restrict__ labels) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nfg) return;
-  double x[ND];
-#pragma unroll
-  for (int c = 0; c < ND; ++c) x[c] = X[(long long)i * ND + c];
-  const double inv = 1.0 / h;
-  const int cx = min(max((int)floor((x[0] - ox) * inv), 0), nx - 1);
-  const int cy = min(max((int)floor((x[1] - oy) * inv), 0), ny - 1);
-  const int cz = (ND == 3) ? min(max((int)floor((x[2] - oz) * inv), 0), nz - 1) : 0;
-  double best = 0.0;
-  int arg = -1;
-  // block of cells within r of the pixel's own: every centre outside it is at least r * h away
-  for (int r = 1;; r *= 2) {
-    const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
-    const int y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
-    const int z0 = (ND == 3) ? max(cz - r, 0) : 0, z1 = (ND == 3) ? min(cz + r, nz - 1) : 0;
-    arg = -1;
-    for (int zz = z0; zz <= z1; ++zz)
-      for (int yy = y0; yy <= y1; ++yy) {
-        const long long row = ((long long)zz * ny + yy) * nx;
-        const int lo = cell_start[row + x0], hi = cell_start[row + x1 + 1];
-        for (int j = lo; j < hi; ++j) {
-          const int k = order[j];
-          double d2 = 0.0;
-#pragma unroll
-          for (int c = 0; c < ND; ++c) {
-            const double df = x[c] - centers[(long long)k * ND + c];
-            d2 += df * df;
-          }
-          if (arg < 0 || d2 < best || (d2 == best && k < arg)) { best = d2; arg = k; }
-        }
-      }
-    const bool whole = x0 == 0 && x1 == nx - 1 && y0 == 0 && y1 == ny - 1 && z0 == 0 && z1 == nz - 1;
-    const double reach = (double)r * h;
-    if (whole || (arg >= 0 && best < reach * reach)) break;
-  }
-  labels[index[i]] = arg + 1;
-}
+//
+// Where the candidates' coordinates lie.  Sorted: the centres ALREADY in cell order (cs[j] = centre order[j]): a
+// candidate is one 16-byte load from a contiguous range, and in 2-D the (up to three) rows' ranges are fetched together
+// before any centre — five dependent memory levels per pixel instead of ten.  ById: the caller's array, candidate j is
+// centers[order[j]] (two dependent trips to L2); scalar loads only, clx_ms_assign_grid promises no alignment.
+enum class Centres { Sorted, ById };
 
-// The same search with the centres ALREADY in cell order (cs[j] = centre order[j]): a candidate is one 16-byte load
-// from a contiguous range instead of order[j] -> centers[order[j]] (two dependent trips to L2), and in 2-D the
-// (up to three) rows' ranges are fetched together before any centre — five dependent memory levels per pixel
-// instead of ten.  Same arithmetic and the same tie rule (smaller centre id) as ms_assign_grid_kernel.
-// One candidate of the search: the centre cs[j] (cell order) with id order[j]; the winner is the minimum under the total
-// order (squared distance, centre id), so the visiting order does not matter.
-template <int ND>
-__device__ __forceinline__ void ms_candidate(const double (&x)[ND], const double* __restrict__ cs,
+// One candidate of the search: slot j of the cell order, the centre with id order[j]; the winner is the minimum under
+// the total order (squared distance, centre id), so the visiting order does not matter.
+template <int ND, Centres SRC>
+__device__ __forceinline__ void ms_candidate(const double (&x)[ND], const double* __restrict__ centres,
                                              const int* __restrict__ order, int j, double& best, int& arg) {
+  const int k = order[j];
   double c[ND];
-  if (ND == 2) {
-    const f64x2 q = *reinterpret_cast<const f64x2*>(cs + (long long)j * 2);
+  if (SRC == Centres::Sorted && ND == 2) {
+    const f64x2 q = *reinterpret_cast<const f64x2*>(centres + (long long)j * 2);
     c[0] = q[0]; c[1] = q[1];
   } else {
+    const long long row = SRC == Centres::Sorted ? j : k;
 #pragma unroll
-    for (int e = 0; e < ND; ++e) c[e] = cs[(long long)j * ND + e];
+    for (int e = 0; e < ND; ++e) c[e] = centres[row * ND + e];
   }
-  const int k = order[j];
   double d2 = 0.0;
 #pragma unroll
   for (int e = 0; e < ND; ++e) {
@@ -629,57 +570,66 @@ __device__ __forceinline__ void ms_candidate(const double (&x)[ND], const double
 
 // The block of cells within r of the pixel's own, r = r0, 2 r0, ...: every centre outside it is at least r h away, so
 // a winner closer than that (strictly) is the nearest centre; otherwise the block doubles until it is the whole grid.
-template <int ND>
-__device__ int ms_ring_search(const double (&x)[ND], int cx, int cy, int cz, int r0, const double* __restrict__ cs,
-                              const int* __restrict__ order, const int* __restrict__ cell_start, double h, int nx,
-                              int ny, int nz) {
+// Returns the centre id (-1: no centre at all).
+template <int ND, Centres SRC>
+__device__ int ms_ring_search(const double (&x)[ND], int cx, int cy, int cz, int r0, const double* __restrict__ centres,
+                              const int* __restrict__ order, const int* __restrict__ cell_start, const Grid& g) {
   double best = 0.0;
   int arg = -1;
   for (int r = r0;; r *= 2) {
-    const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
-    const int y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
-    const int z0 = (ND == 3) ? max(cz - r, 0) : 0, z1 = (ND == 3) ? min(cz + r, nz - 1) : 0;
+    const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
+    const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
+    const int z0 = (ND == 3) ? max(cz - r, 0) : 0, z1 = (ND == 3) ? min(cz + r, g.nz - 1) : 0;
     arg = -1;
     for (int zz = z0; zz <= z1; ++zz)
       for (int yy = y0; yy <= y1; ++yy) {
-        const long long row = ((long long)zz * ny + yy) * nx;
+        const long long row = ((long long)zz * g.ny + yy) * g.nx;
         const int lo = cell_start[row + x0], hi = cell_start[row + x1 + 1];
-        for (int j = lo; j < hi; ++j) ms_candidate<ND>(x, cs, order, j, best, arg);
+        for (int j = lo; j < hi; ++j) ms_candidate<ND, SRC>(x, centres, order, j, best, arg);
       }
-    const bool whole = x0 == 0 && x1 == nx - 1 && y0 == 0 && y1 == ny - 1 && z0 == 0 && z1 == nz - 1;
-    const double reach = (double)r * h;
+    const bool whole = x0 == 0 && x1 == g.nx - 1 && y0 == 0 && y1 == g.ny - 1 && (ND == 2 || (z0 == 0 && z1 == g.nz - 1));
+    const double reach = (double)r * g.h;
     if (whole || (arg >= 0 && best < reach * reach)) break;
   }
   return arg;
 }
 
-template <int ND>
-__global__ __launch_bounds__(256) void ms_assign_cells_kernel(
-    const double* __restrict__ X, const int* __restrict__ index, int nfg, const double* __restrict__ cs,
-    const int* __restrict__ order, const int* __restrict__ cell_start, double ox, double oy,
-    double oz, double h, double inv, int nx, int ny, int nz, int* __restrict__ labels) {
+// the search from the point's own cell
+template <int ND, Centres SRC>
+__device__ __forceinline__ int ms_nearest(const double (&x)[ND], const double* __restrict__ centres,
+                                          const int* __restrict__ order, const int* __restrict__ cell_start,
+                                          const Grid& g) {
+  const int cx = clamp_cell(x[0], g.ox, g.inv, g.nx);
+  const int cy = clamp_cell(x[1], g.oy, g.inv, g.ny);
+  const int cz = (ND == 3) ? clamp_cell(x[ND - 1], g.oz, g.inv, g.nz) : 0;
+  return ms_ring_search<ND, SRC>(x, cx, cy, cz, 1, centres, order, cell_start, g);
+}
+
+template <int ND, Centres SRC>
+__global__ __launch_bounds__(256) void ms_assign_grid_kernel(
+    const double* __restrict__ X, const int* __restrict__ index, int nfg, const double* __restrict__ centres,
+    const int* __restrict__ order, const int* __restrict__ cell_start, Grid g, int* __restrict__ labels) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nfg) return;
   double x[ND];
 #pragma unroll
   for (int c = 0; c < ND; ++c) x[c] = X[(long long)i * ND + c];
-  const int cx = min(max((int)floor((x[0] - ox) * inv), 0), nx - 1);
-  const int cy = min(max((int)floor((x[1] - oy) * inv), 0), ny - 1);
-  const int cz = (ND == 3) ? min(max((int)floor((x[2] - oz) * inv), 0), nz - 1) : 0;
-  labels[index[i]] = ms_ring_search<ND>(x, cx, cy, cz, 1, cs, order, cell_start, h, nx, ny, nz) + 1;
+  labels[index[i]] = ms_nearest<ND, SRC>(x, centres, order, cell_start, g) + 1;
 }
 
 // 2-D search, the common case — the 3 x 3 block holds the winner — as one straight line: the six row-range words of the
 // block together; then the block's candidates as ONE sequence (the three rows' ranges end to end), two per trip, instead
 // of a loop per row (a wavefront holds pixels of ~3 objects, whose centres sit in different rows of their blocks).
-// Offsets are 32-bit (the grid has < 2^31 cells, the host checks), inv = 1 / h comes from the host (the same IEEE
-// quotient).  A pixel whose block does not decide (rare: embeddings cluster around their centre) goes on with
-// ms_ring_search at r = 2.  Returns the centre id (-1: no centre at all).
+// Offsets are 32-bit (the grid has < 2^31 cells, the host checks).  A pixel whose block does not decide (rare:
+// embeddings cluster around their centre) goes on with ms_ring_search at r = 2.  Centres in cell order only.
+// Returns the centre id (-1: no centre at all).
 __device__ __forceinline__ int ms_search_2d(const double (&x)[2], const double* __restrict__ cs,
-                                            const int* __restrict__ order, const int* __restrict__ cell_start, double ox,
-                                            double oy, double h, double inv, int nx, int ny) {
-  const int cx = min(max((int)floor((x[0] - ox) * inv), 0), nx - 1);
-  const int cy = min(max((int)floor((x[1] - oy) * inv), 0), ny - 1);
+                                            const int* __restrict__ order, const int* __restrict__ cell_start,
+                                            const Grid& g) {
+  const double h = g.h;
+  const int nx = g.nx, ny = g.ny;
+  const int cx = clamp_cell(x[0], g.ox, g.inv, nx);
+  const int cy = clamp_cell(x[1], g.oy, g.inv, ny);
   const int x0 = max(cx - 1, 0), x1 = min(cx + 1, nx - 1);
   const int y0 = max(cy - 1, 0), y1 = min(cy + 1, ny - 1);
   // (byte offsets in 32 bits off the uniform base: one address register per load; selects, not branches)
@@ -727,20 +677,20 @@ __device__ __forceinline__ int ms_search_2d(const double (&x)[2], const double* 
     }
   }
   const bool whole = x0 == 0 && x1 == nx - 1 && y0 == 0 && y1 == ny - 1;
-  if (!(whole || (arg >= 0 && best < h * h))) arg = ms_ring_search<2>(x, cx, cy, 0, 2, cs, order, cell_start, h, nx, ny, 1);
+  if (!(whole || (arg >= 0 && best < h * h)))
+    arg = ms_ring_search<2, Centres::Sorted>(x, cx, cy, 0, 2, cs, order, cell_start, g);
   return arg;
 }
 
 __global__ __launch_bounds__(256) void ms_assign_cells2d_kernel(
     const double* __restrict__ X, const int* __restrict__ index, int nfg, const double* __restrict__ cs,
-    const int* __restrict__ order, const int* __restrict__ cell_start, double ox, double oy, double h, double inv,
-    int nx, int ny, int* __restrict__ labels) {
+    const int* __restrict__ order, const int* __restrict__ cell_start, Grid g, int* __restrict__ labels) {
   const unsigned int i = blockIdx.x * 256u + threadIdx.x;
   if (i >= (unsigned int)nfg) return;
   const f64x2 p = *reinterpret_cast<const f64x2*>(X + (size_t)i * 2);
   const int dst = index[i];
   const double x[2] = {p[0], p[1]};
-  labels[dst] = ms_search_2d(x, cs, order, cell_start, ox, oy, h, inv, nx, ny) + 1;
+  labels[dst] = ms_search_2d(x, cs, order, cell_start, g) + 1;
 }
 
 // The assignment that writes the WHOLE label map (round 5).  The form above scatters one 4-byte label per foreground
@@ -762,8 +712,9 @@ template <int U>
 __device__ __forceinline__ void ms_search_2d_multi(const double (&x)[U][2], const bool (&live)[U],
                                                    const double* __restrict__ cs, int ncenters,
                                                    const int* __restrict__ order, const int* __restrict__ cell_start,
-                                                   double ox, double oy, double h, double inv, int nx, int ny,
-                                                   int (&arg)[U]) {
+                                                   const Grid& g, int (&arg)[U]) {
+  const double h = g.h;
+  const int nx = g.nx, ny = g.ny;
   const char* csb = reinterpret_cast<const char*>(cell_start);
   const char* cb = reinterpret_cast<const char*>(cs);
   const char* ob = reinterpret_cast<const char*>(order);
@@ -772,8 +723,8 @@ __device__ __forceinline__ void ms_search_2d_multi(const double (&x)[U][2], cons
   int lo[U][3], hi[U][3];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    cx[u] = min(max((int)floor((x[u][0] - ox) * inv), 0), nx - 1);
-    cy[u] = min(max((int)floor((x[u][1] - oy) * inv), 0), ny - 1);
+    cx[u] = clamp_cell(x[u][0], g.ox, g.inv, nx);
+    cy[u] = clamp_cell(x[u][1], g.oy, g.inv, ny);
     const int x0 = max(cx[u] - 1, 0), x1 = min(cx[u] + 1, nx - 1);
     const int y0 = max(cy[u] - 1, 0), y1 = min(cy[u] + 1, ny - 1);
     whole[u] = x0 == 0 && x1 == nx - 1 && y0 == 0 && y1 == ny - 1;
@@ -832,33 +783,29 @@ __device__ __forceinline__ void ms_search_2d_multi(const double (&x)[U][2], cons
 #pragma unroll
   for (int u = 0; u < U; ++u)
     if (live[u] && !(whole[u] || (arg[u] >= 0 && best[u] < h * h)))
-      arg[u] = ms_ring_search<2>(x[u], cx[u], cy[u], 0, 2, cs, order, cell_start, h, nx, ny, 1);
+      arg[u] = ms_ring_search<2, Centres::Sorted>(x[u], cx[u], cy[u], 0, 2, cs, order, cell_start, g);
 }
 
-constexpr int DENSE_WAVES = 1;          // wave-tiles per block: 1 / 2 / 4 measured 111 / 115 / 116 us at 8192^2
-template <int ND, int PXL, int G, int U>
-__global__ __launch_bounds__(64 * DENSE_WAVES) void ms_assign_dense_kernel(
+// One wave-tile per block of one wavefront (2 / 4 wave-tiles per block measured 115 / 116 us against 111 us at 8192^2);
+// U = 2 points of a lane searched together (104 us at 8192^2; 1: 128, 3: 117, 4: 127).
+constexpr int DENSE_U = 2;
+template <int ND, int PXL>
+__global__ __launch_bounds__(64) void ms_assign_dense_kernel(
     const double* __restrict__ X, const double* __restrict__ cs, int ncenters, const int* __restrict__ order,
-    const int* __restrict__ cell_start, double ox, double oy, double oz, double h, double inv, int nx, int ny, int nz,
-    const unsigned long long* __restrict__ flags, const int* __restrict__ counts, const int* __restrict__ tile_start,
-    long long npix, int vec, int* __restrict__ labels) {
+    const int* __restrict__ cell_start, Grid grid, const unsigned long long* __restrict__ flags,
+    const int* __restrict__ counts, const int* __restrict__ tile_start, long long npix, int vec,
+    int* __restrict__ labels) {
+  constexpr int G = 16 / PXL, U = DENSE_U;
   constexpr int WT = 64 * G * PXL;
-  __shared__ int lab_all[DENSE_WAVES * WT];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int* lab = lab_all + wave * WT;                      // (a wavefront's own tile: no barrier between wavefronts)
-  const int wt = blockIdx.x * DENSE_WAVES + wave;
+  __shared__ int lab[WT];
+  const int lane = threadIdx.x;
+  const int wt = blockIdx.x;
   // wave-uniform words first: the tile's points, its flag words (scalar loads, in flight under phase 1)
   const int p0 = tile_start[wt];
   const int total = counts[wt];
   int run = 0;
-  const unsigned long long* tf = flags + (long long)wt * G * PXL;
-  unsigned long long B[G][PXL];
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int e = 0; e < PXL; ++e) B[g][e] = tf[g * PXL + e];
-  if (ND == 2) {
+  const TileFlags<G, PXL> tile(flags, wt);
+  if constexpr (ND == 2) {
     for (int q0 = 0; q0 < total; q0 += 64 * U) {
       double x[U][2];
       bool live[U];
@@ -870,7 +817,7 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void ms_assign_dense_kernel(
         const f64x2 p = *reinterpret_cast<const f64x2*>(X + (size_t)(p0 + (live[u] ? q : 0)) * 2);
         x[u][0] = p[0]; x[u][1] = p[1];
       }
-      ms_search_2d_multi<U>(x, live, cs, ncenters, order, cell_start, ox, oy, h, inv, nx, ny, arg);
+      ms_search_2d_multi<U>(x, live, cs, ncenters, order, cell_start, grid, arg);
 #pragma unroll
       for (int u = 0; u < U; ++u)
         if (live[u]) lab[q0 + u * 64 + lane] = arg[u] + 1;
@@ -880,29 +827,21 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void ms_assign_dense_kernel(
       double x[ND];
 #pragma unroll
       for (int c = 0; c < ND; ++c) x[c] = X[(size_t)(p0 + q) * ND + c];
-      const int cx = min(max((int)floor((x[0] - ox) * inv), 0), nx - 1);
-      const int cy = min(max((int)floor((x[1] - oy) * inv), 0), ny - 1);
-      const int cz = min(max((int)floor((x[ND - 1] - oz) * inv), 0), nz - 1);
-      lab[q] = ms_ring_search<ND>(x, cx, cy, cz, 1, cs, order, cell_start, h, nx, ny, nz) + 1;
+      lab[q] = ms_nearest<ND, Centres::Sorted>(x, cs, order, cell_start, grid) + 1;
     }
   }
   __builtin_amdgcn_wave_barrier();                     // the wavefront's LDS operations execute in order
   const long long base = (long long)wt * WT;
   if (base >= npix) return;
-  const unsigned long long lower = (1ull << lane) - 1ull;
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    int bef = 0, cnt = 0;
-#pragma unroll
-    for (int e = 0; e < PXL; ++e) {
-      bef += __popcll(B[g][e] & lower);
-      cnt += __popcll(B[g][e]);
-    }
+    int bef, cnt;
+    tile.count(g, lane, bef, cnt);
     int pos = run + bef;
     int out[PXL];
 #pragma unroll
     for (int e = 0; e < PXL; ++e) {
-      const bool fg = (B[g][e] >> lane) & 1ull;
+      const bool fg = tile.set(g, e, lane);
       out[e] = fg ? lab[fg ? pos : 0] : 0;
       pos += fg ? 1 : 0;
     }
@@ -923,91 +862,128 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void ms_assign_dense_kernel(
 
 }  // namespace
 
-// workspace of the compaction: [flags: one bit per pixel, whole wave-tiles][counts: nwt ints][chunk counts of the flags pass: <= nwt / 4 ints]
-static long long wave_tiles(long long npix) { return (npix + 4095) / 4096 * 4; }      // whole groups of four
-
-extern "C" size_t clx_ms_prepare_workspace(long long npix) {
-  const long long nwt = wave_tiles(npix);
-  return (size_t)nwt * 128 + (size_t)(3 * nwt + 2) * sizeof(int) + 64;
+// ---------------------------------------------------------------------------------------------
+// HOST: what the entry points share.  A check sets the error under the entry's name and returns CLX_ERR_ARG.
+// ---------------------------------------------------------------------------------------------
+// launch(std::integral_constant<int, ND>) for ND = 2 or 3 (every entry refuses any other ND before it gets here)
+template <typename F>
+static void for_nd(int ND, F&& launch) {
+  if (ND == 2) launch(std::integral_constant<int, 2>{});
+  else launch(std::integral_constant<int, 3>{});
 }
 
-template <int ND, typename TIn, int G, bool WB, int BLOCKS>
-static void launch_prepare(TIn* emb, const TIn* std, double threshold, int Z, int Y, int X, double* Xout, int* index,
-                           int* nfg_out, void* workspace, hipStream_t st) {
-  constexpr int PXL = 16 / (int)sizeof(TIn);
-  static_assert(64 * G * PXL == 1024, "wave-tiles of 1024 pixels");
+static Grid make_grid(const double* origin, double cell, int nx, int ny, int nz, int ND) {
+  return Grid{origin[0], origin[1], ND == 3 ? origin[2] : 0.0, cell, 1.0 / cell, nx, ny, nz};
+}
+
+static int check_grid(const char* entry, int ND, double cell, int nx, int ny, int nz) {
+  CLX_REQUIRE(cell > 0.0 && nx > 0 && ny > 0 && nz > 0 && (ND == 3 || nz == 1), "%s: bad grid", entry);
+  return CLX_OK;
+}
+
+// what the searches over cell-ordered centres ask for: 32-bit cell offsets, and in 2-D 16-byte loads of points and centres
+static int check_sorted_search(const char* entry, int ND, const double* X, const double* centers_sorted, int nx, int ny,
+                               int nz) {
+  CLX_REQUIRE((long long)nx * ny * nz < (1ll << 31) - 1, "%s: more than 2^31 cells", entry);
+  CLX_REQUIRE(ND == 3 || ((((uintptr_t)X | (uintptr_t)centers_sorted) & 15) == 0), "%s: 16-byte alignment", entry);
+  return CLX_OK;
+}
+
+// the image of the compaction and its workspace
+static int check_image(const char* entry, int ND, int Z, int Y, int X, const void* workspace) {
+  CLX_REQUIRE((ND == 2 || ND == 3) && Z > 0 && Y > 0 && X > 0, "%s: bad extents", entry);
+  CLX_REQUIRE(ND == 3 || Z == 1, "%s: Z must be 1 for 2-D data", entry);
+  CLX_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", entry);
+  CLX_REQUIRE((long long)Z * Y * X < (1ll << 31), "%s: too many pixels", entry);
+  return CLX_OK;
+}
+
+// workspace of the compaction: [flags: one bit per pixel, whole wave-tiles: 128 bytes each][counts: nwt ints]
+// [chunk counts of the flags pass: one per block, <= nwt / 4, in nwt ints][tile_start, the points in front of every
+// tile: nwt ints][2 ints + 64 bytes spare].  nwt is a multiple of four, so counts is 16-byte aligned where flags is.
+struct PrepareWorkspace {
+  unsigned long long* flags;
+  int *counts, *chunk_counts, *tile_start;
+  int nwt;
+  size_t bytes;
+};
+static PrepareWorkspace prepare_workspace_of(const void* workspace, long long npix) {
+  const long long nwt = (npix + 4095) / 4096 * 4;      // wave-tiles of 1024 pixels, whole groups of four
+  const uintptr_t flags = (uintptr_t)workspace, counts = flags + (size_t)nwt * 128;
+  return PrepareWorkspace{(unsigned long long*)flags, (int*)counts, (int*)(counts + (size_t)nwt * sizeof(int)),
+                          (int*)(counts + (size_t)(2 * nwt) * sizeof(int)), (int)nwt,
+                          (size_t)nwt * 128 + (size_t)(3 * nwt + 2) * sizeof(int) + 64};
+}
+
+extern "C" size_t clx_ms_prepare_workspace(long long npix) { return prepare_workspace_of(nullptr, npix).bytes; }
+
+constexpr int FLAGS_BLOCKS = 2048;      // the flags pass in at most this many blocks (the scatter pass: a block per four tiles)
+
+template <typename TIn>
+static int ms_prepare(const char* entry, TIn* emb, const TIn* sd, double threshold, int ND, int Z, int Y, int X,
+                      double* Xout, int* index, int* nfg_out, void* workspace, clx_stream stream) {
+  CLX_REQUIRE(emb && sd && Xout && nfg_out && workspace, "%s: null pointer", entry);
+  if (const int rc = check_image(entry, ND, Z, Y, X, workspace)) return rc;
+  constexpr int PXL = 16 / (int)sizeof(TIn), G = 16 / PXL;      // wave-tiles of 64 * G * PXL = 1024 pixels
+  constexpr bool WB = std::is_same<TIn, double>::value;          // float64: coordinates added in place
   const long long npix = (long long)Z * Y * X;
-  const int nwt = (int)wave_tiles(npix);
-  unsigned long long* flags = (unsigned long long*)workspace;
-  int* counts = (int*)(flags + (size_t)nwt * 16);          // 16-byte aligned: nwt is a multiple of 4
-  int* chunk_counts = counts + nwt;                         // one per block of the flags pass (<= nwt / 4)
-  int* tile_start = counts + 2 * nwt;                       // the points in front of every tile
+  const PrepareWorkspace ws = prepare_workspace_of(workspace, npix);
+  const int nwt = ws.nwt;
   // every channel plane starts at a multiple of npix elements: 16-byte accesses need npix % PXL == 0 and aligned bases
-  const int vec = (npix % PXL == 0) && (((uintptr_t)emb | (uintptr_t)std) & 15) == 0 ? 1 : 0;
+  const int vec = (npix % PXL == 0) && (((uintptr_t)emb | (uintptr_t)sd) & 15) == 0 ? 1 : 0;
   const FastDiv dX = make_fastdiv((uint32_t)X), dY = make_fastdiv((uint32_t)Y);
-  static const int g1cap = getenv("CLX_MS_FLAGS_GRID") ? atoi(getenv("CLX_MS_FLAGS_GRID")) : 2048;        // (sweeps)
-  static const int g3cap = getenv("CLX_MS_SCATTER_GRID") ? atoi(getenv("CLX_MS_SCATTER_GRID")) : 1 << 20;
-  // the flags pass in at most g1cap blocks of contiguous chunks, a multiple of four tiles each
-  int tiles_per_block = (nwt + g1cap - 1) / (g1cap > 0 ? g1cap : 1);
-  tiles_per_block = (tiles_per_block + 3) / 4 * 4;
+  // the flags pass in contiguous chunks, a multiple of four tiles each
+  const int tiles_per_block = ((nwt + FLAGS_BLOCKS - 1) / FLAGS_BLOCKS + 3) / 4 * 4;
   const int g1 = (nwt + tiles_per_block - 1) / tiles_per_block;
-  const int nb = (nwt + 3) / 4;
-  const int g3 = nb < g3cap ? nb : g3cap;
-  CLX_LAUNCH_KIND(CLX_PROF_MS_PREPARE, (ms_flags_kernel<TIn, G>), dim3(g1), dim3(256), 0, st, std, threshold, npix, vec,
-                  nwt, tiles_per_block, flags, counts, chunk_counts);
-  CLX_LAUNCH_KIND(CLX_PROF_MS_PREPARE, (ms_scatter_kernel<ND, TIn, G, WB, BLOCKS>), dim3(g3), dim3(256), 0, st, emb, dX, dY,
-                  Y, X, npix, vec, nwt, flags, counts, chunk_counts, tiles_per_block, Xout, index, nfg_out, tile_start);
+  hipStream_t st = (hipStream_t)stream;
+  CLX_LAUNCH_KIND(CLX_PROF_MS_PREPARE, (ms_flags_kernel<TIn, G>), dim3(g1), dim3(256), 0, st, sd, threshold, npix, vec,
+                  nwt, tiles_per_block, ws.flags, ws.counts, ws.chunk_counts);
+  for_nd(ND, [&](auto nd) {
+    constexpr int D = decltype(nd)::value;
+    constexpr int BLOCKS = WB ? (D == 2 ? 3 : 2) : (D == 2 ? 4 : 3);      // blocks per CU the registers are held to
+    CLX_LAUNCH_KIND(CLX_PROF_MS_PREPARE, (ms_scatter_kernel<D, TIn, G, WB, BLOCKS>), dim3(nwt / 4), dim3(256), 0, st, emb,
+                    dX, dY, Y, X, npix, vec, nwt, ws.flags, ws.counts, ws.chunk_counts, tiles_per_block, Xout, index,
+                    nfg_out, ws.tile_start);
+  });
+  CLX_CHECK_LAUNCH(entry);
+  return CLX_OK;
 }
 
 extern "C" int clx_ms_prepare(double* emb, const double* std, double threshold, int ND,
                               int Z, int Y, int X, double* Xout, int* index, int* nfg_out,
                               void* workspace, clx_stream stream) {
-  CLX_REQUIRE(emb && std && Xout && nfg_out && workspace, "clx_ms_prepare: null pointer");
-  CLX_REQUIRE((ND == 2 || ND == 3) && Z > 0 && Y > 0 && X > 0, "clx_ms_prepare: bad extents");
-  CLX_REQUIRE(ND == 3 || Z == 1, "clx_ms_prepare: Z must be 1 for 2-D data");
-  CLX_REQUIRE(((uintptr_t)workspace & 15) == 0, "clx_ms_prepare: workspace must be 16-byte aligned");
-  const long long npix = (long long)Z * Y * X;
-  CLX_REQUIRE(npix < (1ll << 31), "clx_ms_prepare: too many pixels");
-  hipStream_t st = (hipStream_t)stream;
-  if (ND == 2) launch_prepare<2, double, 8, true, 3>(emb, std, threshold, Z, Y, X, Xout, index, nfg_out, workspace, st);
-  else launch_prepare<3, double, 8, true, 2>(emb, std, threshold, Z, Y, X, Xout, index, nfg_out, workspace, st);
-  CLX_CHECK_LAUNCH("clx_ms_prepare");
-  return CLX_OK;
+  return ms_prepare("clx_ms_prepare", emb, std, threshold, ND, Z, Y, X, Xout, index, nfg_out, workspace, stream);
 }
 
 extern "C" int clx_ms_prepare_f32(const float* emb, const float* std, double threshold, int ND,
                                   int Z, int Y, int X, double* Xout, int* index, int* nfg_out,
                                   void* workspace, clx_stream stream) {
-  CLX_REQUIRE(emb && std && Xout && nfg_out && workspace, "clx_ms_prepare_f32: null pointer");
-  CLX_REQUIRE((ND == 2 || ND == 3) && Z > 0 && Y > 0 && X > 0, "clx_ms_prepare_f32: bad extents");
-  CLX_REQUIRE(ND == 3 || Z == 1, "clx_ms_prepare_f32: Z must be 1 for 2-D data");
-  CLX_REQUIRE(((uintptr_t)workspace & 15) == 0, "clx_ms_prepare_f32: workspace must be 16-byte aligned");
-  const long long npix = (long long)Z * Y * X;
-  CLX_REQUIRE(npix < (1ll << 31), "clx_ms_prepare_f32: too many pixels");
-  hipStream_t st = (hipStream_t)stream;
-  float* e = const_cast<float*>(emb);          // (WB = false: never written)
-  if (ND == 2) launch_prepare<2, float, 4, false, 4>(e, std, threshold, Z, Y, X, Xout, index, nfg_out, workspace, st);
-  else launch_prepare<3, float, 4, false, 3>(e, std, threshold, Z, Y, X, Xout, index, nfg_out, workspace, st);
-  CLX_CHECK_LAUNCH("clx_ms_prepare_f32");
+  // (float32 input is never written: WB is false)
+  return ms_prepare("clx_ms_prepare_f32", const_cast<float*>(emb), std, threshold, ND, Z, Y, X, Xout, index, nfg_out,
+                    workspace, stream);
+}
+
+template <typename Source>
+static int ms_iterate(const char* entry, const double* fit, int nfit, const Source& source, const double* seeds, int nseeds,
+                      int ND, double bandwidth, int max_iter, double* centers, int* counts, int* iters,
+                      clx_stream stream) {
+  CLX_REQUIRE(fit && seeds && centers && counts && iters, "%s: null pointer", entry);
+  CLX_REQUIRE((ND == 2 || ND == 3) && nfit >= 0 && nseeds >= 0 && max_iter >= 0, "%s: bad extents", entry);
+  CLX_REQUIRE(bandwidth > 0.0, "%s: bandwidth must be positive", entry);
+  if (nseeds == 0) return CLX_OK;
+  for_nd(ND, [&](auto nd) {
+    ms_iterate_kernel<decltype(nd)::value><<<(nseeds + 3) / 4, 256, 0, (hipStream_t)stream>>>(
+        fit, source, seeds, nseeds, bandwidth, max_iter, centers, counts, iters);
+  });
+  CLX_CHECK_LAUNCH(entry);
   return CLX_OK;
 }
 
 extern "C" int clx_ms_iterate(const double* fit, int nfit, const double* seeds, int nseeds,
                               int ND, double bandwidth, int max_iter, double* centers,
                               int* counts, int* iters, clx_stream stream) {
-  CLX_REQUIRE(fit && seeds && centers && counts && iters, "clx_ms_iterate: null pointer");
-  CLX_REQUIRE((ND == 2 || ND == 3) && nfit >= 0 && nseeds >= 0 && max_iter >= 0,
-              "clx_ms_iterate: bad extents");
-  CLX_REQUIRE(bandwidth > 0.0, "clx_ms_iterate: bandwidth must be positive");
-  if (nseeds == 0) return CLX_OK;
-  const int grid = (nseeds + 3) / 4;
-  hipStream_t st = (hipStream_t)stream;
-  if (ND == 2)
-    ms_iterate_kernel<2><<<grid, 256, 0, st>>>(fit, nfit, seeds, nseeds, bandwidth, max_iter, centers, counts, iters);
-  else
-    ms_iterate_kernel<3><<<grid, 256, 0, st>>>(fit, nfit, seeds, nseeds, bandwidth, max_iter, centers, counts, iters);
-  CLX_CHECK_LAUNCH("clx_ms_iterate");
-  return CLX_OK;
+  return ms_iterate("clx_ms_iterate", fit, nfit, AllPoints{nfit}, seeds, nseeds, ND, bandwidth, max_iter, centers, counts,
+                    iters, stream);
 }
 
 extern "C" int clx_ms_iterate_grid(const double* fit_sorted, int nfit, const int* cell_start,
@@ -1015,26 +991,13 @@ extern "C" int clx_ms_iterate_grid(const double* fit_sorted, int nfit, const int
                                    const double* seeds, int nseeds, int ND, double bandwidth,
                                    int max_iter, double* centers, int* counts, int* iters,
                                    clx_stream stream) {
-  CLX_REQUIRE(fit_sorted && cell_start && origin && seeds && centers && counts && iters,
-              "clx_ms_iterate_grid: null pointer");
-  CLX_REQUIRE((ND == 2 || ND == 3) && nfit >= 0 && nseeds >= 0 && max_iter >= 0,
-              "clx_ms_iterate_grid: bad extents");
-  CLX_REQUIRE(bandwidth > 0.0 && cell >= bandwidth, "clx_ms_iterate_grid: cell edge must be >= bandwidth > 0");
-  CLX_REQUIRE(nx > 0 && ny > 0 && nz > 0 && (ND == 3 || nz == 1), "clx_ms_iterate_grid: bad grid");
-  if (nseeds == 0) return CLX_OK;
-  const int grid = (nseeds + 3) / 4;
-  hipStream_t st = (hipStream_t)stream;
-  const double inv = 1.0 / cell;
-  if (ND == 2)
-    ms_iterate_grid_kernel<2><<<grid, 256, 0, st>>>(fit_sorted, cell_start, origin[0], origin[1], 0.0, inv,
-                                                     nx, ny, nz, seeds, nseeds, bandwidth, max_iter,
-                                                     centers, counts, iters);
-  else
-    ms_iterate_grid_kernel<3><<<grid, 256, 0, st>>>(fit_sorted, cell_start, origin[0], origin[1], origin[2],
-                                                     inv, nx, ny, nz, seeds, nseeds, bandwidth, max_iter,
-                                                     centers, counts, iters);
-  CLX_CHECK_LAUNCH("clx_ms_iterate_grid");
-  return CLX_OK;
+  const char* entry = "clx_ms_iterate_grid";
+  CLX_REQUIRE(cell_start && origin, "%s: null pointer", entry);
+  CLX_REQUIRE(cell >= bandwidth, "%s: cell edge must be >= bandwidth", entry);
+  if (const int rc = check_grid(entry, ND, cell, nx, ny, nz)) return rc;
+  // (make_grid reads origin[2] only for ND == 3; any other ND than 2 or 3 is refused below, with the rest)
+  return ms_iterate(entry, fit_sorted, nfit, CellsAround{cell_start, make_grid(origin, cell, nx, ny, nz, ND)}, seeds,
+                    nseeds, ND, bandwidth, max_iter, centers, counts, iters, stream);
 }
 
 extern "C" int clx_ms_assign(const double* X, const int* index, int nfg, const double* centers,
@@ -1042,12 +1005,10 @@ extern "C" int clx_ms_assign(const double* X, const int* index, int nfg, const d
   CLX_REQUIRE(X && index && centers && labels, "clx_ms_assign: null pointer");
   CLX_REQUIRE((ND == 2 || ND == 3) && nfg >= 0 && ncenters > 0, "clx_ms_assign: bad extents");
   if (nfg == 0) return CLX_OK;
-  const int grid = (nfg + 255) / 256;
-  hipStream_t st = (hipStream_t)stream;
-  if (ND == 2)
-    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_kernel<2>), dim3(grid), dim3(256), 0, st, X, index, nfg, centers, ncenters, labels);
-  else
-    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_kernel<3>), dim3(grid), dim3(256), 0, st, X, index, nfg, centers, ncenters, labels);
+  for_nd(ND, [&](auto nd) {
+    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_kernel<decltype(nd)::value>), dim3((nfg + 255) / 256), dim3(256), 0,
+                    (hipStream_t)stream, X, index, nfg, centers, ncenters, labels);
+  });
   CLX_CHECK_LAUNCH("clx_ms_assign");
   return CLX_OK;
 }
@@ -1058,16 +1019,13 @@ extern "C" int clx_ms_assign_grid(const double* X, const int* index, int nfg, co
                                   clx_stream stream) {
   CLX_REQUIRE(X && index && centers && labels && order && cell_start && origin, "clx_ms_assign_grid: null pointer");
   CLX_REQUIRE((ND == 2 || ND == 3) && nfg >= 0 && ncenters > 0, "clx_ms_assign_grid: bad extents");
-  CLX_REQUIRE(cell > 0.0 && nx > 0 && ny > 0 && nz > 0 && (ND == 3 || nz == 1), "clx_ms_assign_grid: bad grid");
+  if (const int rc = check_grid("clx_ms_assign_grid", ND, cell, nx, ny, nz)) return rc;
   if (nfg == 0) return CLX_OK;
-  const int grid = (nfg + 255) / 256;
-  hipStream_t st = (hipStream_t)stream;
-  if (ND == 2)
-    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_grid_kernel<2>), dim3(grid), dim3(256), 0, st, X, index, nfg, centers, ncenters, order, cell_start, origin[0],
-                                                    origin[1], 0.0, cell, nx, ny, nz, labels);
-  else
-    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_grid_kernel<3>), dim3(grid), dim3(256), 0, st, X, index, nfg, centers, ncenters, order, cell_start, origin[0],
-                                                    origin[1], origin[2], cell, nx, ny, nz, labels);
+  const Grid g = make_grid(origin, cell, nx, ny, nz, ND);
+  for_nd(ND, [&](auto nd) {
+    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_grid_kernel<decltype(nd)::value, Centres::ById>), dim3((nfg + 255) / 256),
+                    dim3(256), 0, (hipStream_t)stream, X, index, nfg, centers, order, cell_start, g, labels);
+  });
   CLX_CHECK_LAUNCH("clx_ms_assign_grid");
   return CLX_OK;
 }
@@ -1076,65 +1034,50 @@ extern "C" int clx_ms_assign_cells(const double* X, const int* index, int nfg, c
                                    int ncenters, int ND, const int* order, const int* cell_start,
                                    const double* origin, double cell, int nx, int ny, int nz, int* labels,
                                    clx_stream stream) {
-  CLX_REQUIRE(X && index && centers_sorted && labels && order && cell_start && origin, "clx_ms_assign_cells: null pointer");
-  CLX_REQUIRE((ND == 2 || ND == 3) && nfg >= 0 && ncenters > 0, "clx_ms_assign_cells: bad extents");
-  CLX_REQUIRE(cell > 0.0 && nx > 0 && ny > 0 && nz > 0 && (ND == 3 || nz == 1), "clx_ms_assign_cells: bad grid");
-  CLX_REQUIRE((long long)nx * ny * nz < (1ll << 31) - 1, "clx_ms_assign_cells: more than 2^31 cells");
-  CLX_REQUIRE(ND == 3 || ((((uintptr_t)X | (uintptr_t)centers_sorted) & 15) == 0), "clx_ms_assign_cells: 16-byte alignment");
+  const char* entry = "clx_ms_assign_cells";
+  CLX_REQUIRE(X && index && centers_sorted && labels && order && cell_start && origin, "%s: null pointer", entry);
+  CLX_REQUIRE((ND == 2 || ND == 3) && nfg >= 0 && ncenters > 0, "%s: bad extents", entry);
+  if (const int rc = check_grid(entry, ND, cell, nx, ny, nz)) return rc;
+  if (const int rc = check_sorted_search(entry, ND, X, centers_sorted, nx, ny, nz)) return rc;
   if (nfg == 0) return CLX_OK;
-  const int grid = (nfg + 255) / 256;
+  const dim3 blocks((nfg + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  const double inv = 1.0 / cell;
-  if (ND == 2)
-    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, ms_assign_cells2d_kernel, dim3(grid), dim3(256), 0, st, X, index, nfg, centers_sorted, order, cell_start,
-                    origin[0], origin[1], cell, inv, nx, ny, labels);
+  const Grid g = make_grid(origin, cell, nx, ny, nz, ND);
+  if (ND == 2)      // (the straight-line 2-D search has a kernel of its own)
+    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, ms_assign_cells2d_kernel, blocks, dim3(256), 0, st, X, index, nfg, centers_sorted,
+                    order, cell_start, g, labels);
   else
-    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_cells_kernel<3>), dim3(grid), dim3(256), 0, st, X, index, nfg, centers_sorted, order, cell_start, origin[0],
-                                                     origin[1], origin[2], cell, inv, nx, ny, nz, labels);
-  CLX_CHECK_LAUNCH("clx_ms_assign_cells");
+    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_grid_kernel<3, Centres::Sorted>), blocks, dim3(256), 0, st, X, index, nfg,
+                    centers_sorted, order, cell_start, g, labels);
+  CLX_CHECK_LAUNCH(entry);
   return CLX_OK;
-}
-
-template <int ND, int PXL, int G>
-static void launch_assign_dense(const double* X, const double* cs, int ncenters, const int* order, const int* cell_start,
-                                const double* origin, double cell, int nx, int ny, int nz, const void* workspace,
-                                long long npix, int* labels, hipStream_t st) {
-  const int nwt = (int)wave_tiles(npix);
-  const unsigned long long* flags = (const unsigned long long*)workspace;
-  const int* counts = (const int*)(flags + (size_t)nwt * 16);
-  const int* tile_start = counts + 2 * nwt;
-  const int vec = (npix % PXL == 0) && (((uintptr_t)labels) & 15) == 0 ? 1 : 0;
-  static const int u = getenv("CLX_MS_DENSE_U") ? atoi(getenv("CLX_MS_DENSE_U")) : 2;      // (sweep: 104 us at 8192^2; 1: 128, 3: 117, 4: 127)
-#define CLX_DENSE(UU) CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_dense_kernel<ND, PXL, G, UU>), dim3(nwt / DENSE_WAVES), dim3(64 * DENSE_WAVES), 0, st, X, cs, ncenters, order, \
-                  cell_start, origin[0], origin[1], ND == 3 ? origin[2] : 0.0, cell, 1.0 / cell, nx, ny, nz, flags, counts, \
-                  tile_start, npix, vec, labels)
-  if (ND == 2 && u == 1) CLX_DENSE(1); else if (ND == 2 && u == 2) CLX_DENSE(2); else if (ND == 2 && u == 3) CLX_DENSE(3); else if (ND == 2 && u == 4) CLX_DENSE(4); else CLX_DENSE(2);
-#undef CLX_DENSE
 }
 
 extern "C" int clx_ms_assign_dense(const double* X, const double* centers_sorted, int ncenters, int ND, const int* order,
                                    const int* cell_start, const double* origin, double cell, int nx, int ny, int nz,
                                    const void* prepare_workspace, int prepared_from_f32, int Z, int Y, int Xdim,
                                    int* labels, clx_stream stream) {
-  CLX_REQUIRE(X && centers_sorted && labels && order && cell_start && origin && prepare_workspace,
-              "clx_ms_assign_dense: null pointer");
-  CLX_REQUIRE((ND == 2 || ND == 3) && ncenters > 0 && Z > 0 && Y > 0 && Xdim > 0 && (ND == 3 || Z == 1),
-              "clx_ms_assign_dense: bad extents");
-  CLX_REQUIRE(cell > 0.0 && nx > 0 && ny > 0 && nz > 0 && (ND == 3 || nz == 1), "clx_ms_assign_dense: bad grid");
-  CLX_REQUIRE((long long)nx * ny * nz < (1ll << 31) - 1, "clx_ms_assign_dense: more than 2^31 cells");
-  CLX_REQUIRE(ND == 3 || ((((uintptr_t)X | (uintptr_t)centers_sorted) & 15) == 0), "clx_ms_assign_dense: 16-byte alignment");
-  CLX_REQUIRE(((uintptr_t)prepare_workspace & 15) == 0, "clx_ms_assign_dense: workspace must be 16-byte aligned");
+  const char* entry = "clx_ms_assign_dense";
+  CLX_REQUIRE(X && centers_sorted && labels && order && cell_start && origin && prepare_workspace, "%s: null pointer", entry);
+  CLX_REQUIRE(ncenters > 0, "%s: bad extents", entry);
+  if (const int rc = check_image(entry, ND, Z, Y, Xdim, prepare_workspace)) return rc;
+  if (const int rc = check_grid(entry, ND, cell, nx, ny, nz)) return rc;
+  if (const int rc = check_sorted_search(entry, ND, X, centers_sorted, nx, ny, nz)) return rc;
   const long long npix = (long long)Z * Y * Xdim;
-  CLX_REQUIRE(npix < (1ll << 31), "clx_ms_assign_dense: too many pixels");
-  hipStream_t st = (hipStream_t)stream;
-  if (prepared_from_f32) {
-    if (ND == 2) launch_assign_dense<2, 4, 4>(X, centers_sorted, ncenters, order, cell_start, origin, cell, nx, ny, nz, prepare_workspace, npix, labels, st);
-    else launch_assign_dense<3, 4, 4>(X, centers_sorted, ncenters, order, cell_start, origin, cell, nx, ny, nz, prepare_workspace, npix, labels, st);
-  } else {
-    if (ND == 2) launch_assign_dense<2, 2, 8>(X, centers_sorted, ncenters, order, cell_start, origin, cell, nx, ny, nz, prepare_workspace, npix, labels, st);
-    else launch_assign_dense<3, 2, 8>(X, centers_sorted, ncenters, order, cell_start, origin, cell, nx, ny, nz, prepare_workspace, npix, labels, st);
-  }
-  CLX_CHECK_LAUNCH("clx_ms_assign_dense");
+  const PrepareWorkspace ws = prepare_workspace_of(prepare_workspace, npix);
+  const Grid g = make_grid(origin, cell, nx, ny, nz, ND);
+  // the wave-tiles are those of the compaction: 16-byte groups of PXL = 4 pixels of float32 input, 2 of float64
+  auto launch = [&](auto nd, auto pxl) {
+    constexpr int D = decltype(nd)::value, PXL = decltype(pxl)::value;
+    const int vec = (npix % PXL == 0) && (((uintptr_t)labels) & 15) == 0 ? 1 : 0;
+    CLX_LAUNCH_KIND(CLX_PROF_MS_ASSIGN, (ms_assign_dense_kernel<D, PXL>), dim3(ws.nwt), dim3(64), 0, (hipStream_t)stream, X,
+                    centers_sorted, ncenters, order, cell_start, g, ws.flags, ws.counts, ws.tile_start, npix, vec, labels);
+  };
+  for_nd(ND, [&](auto nd) {
+    if (prepared_from_f32) launch(nd, std::integral_constant<int, 4>{});
+    else launch(nd, std::integral_constant<int, 2>{});
+  });
+  CLX_CHECK_LAUNCH(entry);
   return CLX_OK;
 }
 
@@ -1283,8 +1226,8 @@ extern "C" int clx_ms_bucket(const double* fit, int n, int ND, const double* ori
                              int ny, int nz, double* fit_sorted, int* cell_start, void* workspace,
                              clx_stream stream) {
   CLX_REQUIRE(fit && origin && fit_sorted && cell_start && workspace, "clx_ms_bucket: null pointer");
-  CLX_REQUIRE((ND == 2 || ND == 3) && n >= 0 && cell > 0.0, "clx_ms_bucket: bad extents");
-  CLX_REQUIRE(nx > 0 && ny > 0 && nz > 0 && (ND == 3 || nz == 1), "clx_ms_bucket: bad grid");
+  CLX_REQUIRE((ND == 2 || ND == 3) && n >= 0, "clx_ms_bucket: bad extents");
+  if (const int rc = check_grid("clx_ms_bucket", ND, cell, nx, ny, nz)) return rc;
   const long long ncells = (long long)nx * ny * nz;
   CLX_REQUIRE(ncells < (1ll << 30), "clx_ms_bucket: too many cells");
   hipStream_t st = (hipStream_t)stream;
@@ -1298,26 +1241,19 @@ extern "C" int clx_ms_bucket(const double* fit, int n, int ND, const double* ori
   }
   const int grid = n > 0 ? (n + 255) / 256 : 1;
   const double oz = ND == 3 ? origin[2] : 0.0;
-  if (n > 0) {
-    if (ND == 2)
-      bucket_count_kernel<2><<<grid, 256, 0, st>>>(fit, n, origin[0], origin[1], oz, cell, nx, ny, nz, cid, counts);
-    else
-      bucket_count_kernel<3><<<grid, 256, 0, st>>>(fit, n, origin[0], origin[1], oz, cell, nx, ny, nz, cid, counts);
-  }
-  bucket_scan_kernel<<<1, 1024, 0, st>>>(counts, (int)ncells, cell_start);
-  if (n > 0) {
-    bucket_scatter_kernel<<<grid, 256, 0, st>>>(cid, n, cell_start, counts, slot_idx);
-    long long waves = ncells < 65536 ? ncells : 65536;
-    const int ogrid = (int)((waves * 64 + 255) / 256);
-    const int bgrid = grid < 8192 ? grid : 8192;
-    if (ND == 2) {
-      bucket_order_kernel<2><<<ogrid, 256, 0, st>>>(fit, cell_start, (int)ncells, slot_idx, fit_sorted, any_big);
-      bucket_order_big_kernel<2><<<bgrid, 256, 0, st>>>(fit, n, cid, cell_start, slot_idx, fit_sorted, any_big);
-    } else {
-      bucket_order_kernel<3><<<ogrid, 256, 0, st>>>(fit, cell_start, (int)ncells, slot_idx, fit_sorted, any_big);
-      bucket_order_big_kernel<3><<<bgrid, 256, 0, st>>>(fit, n, cid, cell_start, slot_idx, fit_sorted, any_big);
+  const long long waves = ncells < 65536 ? ncells : 65536;
+  const int ogrid = (int)((waves * 64 + 255) / 256);
+  const int bgrid = grid < 8192 ? grid : 8192;
+  for_nd(ND, [&](auto nd) {
+    constexpr int D = decltype(nd)::value;
+    if (n > 0) bucket_count_kernel<D><<<grid, 256, 0, st>>>(fit, n, origin[0], origin[1], oz, cell, nx, ny, nz, cid, counts);
+    bucket_scan_kernel<<<1, 1024, 0, st>>>(counts, (int)ncells, cell_start);
+    if (n > 0) {
+      bucket_scatter_kernel<<<grid, 256, 0, st>>>(cid, n, cell_start, counts, slot_idx);
+      bucket_order_kernel<D><<<ogrid, 256, 0, st>>>(fit, cell_start, (int)ncells, slot_idx, fit_sorted, any_big);
+      bucket_order_big_kernel<D><<<bgrid, 256, 0, st>>>(fit, n, cid, cell_start, slot_idx, fit_sorted, any_big);
     }
-  }
+  });
   CLX_CHECK_LAUNCH("clx_ms_bucket");
   return CLX_OK;
 }

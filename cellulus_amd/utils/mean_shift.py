@@ -11,6 +11,8 @@ sub-sampling mask (same global RNG call, so seeding numpy reproduces it) and
 sklearn's sort + greedy de-duplication of converged centres.
 """
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -24,8 +26,6 @@ def _bucket(fit, bandwidth):
     """Bucket the fit points into uniform-grid cells of edge just above the bandwidth
     (clx_ms_bucket: counting sort by cell, original order inside a cell).  Returns (sorted points,
     cell_start int32 (ncells+1), origin (host), cell edge, (nx, ny, nz))."""
-    import ctypes
-
     n, nd = fit.shape
     cell = float(bandwidth) * (1.0 + 1e-9)        # strictly larger than the query radius
     ext_d = torch.empty(_clx.ROWS_EXTENT_DOUBLES, dtype=torch.float64, device=fit.device)
@@ -66,8 +66,6 @@ def dedup_centers(centers, counts, bandwidth):
     """sklearn MeanShift.fit post-processing (_mean_shift.py: center_intensity_dict, sort by (count, centre) descending,
     greedy removal of centres within `bandwidth`) — libclx's host function clx_ms_dedup_centers (two sorts + the greedy
     pass over a hash grid); `_dedup_centers_numpy` below is the same in numpy, kept as the tests' second opinion."""
-    import ctypes
-
     centers = np.ascontiguousarray(centers, dtype=np.float64)
     counts = np.ascontiguousarray(counts, dtype=np.int32)
     n, nd = centers.shape
@@ -179,8 +177,6 @@ def mean_shift_on_device(emb, std, bandwidth, reduction_probability, threshold, 
     counts = res[ns * nd * 8: ns * nd * 8 + ns * 4].view(torch.int32)
     iters = res[ns * nd * 8 + ns * 4:].view(torch.int32)
     if fit.shape[0] >= GRID_MIN_POINTS:
-        import ctypes
-
         fit_sorted, cell_start, origin, cell, (nx, ny, nz) = _bucket(fit, bandwidth)
         if seeds is None:
             seeds_d = fit_sorted          # neighbouring wavefronts then walk neighbouring cells
@@ -195,8 +191,6 @@ def mean_shift_on_device(emb, std, bandwidth, reduction_probability, threshold, 
     cluster_centers = dedup_centers(res_h[:ns * nd * 8].view(np.float64).reshape(ns, nd),
                                     res_h[ns * nd * 8: ns * nd * 8 + ns * 4].view(np.int32), float(bandwidth))
     ncc = cluster_centers.shape[0]
-    import ctypes
-
     # nearest centre of every foreground pixel: the centres in a uniform grid (any edge gives the exact nearest centre —
     # the search widens its block until the winner is closer than the block's reach; the bandwidth is the edge at which
     # a pixel's own 3^ND block decides; doubled while stray centres would make the grid larger than 2^26 cells)

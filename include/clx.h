@@ -56,8 +56,8 @@ enum clx_profile_kind {
   CLX_PROF_SPLIT_PLANES = 5, /* sp_split_kernel (HBM-bound: no FLOPs) */
   CLX_PROF_CHAIN64 = 6,      /* chain64_fwd / _bwd kernels (fused pairs of 64-channel 1x1 layers) */
   /* the HBM-bound kernels of detect / segment (no FLOPs: total_flops of these kinds is 0; the caller prices them by bytes) */
-  CLX_PROF_MS_PREPARE = 7,   /* ms_prepare_kernel */
-  CLX_PROF_MS_ASSIGN = 8,    /* ms_assign_cells / _grid / ms_assign kernels */
+  CLX_PROF_MS_PREPARE = 7,   /* ms_flags_kernel + ms_scatter_kernel (the two launches of clx_ms_prepare / _f32) */
+  CLX_PROF_MS_ASSIGN = 8,    /* ms_assign_dense / ms_assign_cells2d / ms_assign_grid / ms_assign kernels */
   CLX_PROF_CC = 9,           /* every kernel of clx_label_filter (connected components + size filter + relabel) */
   CLX_PROF_GROW_SHRINK = 10, /* every kernel of clx_grow_shrink */
   CLX_PROF_MINMAX = 11,      /* minmax_init + minmax_kernel */
