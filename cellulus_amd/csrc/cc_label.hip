@@ -10,11 +10,22 @@
 // final root of a component is its smallest raster index.  Stale reads of the
 // parent array are harmless (parents only decrease along a chain; progress is
 // made by the values returned from the atomics).
-#include <stdlib.h>
+//
+// Two pipelines, chosen in clx_cc_label_filter by what the input shows:
+//   run pipeline         3-D volumes, and the 2-D images the label-list layout cannot serve (`out` not 16-byte
+//                        aligned; images a pixel or two wide and thousands of rows tall, whose row masks outgrow the
+//                        workspace).  Union-find over the horizontal runs of every pixel, then five passes over pixels.
+//   label-list pipeline  every other 2-D image.  `out` is the parent array, and the passes after the strip pass work on
+//                        the few thousand strip-local labels instead of on pixels.
 #include "clx_common.h"
 #include "union_find.h"                 // uf_find, uf_find_halve, uf_union
 
 namespace {
+
+// ---------------------------------------------------------------------------------------------
+// Run pipeline: cc_init_runs, cc_merge_runs, cc_flatten_count, cc_count_roots, cc_scan_counts,
+// cc_number_roots, cc_write.  Workspace: [L | size | block counts].
+// ---------------------------------------------------------------------------------------------
 
 // Wave w of the grid owns 64 consecutive pixels of one row ("segment").  Returns the pixel index
 // of lane 0, the row's first pixel index and x of this lane; valid = inside the row.
@@ -92,112 +103,6 @@ __global__ __launch_bounds__(256) void cc_merge_runs(const int* __restrict__ seg
       if (b && !(left && a)) uf_union(L, (int)p.i, (int)r);
       if (a && !b && !left) uf_union(L, (int)p.i, (int)r - 1);
       if (c && !b && !right) uf_union(L, (int)p.i, (int)r + 1);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 2-D fast path for passes 1 + 2: a wavefront walks a strip of STRIP_ROWS rows of its 64-pixel
-// column segment TOP-DOWN, carrying the previous row's values and labels in registers.  A run takes
-// the smallest label of the runs it touches in the row above (segmented min inside the wave), a run
-// that touches nothing starts a new label (its first pixel), and a global union is needed only when
-// a run touches two different labels — so inside a strip an object costs no atomic at all instead
-// of one per row.  What the strips do not see — the row above a strip, the column left of a
-// segment — is linked afterwards by cc_link_borders (1/32 + 1/64 of the pixels).
-// ---------------------------------------------------------------------------------------------
-constexpr int STRIP_ROWS = 32;
-
-__global__ __launch_bounds__(256) void cc_strip_kernel(const int* __restrict__ seg, int* L, int* __restrict__ size,
-                                                       int Y, int X, int nseg, int nstrips) {
-  const int lane = threadIdx.x & 63;
-  const long long nwaves = (long long)nstrips * nseg;
-  for (long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwaves;
-       w += ((long long)gridDim.x * blockDim.x) >> 6) {
-    const int strip = (int)(w / nseg), sg = (int)(w - (long long)strip * nseg);
-    const int x = sg * 64 + lane;
-    const bool in_x = x < X;
-    const int y0 = strip * STRIP_ROWS, y1 = min(y0 + STRIP_ROWS, Y);
-    int pv = 0, pl = -1;
-    for (int y = y0; y < y1; ++y) {
-      const long long i = (long long)y * X + x;
-      const int v = in_x ? seg[i] : 0;
-      unsigned long long starts;
-      const int sl = run_start_lane(v, lane, &starts);
-      // labels of the (up to three) touching pixels of the row above.  If the pixel straight above
-      // matches, its two neighbours belong to the same run; otherwise up-left and up-right are two
-      // DIFFERENT runs (the pixel between them differs), and both labels count.
-      int c[3];
-#pragma unroll
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int src = min(max(lane + dx, 0), 63);
-        const int nv = __shfl(pv, src, 64), nl = __shfl(pl, src, 64);
-        c[dx + 1] = (v != 0 && nv == v && (lane + dx) == src) ? nl : 0x7fffffff;
-      }
-      if (c[1] != 0x7fffffff) c[0] = c[2] = 0x7fffffff;
-      int cand = min(c[0], min(c[1], c[2]));
-      // segmented inclusive min-scan towards higher lanes, then everyone takes the run's last lane
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(cand, d, 64);
-        if (lane - d >= sl) cand = min(cand, t);
-      }
-      const unsigned long long above = (lane == 63) ? 0ull : (starts >> (lane + 1));
-      const int el = above ? lane + __builtin_ctzll(above) : 63;
-      const int runmin = __shfl(cand, el, 64);
-      int label = -1;
-      if (v != 0) {
-        label = (runmin == 0x7fffffff) ? (int)(i - lane + sl) : runmin;
-        if (runmin == 0x7fffffff && sl == lane) size[i] = 0;       // a new root
-        L[i] = label;
-      } else if (in_x) {
-        L[i] = -1;
-      }
-      // every other label the run touches is joined to the one it took (the L entries involved were
-      // written by this wavefront in earlier rows: fence; the links themselves are atomics)
-      const bool j0 = c[0] != 0x7fffffff && c[0] != label, j1 = c[1] != 0x7fffffff && c[1] != label,
-                 j2 = c[2] != 0x7fffffff && c[2] != label;
-      if (j0 || j1 || j2) {
-        __threadfence();
-        if (j0) uf_union(L, c[0], label);
-        if (j1) uf_union(L, c[1], label);
-        if (j2) uf_union(L, c[2], label);
-      }
-      pv = v;
-      pl = label;
-    }
-  }
-}
-
-// links across the borders the strips ignore: for the first row of every strip the three pixels above,
-// for the first column of every segment the three pixels to the left
-__global__ void cc_link_borders(const int* __restrict__ seg, int* L, int Y, int X, int nseg, int nstrips) {
-  const long long n_rows = (long long)(nstrips - 1) * X;          // pixels of the strips' first rows (not strip 0)
-  const long long n_cols = (long long)(nseg - 1) * Y;             // pixels of the segments' first columns
-  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n_rows + n_cols;
-       k += (long long)gridDim.x * blockDim.x) {
-    if (k < n_rows) {
-      const int y = (int)(k / X + 1) * STRIP_ROWS, x = (int)(k % X);
-      const long long i = (long long)y * X + x;
-      const int v = seg[i];
-      if (v == 0) continue;
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int xx = x + dx;
-        if (xx < 0 || xx >= X) continue;
-        const long long j = i - X + dx;
-        if (seg[j] == v) uf_union(L, (int)i, (int)j);
-      }
-    } else {
-      const long long kk = k - n_rows;
-      const int x = (int)(kk / Y + 1) * 64, y = (int)(kk % Y);
-      const long long i = (long long)y * X + x;
-      const int v = seg[i];
-      if (v == 0) continue;
-      for (int dy = -1; dy <= 1; ++dy) {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= Y) continue;
-        const long long j = (long long)yy * X + x - 1;
-        if (seg[j] == v) uf_union(L, (int)i, (int)j);
-      }
     }
   }
 }
@@ -355,10 +260,15 @@ __global__ void cc_write(const int* __restrict__ seg, const int* __restrict__ L,
 }
 
 // ---------------------------------------------------------------------------------------------
-// 2-D path, round 3: four byte-moving passes instead of nine.  The union-find parent array IS the
-// output image (entries = parent index + 1, background 0 — so background pixels are written once
+// Label-list pipeline (2-D): four byte-moving passes where the run pipeline has nine.  The union-find parent
+// array IS the output image (entries = parent index + 1, background 0 — so background pixels are written once
 // and never touched again), and everything between the strip pass and the final rewrite works on
-// the (few thousand) strip-local LABELS instead of on pixels:
+// the (few thousand) strip-local LABELS instead of on pixels.
+// A wavefront walks a strip of STRIP_ROWS rows of its 64-pixel column segment TOP-DOWN, carrying the previous row's
+// values and labels in registers.  A run takes the smallest label of the runs it touches in the row above, a run that
+// touches nothing starts a new label (its first pixel), and a global union is needed only when a run touches two
+// different labels — so inside a strip an object costs no atomic at all instead of one per row.  What the strips do not
+// see — the row above a strip, the column left of a segment — is linked afterwards (1/32 + 1/64 of the pixels).
 //   1. cc_strip1   seg -> out (label + 1 | 0); every run adds its length to its provisional label's
 //                  size; per (row, segment) one 64-bit mask of the labels the row creates and one of its
 //                  foreground pixels; rows without foreground take a wave-uniform branch around the lane work
@@ -369,12 +279,13 @@ __global__ void cc_write(const int* __restrict__ seg, const int* __restrict__ L,
 //   6. cc_scan_counts over the (<= 8192) chunks
 //   7. cc_rank     per label: id of its root = chunk prefix + word prefix + popcount inside the word + 1, 0 if
 //                  removed; stored in size[label]
-//   8. cc_rewrite_masked  out[i] = out[i] ? size[out[i] - 1] : 0, in place, 16 bytes per lane; groups without
-//                  foreground (by the masks of pass 1) are neither read nor written
+//   8. cc_rewrite_masked (X % 4 == 0; cc_rewrite otherwise)  out[i] = out[i] ? size[out[i] - 1] : 0, in place, 16 bytes
+//                  per lane; groups without foreground (by the masks of pass 1) are neither read nor written
 // Bytes per pixel: 4 read + 4 written (1), 4 read + 4 written at foreground groups only (8); passes 2-7
-// touch borders and labels (a few microseconds each).  Round 2 read or wrote every pixel nine times
-// (36 B per pixel).
-// Round 4, measured at 4096^2 (PMC: profiles/r04_cc_pmc.txt): pass 1 is bound by instruction ISSUE, not by bytes — its
+// touch borders and labels (a few microseconds each).
+// Workspace: [size | label masks | foreground masks | survivor bitmap | survivors before each bitmap word |
+// chunk counts | edge columns left, right].
+// Measured at 4096^2 (PMC: profiles/r04_cc_pmc.txt): pass 1 is bound by instruction ISSUE, not by bytes — its
 // access pattern alone (load a row, store it) runs in 23 us, the pass in 48: 71 vector + 45 scalar instructions per
 // row of 64 pixels, one instruction per wavefront per four cycles, 256 rows per SIMD.  A tile form of the pass (all
 // rows of a 16- or 32-row tile loaded at once, runs linked through a union-find in LDS, one size store per root
@@ -383,40 +294,7 @@ __global__ void cc_write(const int* __restrict__ seg, const int* __restrict__ L,
 // 26-pixel-wide object crossing a border cost 78 unions for one useful link), word prefixes for the ranks
 // (cc_rank 17 -> 5 + 4.6 us), 16-byte accesses in the scan (8 -> 4.4 us).
 // ---------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ int uf1_find(const int* L, int a) {
-  int p = L[a] - 1;
-  while (p != a) { a = p; p = L[a] - 1; }
-  return a;
-}
-__device__ __forceinline__ int uf1_find_halve(int* L, int a) {
-  int p = L[a] - 1;
-  while (p != a) {
-    const int gp = L[p] - 1;
-    if (gp != p) L[a] = gp + 1;
-    a = p;
-    p = gp;
-  }
-  return a;
-}
-__device__ __forceinline__ void uf1_union(int* L, int a, int b) {
-  bool done;
-  do {
-    a = uf1_find_halve(L, a);
-    b = uf1_find_halve(L, b);
-    if (a < b) {
-      const int old = atomicMin(&L[b], a + 1) - 1;
-      done = (old == b);
-      b = old;
-    } else if (b < a) {
-      const int old = atomicMin(&L[a], b + 1) - 1;
-      done = (old == a);
-      a = old;
-    } else {
-      done = true;
-    }
-  } while (!done);
-}
+constexpr int STRIP_ROWS = 32;
 
 // whole-wave shifts by one lane as DPP moves (no LDS crossbar trip): lane i takes lane i -/+ 1, the end lane `fill`
 __device__ __forceinline__ int wave_shr1(int x, int fill) { return __builtin_amdgcn_update_dpp(fill, x, 0x138, 0xf, 0xf, false); }
@@ -519,9 +397,9 @@ __global__ __launch_bounds__(256) void cc_strip1(const int* __restrict__ seg, in
         const bool j0 = c0 != INF && c0 != label, j1 = c1 != INF && c1 != label, j2 = c2 != INF && c2 != label;
         if (j0 || j1 || j2) {
           __threadfence();
-          if (j0) uf1_union(L, c0, label);
-          if (j1) uf1_union(L, c1, label);
-          if (j2) uf1_union(L, c2, label);
+          if (j0) uf_union<1>(L, c0, label);
+          if (j1) uf_union<1>(L, c1, label);
+          if (j2) uf_union<1>(L, c2, label);
         }
         pv = v;
         pl = label;
@@ -555,9 +433,9 @@ __global__ void cc_link1(const int* __restrict__ seg, int* L, const int* __restr
       //  that pass has joined this pixel to it)
       const bool left = (x & 63) != 0 && seg[i - 1] == v, right = ((x + 1) & 63) != 0 && x + 1 < X && seg[i + 1] == v;
       const bool a = x > 0 && seg[j - 1] == v, b = seg[j] == v, c = x + 1 < X && seg[j + 1] == v;
-      if (b && !(left && a)) uf1_union(L, (int)i, (int)j);
-      if (a && !b && !left) uf1_union(L, (int)i, (int)(j - 1));
-      if (c && !b && !right) uf1_union(L, (int)i, (int)(j + 1));
+      if (b && !(left && a)) uf_union<1>(L, (int)i, (int)j);
+      if (a && !b && !left) uf_union<1>(L, (int)i, (int)(j - 1));
+      if (c && !b && !right) uf_union<1>(L, (int)i, (int)(j + 1));
     } else {
       const long long kk = k - n_rows;
       const int sb = (int)(kk / Y + 1), x = sb * 64, y = (int)(kk % Y);
@@ -571,9 +449,9 @@ __global__ void cc_link1(const int* __restrict__ seg, int* L, const int* __restr
       const bool a = y > 0 && (other ? other[y - 1] : seg[i - X - 1]) == v;
       const bool b = (other ? other[y] : seg[i - 1]) == v;
       const bool c = y + 1 < Y && (other ? other[y + 1] : seg[i + X - 1]) == v;
-      if (b && !(up && a)) uf1_union(L, (int)i, (int)(i - 1));
-      if (a && !b && !up) uf1_union(L, (int)i, (int)(i - X - 1));
-      if (c && !b && !down) uf1_union(L, (int)i, (int)(i + X - 1));
+      if (b && !(up && a)) uf_union<1>(L, (int)i, (int)(i - 1));
+      if (a && !b && !up) uf_union<1>(L, (int)i, (int)(i - X - 1));
+      if (c && !b && !down) uf_union<1>(L, (int)i, (int)(i + X - 1));
     }
   }
 }
@@ -593,7 +471,7 @@ constexpr int MAX_RANK_CHUNKS = 8192;
 __global__ void cc_fold(int* L, int* size, const unsigned long long* __restrict__ labelmask, long long nwords,
                         int nseg, int X) {
   CC_FOR_EACH_LABEL(l) {
-    const int r = uf1_find(L, l);
+    const int r = uf_find<1>(L, l);
     if (r != l) {
       atomicAdd(&size[r], size[l]);     // size[l] is final (written by the strip pass only)
       L[l] = r + 1;                     // any ancestor is a valid parent; the root is the best one
@@ -720,8 +598,8 @@ inline int grid_for(long long total, int block) {
 }  // namespace
 
 extern "C" size_t clx_cc_workspace(long long npix) {
-  // the larger of the two layouts: [L | size | block counts] (3-D) and
-  // [size | label masks (one 64-bit word per row and 64-pixel segment, <= npix / 32 + 2 Y ints) | bitmap | chunk counts] (2-D)
+  // the larger of the two layouts: [L | size | block counts] (run pipeline) and
+  // [size | label masks (one 64-bit word per row and 64-pixel segment, <= npix / 32 + 2 Y ints) | bitmap | chunk counts] (label-list pipeline)
   const long long nblocks = (npix + SCAN_BLOCK - 1) / SCAN_BLOCK;
   return (size_t)(3 * npix + npix / 16 + MAX_RANK_CHUNKS + nblocks + 128) * sizeof(int);
 }
@@ -733,21 +611,10 @@ extern "C" int clx_cc_label_filter(const int* seg, int* out, int Z, int Y, int X
   const long long npix = (long long)Z * Y * X;
   CLX_REQUIRE(npix < (1ll << 31), "clx_cc_label_filter: too many pixels");
   CLX_REQUIRE(seg != out, "clx_cc_label_filter: in-place operation is not supported");
-  int* L = (int*)workspace;
-  int* size = L + npix;
-  int* counts = size + npix;
-  const int nblocks = (int)((npix + SCAN_BLOCK - 1) / SCAN_BLOCK);
-  const int grid = grid_for(npix, 256);
   hipStream_t st = (hipStream_t)stream;
   if (min_size < 1) min_size = 1;   // every component has >= 1 pixel: keep all
   const int nseg = (X + 63) / 64;
-  const long long nwaves = (long long)Z * Y * nseg;
-  const int wgrid = grid_for(nwaves * 64, 256);
-  static const bool strips = getenv("CLX_CC_STRIPS") == nullptr || atoi(getenv("CLX_CC_STRIPS")) != 0;
-  static const bool labels = getenv("CLX_CC_LABELS") == nullptr || atoi(getenv("CLX_CC_LABELS")) != 0;
-  // label-list path (2-D): `out` is the parent array.  Workspace: [size | label masks | foreground masks |
-  // survivor bitmap | survivors before each bitmap word | chunk counts | edge columns left, right]
-  static const bool masked = getenv("CLX_CC_MASKED_REWRITE") == nullptr || atoi(getenv("CLX_CC_MASKED_REWRITE")) != 0;
+  // the label-list layout (see the pipeline's banner)
   const long long nwords = (npix + 31) / 32;
   // rank chunks: >= 2048 pixels, a multiple of 32, at most MAX_RANK_CHUNKS of them
   long long rank_chunk = (npix + MAX_RANK_CHUNKS - 1) / MAX_RANK_CHUNKS;
@@ -764,11 +631,11 @@ extern "C" int clx_cc_label_filter(const int* seg, int* out, int Z, int Y, int X
   int* colL = chunk + nchunks;                       // edge columns of the 64-pixel segments, [segment][y]
   int* colR = colL + (long long)nseg * Y;
   // (images a few pixels wide and very tall: the edge columns do not fit the workspace — the border pass then reads
-  //  the image; if the masks do not fit either — one 64-bit word per row for a handful of pixels — the pixel-list path below)
+  //  the image; if the masks do not fit either — one 64-bit word per row for a handful of pixels — the run pipeline below)
   if ((size_t)((unsigned char*)(colR + (long long)nseg * Y) - (unsigned char*)workspace) > clx_cc_workspace(npix))
     colL = colR = nullptr;
   const bool fits = (size_t)((unsigned char*)(chunk + nchunks) - (unsigned char*)workspace) <= clx_cc_workspace(npix);
-  if (Z == 1 && strips && labels && fits && ((uintptr_t)out & 15) == 0) {
+  if (Z == 1 && fits && ((uintptr_t)out & 15) == 0) {          // (16-byte groups of `out` in the rewrite)
     const int nstrips = (Y + STRIP_ROWS - 1) / STRIP_ROWS;
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_strip1, dim3(grid_for((long long)nstrips * nseg * 64, 256)), dim3(256), 0, st, seg, out, sz, labelmask, fgmask, colL, colR, Y, X, nseg, nstrips);
     const long long nb = (long long)(nstrips - 1) * X + (long long)(nseg - 1) * Y;
@@ -779,27 +646,28 @@ extern "C" int clx_cc_label_filter(const int* seg, int* out, int Z, int Y, int X
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_word_prefix, dim3(grid_for((long long)nchunks * 64, 256)), dim3(256), 0, st, bitmap, nwords, (int)(rank_chunk / 32), nchunks, wprefix, chunk);
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_scan_counts, dim3(1), dim3(1024), 0, st, chunk, nchunks, ncomp_out);
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_rank, dim3(lgrid), dim3(256), 0, st, out, sz, labelmask, nmask, nseg, X, bitmap, chunk, wprefix, (int)rank_chunk);
-    if (masked && X % 4 == 0)
+    if (X % 4 == 0) {
       CLX_LAUNCH_KIND(CLX_PROF_CC, cc_rewrite_masked, dim3((X / 4 + 255) / 256, (Y + 7) / 8 < 32768 ? (Y + 7) / 8 : 32768), dim3(256), 0, st, out, sz, fgmask, Y, X, nseg);
-    else
+    } else {
       CLX_LAUNCH_KIND(CLX_PROF_CC, cc_rewrite, dim3(grid_for(npix / 4 + 1, 256)), dim3(256), 0, st, out, sz, npix);
+    }
     CLX_CHECK_LAUNCH("clx_cc_label_filter");
     return CLX_OK;
   }
-  if (Z == 1 && strips) {
-    const int nstrips = (Y + STRIP_ROWS - 1) / STRIP_ROWS;
-    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_strip_kernel, dim3(grid_for((long long)nstrips * nseg * 64, 256)), dim3(256), 0, st, seg, L, size, Y, X, nseg, nstrips);
-    const long long nb = (long long)(nstrips - 1) * X + (long long)(nseg - 1) * Y;
-    if (nb > 0) CLX_LAUNCH_KIND(CLX_PROF_CC, cc_link_borders, dim3(grid_for(nb, 256)), dim3(256), 0, st, seg, L, Y, X, nseg, nstrips);
-  } else {
-    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_init_runs, dim3(wgrid), dim3(256), 0, st, seg, L, size, X, nseg, nwaves);
-    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_merge_runs, dim3(wgrid), dim3(256), 0, st, seg, L, Z, Y, X, nseg, nwaves);
-  }
+  // the run pipeline
+  int* L = (int*)workspace;
+  int* size = L + npix;
+  int* counts = size + npix;
+  const int nblocks = (int)((npix + SCAN_BLOCK - 1) / SCAN_BLOCK);
+  const long long nwaves = (long long)Z * Y * nseg;
+  const int wgrid = grid_for(nwaves * 64, 256);
+  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_init_runs, dim3(wgrid), dim3(256), 0, st, seg, L, size, X, nseg, nwaves);
+  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_merge_runs, dim3(wgrid), dim3(256), 0, st, seg, L, Z, Y, X, nseg, nwaves);
   CLX_LAUNCH_KIND(CLX_PROF_CC, cc_flatten_count, dim3(wgrid), dim3(256), 0, st, seg, L, size, X, nseg, nwaves);
   CLX_LAUNCH_KIND(CLX_PROF_CC, cc_count_roots, dim3(nblocks), dim3(256), 0, st, seg, L, size, min_size, npix, counts);
   CLX_LAUNCH_KIND(CLX_PROF_CC, cc_scan_counts, dim3(1), dim3(1024), 0, st, counts, nblocks, ncomp_out);
   CLX_LAUNCH_KIND(CLX_PROF_CC, cc_number_roots, dim3(nblocks), dim3(256), 0, st, seg, L, size, min_size, npix, counts);
-  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_write, dim3(grid), dim3(256), 0, st, seg, L, size, out, npix);
+  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_write, dim3(grid_for(npix, 256)), dim3(256), 0, st, seg, L, size, out, npix);
   CLX_CHECK_LAUNCH("clx_cc_label_filter");
   return CLX_OK;
 }

@@ -5,21 +5,27 @@
 // counts are bit-exact.  Compiled with the default contraction but the index
 // expression has no multiply-add pair to fuse.
 #include "clx_common.h"
-#include <stdlib.h>
 
 namespace {
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  static const int cap = getenv("CLX_OTSU_GRID") ? atoi(getenv("CLX_OTSU_GRID")) : 1024;     // (sweeps)
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
+// blocks of 256 threads over `work` items, 1 .. cap of them
+inline int blocks_of(long long work, int cap) {
+  const long long g = (work + 255) / 256;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
 }
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-constexpr int MM_BLOCKS = 512;      // == (CLX_MINMAX_DOUBLES - 2) / 2
+// What a lane loads at once: 16 bytes, N elements (8-byte accesses run at 0.54-0.70x the 16-byte rate).  float32 is the
+// network's std channel handed over in device memory (cellulus_amd/infer.py::fused_stages): the float64 values the staged
+// path reads back from zarr are these floats widened, so min / max / bin of the widened value are the staged path's bits.
+template <typename T> struct Vec16;
+template <> struct Vec16<double> { typedef f64x2 type; static constexpr int N = 2; };
+template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
+
+constexpr int MM_BLOCKS = 512;      // grid cap of the min/max kernel: one pair of partials per block
+static_assert(CLX_MINMAX_DOUBLES == 2 + 2 * MM_BLOCKS, "the caller's buffer holds the two results and every block's partials");
+constexpr int HIST_BLOCKS = 1024;   // grid cap of the histogram kernel
 
 // Block partials, then one small block over them: no two blocks meet on an address.  (Until round 4 every block ended
 // with two float64 atomics on the SAME two words: they are served one after the other at the memory side, ~12 ns each —
@@ -59,66 +65,39 @@ __global__ __launch_bounds__(256) void minmax_final(double* mm, int nblocks) {
   }
 }
 
-// float32 input (the network's std channel handed over in device memory, cellulus_amd/infer.py::fused_stages): the
-// float64 values the staged path reads back from zarr are these floats widened, so min / max / bin of the widened
-// value are the staged path's bits.  16 bytes = four floats per lane.
-// A block reads ONE contiguous range, eight 4-KB pieces of it in flight per round.
-__global__ __launch_bounds__(256) void minmax_f32_kernel(const float* __restrict__ x, long long n, double* mm) {
-  float lo = __int_as_float(0x7f800000), hi = -lo;
-  const long long n4 = n >> 2;
-  const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-  const long long per_block = (n4 + gridDim.x - 1) / gridDim.x;
-  const long long b0 = (long long)blockIdx.x * per_block, b1 = b0 + per_block < n4 ? b0 + per_block : n4;
-  long long i = b0 + threadIdx.x;
-  for (; i + 7 * 256 < b1; i += 8 * 256) {
-    f32x4 v[8];
+// min / max of one 16-byte piece folded into the running pair, in the element type (for floats fmin / fmax are the
+// float overloads, i.e. fminf / fmaxf: v_min3_f32 / v_max3_f32, no conversion)
+template <typename T, typename V>
+__device__ __forceinline__ void minmax_piece(const V v, T& lo, T& hi) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = x4[i + 256 * u];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { lo = fminf(lo, v[u][e]); hi = fmaxf(hi, v[u][e]); }
-  }
-  for (; i < b1; i += 256) {
-    const f32x4 a = x4[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { lo = fminf(lo, a[e]); hi = fmaxf(hi, a[e]); }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) {
-    lo = fminf(lo, x[(n4 << 2) + threadIdx.x]);
-    hi = fmaxf(hi, x[(n4 << 2) + threadIdx.x]);
-  }
-  minmax_block_out(lo, hi, mm);
+  for (int e = 0; e < Vec16<T>::N; ++e) { lo = fmin(lo, v[e]); hi = fmax(hi, v[e]); }
 }
 
-// 16-byte loads (two doubles per lane): 8-byte accesses run at 0.54-0.70x the 16-byte rate
-__global__ __launch_bounds__(256) void minmax_kernel(const double* __restrict__ x, long long n, double* mm) {
-  double lo = __longlong_as_double(0x7ff0000000000000ll), hi = -lo;
-  const long long n2 = n >> 1;
-  const f64x2* x2 = reinterpret_cast<const f64x2*>(x);
-  // a block reads ONE contiguous range (eight 4-KB pieces of it in flight per round): with the grid-strided walk the
-  // loads of a thread were 8 MB apart and a 4096^2 image ran at 2.3 TB/s
-  const long long per_block = (n2 + gridDim.x - 1) / gridDim.x;
-  const long long b0 = (long long)blockIdx.x * per_block, b1 = b0 + per_block < n2 ? b0 + per_block : n2;
+// A block reads ONE contiguous range, eight 4-KB pieces of it in flight per round: with the grid-strided walk the
+// loads of a thread were 8 MB apart and a 4096^2 image ran at 2.3 TB/s.  The last n % N elements go to block 0's
+// first threads.  The reduction runs in T and widens only in minmax_block_out.
+template <typename T>
+__global__ __launch_bounds__(256) void minmax_kernel(const T* __restrict__ x, long long n, double* mm) {
+  typedef typename Vec16<T>::type V;
+  constexpr int N = Vec16<T>::N;
+  T lo = (T)__builtin_huge_valf(), hi = -lo;
+  const long long nv = n / N;
+  const V* xv = reinterpret_cast<const V*>(x);
+  const long long per_block = (nv + gridDim.x - 1) / gridDim.x;
+  const long long b0 = (long long)blockIdx.x * per_block, b1 = b0 + per_block < nv ? b0 + per_block : nv;
   long long i = b0 + threadIdx.x;
   for (; i + 7 * 256 < b1; i += 8 * 256) {
-    f64x2 v[8];
+    V v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = x2[i + 256 * u];
+    for (int u = 0; u < 8; ++u) v[u] = xv[i + 256 * u];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      lo = fmin(lo, fmin(v[u][0], v[u][1]));
-      hi = fmax(hi, fmax(v[u][0], v[u][1]));
-    }
+    for (int u = 0; u < 8; ++u) minmax_piece(v[u], lo, hi);
   }
-  for (; i < b1; i += 256) {
-    const f64x2 a = x2[i];
-    lo = fmin(lo, fmin(a[0], a[1]));
-    hi = fmax(hi, fmax(a[0], a[1]));
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    lo = fmin(lo, x[n - 1]);
-    hi = fmax(hi, x[n - 1]);
+  for (; i < b1; i += 256) minmax_piece(xv[i], lo, hi);
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n % N)) {
+    const T t = x[nv * N + threadIdx.x];
+    lo = fmin(lo, t);
+    hi = fmax(hi, t);
   }
   minmax_block_out(lo, hi, mm);
 }
@@ -149,10 +128,14 @@ __device__ __forceinline__ void hist_one(double v, double first, double last, do
 }
 
 // per-WAVE private histograms in LDS (4 copies) cut the LDS-atomic contention; the bin
-// edges are staged in LDS too (the +-1 corrections read them for every element)
-__global__ __launch_bounds__(256) void histogram_kernel(const double* __restrict__ x, long long n,
+// edges are staged in LDS too (the +-1 corrections read them for every element).  Every element is widened to double
+// in registers before it is binned.
+template <typename T>
+__global__ __launch_bounds__(256) void histogram_kernel(const T* __restrict__ x, long long n,
                                                         const double* __restrict__ edges, int nbins,
                                                         unsigned long long* __restrict__ counts) {
+  typedef typename Vec16<T>::type V;
+  constexpr int N = Vec16<T>::N;
   extern __shared__ unsigned char hist_smem[];
   double* eds = reinterpret_cast<double*>(hist_smem);                       // [nbins + 1]
   unsigned int* local = reinterpret_cast<unsigned int*>(eds + nbins + 1);   // [4][nbins]
@@ -162,75 +145,31 @@ __global__ __launch_bounds__(256) void histogram_kernel(const double* __restrict
   unsigned int* mine = local + (threadIdx.x >> 6) * nbins;
   const double first = eds[0], last = eds[nbins];
   const double denom = (double)nbins / (last - first);      // (see hist_one)
-  const long long n2 = n >> 1;
-  const f64x2* x2 = reinterpret_cast<const f64x2*>(x);
+  const long long nv = n / N;
+  const V* xv = reinterpret_cast<const V*>(x);
   int cur = 0;
   unsigned int run = 0u;
   // a block takes ONE contiguous range, four 4-KB pieces of it in flight per round (consecutive values of a thread are
   // then 4 KB apart instead of the whole grid's stride: same plateau, same bin, one LDS atomic per run)
-  const long long per_block = (n2 + gridDim.x - 1) / gridDim.x;
-  const long long b0 = (long long)blockIdx.x * per_block, b1 = b0 + per_block < n2 ? b0 + per_block : n2;
+  const long long per_block = (nv + gridDim.x - 1) / gridDim.x;
+  const long long b0 = (long long)blockIdx.x * per_block, b1 = b0 + per_block < nv ? b0 + per_block : nv;
   long long i = b0 + threadIdx.x;
   for (; i + 3 * 256 < b1; i += 4 * 256) {
-    f64x2 v[4];
+    V v[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = x2[i + 256 * u];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      hist_one(v[u][0], first, last, denom, nbins, eds, mine, cur, run);
-      hist_one(v[u][1], first, last, denom, nbins, eds, mine, cur, run);
-    }
-  }
-  for (; i < b1; i += 256) {
-    const f64x2 v = x2[i];
-    hist_one(v[0], first, last, denom, nbins, eds, mine, cur, run);
-    hist_one(v[1], first, last, denom, nbins, eds, mine, cur, run);
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) hist_one(x[n - 1], first, last, denom, nbins, eds, mine, cur, run);
-  if (run) atomicAdd(&mine[cur], run);
-  __syncthreads();
-  for (int k = threadIdx.x; k < nbins; k += blockDim.x) {
-    const unsigned int c = local[k] + local[nbins + k] + local[2 * nbins + k] + local[3 * nbins + k];
-    if (c) atomicAdd(&counts[k], (unsigned long long)c);
-  }
-}
-
-// the same histogram of float32 values widened in registers (four per 16-byte load)
-__global__ __launch_bounds__(256) void histogram_f32_kernel(const float* __restrict__ x, long long n,
-                                                            const double* __restrict__ edges, int nbins,
-                                                            unsigned long long* __restrict__ counts) {
-  extern __shared__ unsigned char hist_smem[];
-  double* eds = reinterpret_cast<double*>(hist_smem);                       // [nbins + 1]
-  unsigned int* local = reinterpret_cast<unsigned int*>(eds + nbins + 1);   // [4][nbins]
-  for (int k = threadIdx.x; k <= nbins; k += blockDim.x) eds[k] = edges[k];
-  for (int k = threadIdx.x; k < 4 * nbins; k += blockDim.x) local[k] = 0u;
-  __syncthreads();
-  unsigned int* mine = local + (threadIdx.x >> 6) * nbins;
-  const double first = eds[0], last = eds[nbins];
-  const double denom = (double)nbins / (last - first);      // (see hist_one)
-  const long long n4 = n >> 2;
-  const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-  int cur = 0;
-  unsigned int run = 0u;
-  const long long per_block = (n4 + gridDim.x - 1) / gridDim.x;
-  const long long b0 = (long long)blockIdx.x * per_block, b1 = b0 + per_block < n4 ? b0 + per_block : n4;
-  long long i = b0 + threadIdx.x;
-  for (; i + 3 * 256 < b1; i += 4 * 256) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = x4[i + 256 * u];
+    for (int u = 0; u < 4; ++u) v[u] = xv[i + 256 * u];
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hist_one((double)v[u][e], first, last, denom, nbins, eds, mine, cur, run);
+      for (int e = 0; e < N; ++e) hist_one((double)v[u][e], first, last, denom, nbins, eds, mine, cur, run);
   }
   for (; i < b1; i += 256) {
-    const f32x4 v = x4[i];
+    const V v = xv[i];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) hist_one((double)v[e], first, last, denom, nbins, eds, mine, cur, run);
+    for (int e = 0; e < N; ++e) hist_one((double)v[e], first, last, denom, nbins, eds, mine, cur, run);
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (long long i = n4 << 2; i < n; ++i) hist_one((double)x[i], first, last, denom, nbins, eds, mine, cur, run);
+  if (blockIdx.x == 0 && threadIdx.x == 0)                  // the last n % N elements
+    for (long long t = nv * N; t < n; ++t) hist_one((double)x[t], first, last, denom, nbins, eds, mine, cur, run);
   if (run) atomicAdd(&mine[cur], run);
   __syncthreads();
   for (int k = threadIdx.x; k < nbins; k += blockDim.x) {
@@ -239,57 +178,48 @@ __global__ __launch_bounds__(256) void histogram_f32_kernel(const float* __restr
   }
 }
 
-inline int mm_grid(long long work) {
-  static const int cap = getenv("CLX_MINMAX_GRID") ? atoi(getenv("CLX_MINMAX_GRID")) : MM_BLOCKS;
-  long long g = (work + 255) / 256;
-  const int c = cap < MM_BLOCKS ? (cap < 1 ? 1 : cap) : MM_BLOCKS;
-  return (int)(g > c ? c : (g < 1 ? 1 : g));
+// the two entry points of each kernel: `who` is the entry's name in its messages
+template <typename T>
+int minmax_of(const char* who, const T* x, long long n, double* minmax, clx_stream stream) {
+  CLX_REQUIRE(x && minmax && n > 0, "%s: bad arguments", who);
+  CLX_REQUIRE(((uintptr_t)x & 15) == 0, "%s: x must be 16-byte aligned", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int g = blocks_of(n / (8 * Vec16<T>::N) + 1, MM_BLOCKS);
+  CLX_LAUNCH_KIND(CLX_PROF_MINMAX, minmax_kernel<T>, dim3(g), dim3(256), 0, st, x, n, minmax);
+  CLX_LAUNCH_KIND(CLX_PROF_MINMAX, minmax_final, dim3(1), dim3(256), 0, st, minmax, g);
+  CLX_CHECK_LAUNCH(who);
+  return CLX_OK;
+}
+
+template <typename T>
+int histogram_of(const char* who, const T* x, long long n, const double* edges, int nbins, long long* counts,
+                 clx_stream stream) {
+  CLX_REQUIRE(x && edges && counts && n > 0, "%s: bad arguments", who);
+  CLX_REQUIRE(nbins > 0 && nbins <= 2048, "%s: nbins must be in 1..2048", who);
+  CLX_REQUIRE(((uintptr_t)x & 15) == 0, "%s: x must be 16-byte aligned", who);
+  const size_t lds = (size_t)(nbins + 1) * sizeof(double) + (size_t)4 * nbins * sizeof(unsigned int);
+  CLX_LAUNCH_KIND(CLX_PROF_HISTOGRAM, histogram_kernel<T>, dim3(blocks_of(n / Vec16<T>::N + 1, HIST_BLOCKS)), dim3(256), lds,
+                  (hipStream_t)stream, x, n, edges, nbins, (unsigned long long*)counts);
+  CLX_CHECK_LAUNCH(who);
+  return CLX_OK;
 }
 
 }  // namespace
 
 extern "C" int clx_minmax_f32(const float* x, long long n, double* minmax, clx_stream stream) {
-  CLX_REQUIRE(x && minmax && n > 0, "clx_minmax_f32: bad arguments");
-  CLX_REQUIRE(((uintptr_t)x & 15) == 0, "clx_minmax_f32: x must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int g = mm_grid(n / 32 + 1);
-  CLX_LAUNCH_KIND(CLX_PROF_MINMAX, minmax_f32_kernel, dim3(g), dim3(256), 0, st, x, n, minmax);
-  CLX_LAUNCH_KIND(CLX_PROF_MINMAX, minmax_final, dim3(1), dim3(256), 0, st, minmax, g);
-  CLX_CHECK_LAUNCH("clx_minmax_f32");
-  return CLX_OK;
+  return minmax_of("clx_minmax_f32", x, n, minmax, stream);
+}
+
+extern "C" int clx_minmax_f64(const double* x, long long n, double* minmax, clx_stream stream) {
+  return minmax_of("clx_minmax_f64", x, n, minmax, stream);
 }
 
 extern "C" int clx_histogram_f32(const float* x, long long n, const double* edges, int nbins,
                                  long long* counts, clx_stream stream) {
-  CLX_REQUIRE(x && edges && counts && n > 0, "clx_histogram_f32: bad arguments");
-  CLX_REQUIRE(nbins > 0 && nbins <= 2048, "clx_histogram_f32: nbins must be in 1..2048");
-  CLX_REQUIRE(((uintptr_t)x & 15) == 0, "clx_histogram_f32: x must be 16-byte aligned");
-  const size_t lds = (size_t)(nbins + 1) * sizeof(double) + (size_t)4 * nbins * sizeof(unsigned int);
-  CLX_LAUNCH_KIND(CLX_PROF_HISTOGRAM, histogram_f32_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), lds,
-                  (hipStream_t)stream, x, n, edges, nbins, (unsigned long long*)counts);
-  CLX_CHECK_LAUNCH("clx_histogram_f32");
-  return CLX_OK;
-}
-
-extern "C" int clx_minmax_f64(const double* x, long long n, double* minmax, clx_stream stream) {
-  CLX_REQUIRE(x && minmax && n > 0, "clx_minmax_f64: bad arguments");
-  CLX_REQUIRE(((uintptr_t)x & 15) == 0, "clx_minmax_f64: x must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int g = mm_grid(n / 16 + 1);
-  CLX_LAUNCH_KIND(CLX_PROF_MINMAX, minmax_kernel, dim3(g), dim3(256), 0, st, x, n, minmax);
-  CLX_LAUNCH_KIND(CLX_PROF_MINMAX, minmax_final, dim3(1), dim3(256), 0, st, minmax, g);
-  CLX_CHECK_LAUNCH("clx_minmax_f64");
-  return CLX_OK;
+  return histogram_of("clx_histogram_f32", x, n, edges, nbins, counts, stream);
 }
 
 extern "C" int clx_histogram_f64(const double* x, long long n, const double* edges, int nbins,
                                  long long* counts, clx_stream stream) {
-  CLX_REQUIRE(x && edges && counts && n > 0, "clx_histogram_f64: bad arguments");
-  CLX_REQUIRE(nbins > 0 && nbins <= 2048, "clx_histogram_f64: nbins must be in 1..2048");
-  CLX_REQUIRE(((uintptr_t)x & 15) == 0, "clx_histogram_f64: x must be 16-byte aligned");
-  const size_t lds = (size_t)(nbins + 1) * sizeof(double) + (size_t)4 * nbins * sizeof(unsigned int);
-  CLX_LAUNCH_KIND(CLX_PROF_HISTOGRAM, histogram_kernel, dim3(grid_for(n / 2 + 1, 256)), dim3(256), lds, (hipStream_t)stream, 
-      x, n, edges, nbins, (unsigned long long*)counts);
-  CLX_CHECK_LAUNCH("clx_histogram_f64");
-  return CLX_OK;
+  return histogram_of("clx_histogram_f64", x, n, edges, nbins, counts, stream);
 }

@@ -111,7 +111,10 @@ def test_label_and_size_filter_bit_exact_vs_skimage_golden(case, device):
     assert size_filter(seg, 0, device=device) is seg                          # misc.py:12-13
 
 
-@pytest.mark.parametrize("shape", [(512, 512), (37, 61), (48, 64, 56), (1, 1), (1, 300), (3000, 2), (200, 260)])
+@pytest.mark.parametrize("shape", [(512, 512), (37, 61), (48, 64, 56), (1, 1), (1, 300), (3000, 2), (200, 260),
+                                   # one pixel wide: (6000, 1) outgrows the 2-D label-list layout (one mask word per row) and
+                                   # takes the run pipeline; (4000, 1) fits it without the edge-column buffers
+                                   (6000, 1), (4000, 1)])
 def test_size_filter_matches_oracle_random(shape, device):
     rng = np.random.default_rng(sum(shape))
     seg = (rng.random(shape) < 0.55).astype(np.int32) * rng.integers(1, 4, size=shape).astype(np.int32)
@@ -951,6 +954,58 @@ def test_float32_handover_kernels_equal_the_float64_ones_on_the_widened_values(s
     mm = (float(std32.min().item()), float(std32.max().item()))
     assert threshold_otsu(std32, minmax=mm) == threshold_otsu(std32.double())
     assert threshold_otsu(torch.full((5, 7), 1.25, dtype=torch.float32, device=device)) == 1.25
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_minmax_and_histogram_kernels_equal_numpy_at_the_ends_of_their_loops(dtype, device):
+    """clx_minmax_f32 / _f64 and clx_histogram_f32 / _f64 through the C ABI against NumPy, for equality, where the
+    loops over 16-byte pieces (N = 4 floats or 2 doubles) begin and end: every tail length n % N with both extremes in
+    the tail, the 8-piece min/max loop beside the single-piece one, and the 4-piece histogram loop — which starts beyond
+    1024 blocks x 768 pieces: one unrolled trip, then one single-piece trip per thread."""
+    from cellulus_amd import _clx
+
+    st = _clx.stream_ptr(device)
+    suffix = "f32" if dtype == np.float32 else "f64"
+    rng = np.random.default_rng(11)
+
+    def minmax(x_d):
+        mm = torch.full((_clx.MINMAX_DOUBLES,), float("nan"), dtype=torch.float64, device=device)
+        _clx.call("clx_minmax_" + suffix, _clx.ptr(x_d), x_d.numel(), _clx.ptr(mm), st)
+        return tuple(mm[:2].cpu().tolist())
+
+    def histogram(x_d, edges):
+        edges_d = torch.from_numpy(edges).to(device)
+        counts = torch.zeros(256, dtype=torch.int64, device=device)
+        _clx.call("clx_histogram_" + suffix, _clx.ptr(x_d), x_d.numel(), _clx.ptr(edges_d), 256, _clx.ptr(counts), st)
+        return counts.cpu().numpy()
+
+    def check(x, **hist_kw):
+        assert x.dtype == dtype
+        x_d = torch.from_numpy(x).to(device)
+        assert x_d.data_ptr() % 16 == 0
+        wide = x.astype(np.float64)
+        assert minmax(x_d) == (wide.min(), wide.max())
+        want, edges = np.histogram(wide, bins=256, **hist_kw)
+        np.testing.assert_array_equal(histogram(x_d, edges), want)
+        assert want.sum() == x.size
+
+    # tails: the minimum in the last element, the maximum in the last but one — inside the n % N tail for every residue
+    for n in range(1, 10):
+        x = rng.random(n).astype(dtype)
+        x[n - 1] = -1.5
+        if n >= 2:
+            x[n - 2] = 2.5
+        check(x, range=(-2.0, 3.0))
+    # min/max: threads 0 .. 163 of a block take the 8-piece loop, the rest the single-piece one
+    n = 129 * 1031
+    x = rng.random(n).astype(dtype)
+    x[0], x[n - 1] = -1.5, 2.5
+    check(x)
+    x[0], x[n - 1] = 2.5, -1.5
+    check(x)
+    # histogram: the smallest size that runs the 4-piece loop
+    n = 5 * 2 ** 20 + 3 if dtype == np.float32 else 5 * 2 ** 19 + 1
+    check(rng.random(n).astype(dtype))
 
 
 def test_noise_stats_emits_the_std_range(device):
