@@ -1,4 +1,4 @@
-"""What the label stages (``measure``, ``relate``, ``expand``, ``split``, ``propagate``, ``fill``) share on the host around
+"""What the label stages (``measure``, ``relate``, ``expand``, ``split``, ``propagate``, ``fill``, ``skeleton``) share on the host around
 their device work: rank 0 reads label datasets ``[sample, bandwidth, ...]`` of the segmentation container, writes a new one
 and one or two CSV files per bandwidth.  A stage checks its own arguments on every rank, then
 

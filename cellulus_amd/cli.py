@@ -7,7 +7,8 @@ command (``python -m cellulus_amd.expand <toml> --source NAME [--distance D --ou
 ``split`` command (``python -m cellulus_amd.split <toml> --source NAME --output NAME [--depth D] [--edge]``) and the ``fill``
 command (``python -m cellulus_amd.fill <toml> --source NAME --output NAME [--max-size N] [--planewise]``) and the ``propagate``
 command (``python -m cellulus_amd.propagate <toml> --seeds NAME --output NAME [--mask NAME] [--channel K [--levels 256]]
-[--regularisation 1] [--limit COST]``)."""
+[--regularisation 1] [--limit COST]``) and the ``skeleton`` command (``python -m cellulus_amd.skeleton <toml> --source NAME
+--output NAME [--max-iter N] [--planewise] [--radius]``)."""
 
 import click
 import tomli
@@ -151,6 +152,22 @@ def fill(config_file, source, output, max_size, planewise):
     from .fill import fill_stage
 
     fill_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output, max_size=max_size, planewise=planewise)
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
+@click.option("--source", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose objects are thinned to their centre lines")
+@click.option("--output", required=True, metavar="NAME", help="write the skeletons into a new dataset NAME")
+@click.option("--max-iter", default=None, metavar="N", type=click.IntRange(0),
+              help="stop after N iterations (two sub-iterations each); 0 changes nothing [default: until nothing is deleted]")
+@click.option("--planewise", is_flag=True, help="3-D: thin every slice as a 2-D map of its own (3-D maps need it)")
+@click.option("--radius", is_flag=True, help="add the smallest, largest and mean squared distance to the object's edge along the skeleton")
+def skeleton(config_file, source, output, max_iter, planewise, radius):
+    from .skeleton import skeleton_stage
+
+    skeleton_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output, max_iter=max_iter, planewise=planewise,
+                   radius=radius)
 
 
 @click.command()

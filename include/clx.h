@@ -1478,6 +1478,67 @@ int clx_label_holes(const int32_t* labels, int nd, int Z, int Y, int X, int plan
                     void* workspace, size_t workspace_bytes, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* "skeleton" stage: every object thinned to its centre lines, and measured  */
+/* (label_thin.hip)                                                          */
+/* ------------------------------------------------------------------------ */
+/* Thinning: CellProfiler's MorphologicalSkeleton, MATLAB's bwmorph('thin'), skimage.morphology.thin -- Guo & Hall 1989,
+ * algorithm A1, two alternating sub-iterations -- on a stored label map, for all objects in one call, label-aware.
+ *   input     one int32 map [Z][Y][X], 2-D (nd == 2, Z == 1) or 3-D.  Every non-zero value is an OBJECT pixel; the value is
+ *             compared and never used as an index.  With nd == 3 every slice is a 2-D map of its own: z neighbours do not
+ *             exist (3-D curve skeletons are not done).  The ends of rows and slices never wrap
+ *   neighbours of p  P2 .. P9 = N, NE, E, SE, S, SW, W, NW, N at y - 1.  Pk = 1 iff that pixel lies inside the slice, is still
+ *             alive and carries p's label.  A pixel of another label counts as background: touching objects thin independently
+ *   counts    C  = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2))
+ *             N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8),  N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9),  N = min(N1, N2)
+ *   sub-iteration  every alive pixel with C == 1, 2 <= N <= 3 and m == 0 is deleted, all at once from the state before the
+ *             sub-iteration.  Odd sub-iterations (the 1st, 3rd, ...): m = (P2 | P3 | !P5) & P4; even ones: m = (P6 | P7 | !P9) & P8
+ *   iteration an odd, then an even sub-iteration over the whole map
+ *   skeleton  the state after the first iteration that deletes nothing.  The rule is not transpose-equivariant
+ *   out       [Z][Y][X] int32, every element written by every call: labels[p] where p is alive after the iterations run so
+ *             far (over all calls since resume == 0), else 0
+ *   iterations  1 .. 64: the whole iterations this call queues on the stream at most, without any host synchronisation
+ *   resume    0: the call initialises the workspace from the labels.  1: it continues from the state a call with the same other
+ *             arguments left in the workspace, and initialises nothing but info
+ *   info [3]  cleared by the call.  [0] reserved, 0.  [1] the pixels deleted in the last iteration this call ran: 0 means the
+ *             fixed point is reached and out holds the skeleton.  [2] the pixels deleted by this call; summed over the calls it
+ *             is object pixels minus skeleton pixels, whatever `iterations` each call was given
+ *   workspace at least clx_label_thin_workspace(nd, Z, Y, X) bytes (a host-only function; 0: a shape the call refuses), 8-byte
+ *             aligned: 16 head words, 16 counters, ten bit planes of one 64-bit word per 64 pixels of a row (rows are padded
+ *             to whole words) and two flag bytes per tile
+ * The labels are read once, into bit planes: alive (two copies), and per neighbour "lies in my slice and has my label".  A
+ * launch runs up to 8 iterations: a block loads 8 words x 128 rows of the alive plane -- a tile of 384 x 96 pixels and a halo of
+ * 64 pixels / 16 rows -- into LDS, keeps the eight neighbour words of its words in registers, makes up to 16 bit-sliced
+ * sub-iterations on chip (one 64-bit operation serves 64 pixels) and writes its tile to the other alive plane: no launch reads
+ * a word it writes.  Every tile advances by the same sub-iterations a launch.  A tile works only if it or a neighbour tile
+ * deleted a pixel in the launch before; the launches after the fixed point return at once.  No block waits for another.
+ * Bits only: the same result in every run.
+ * Refused (CLX_ERR_ARG) before any launch: null labels, out, info or workspace, nd not 2 or 3, nd == 2 with Z != 1, a
+ * non-positive extent, Z*Y*X >= 2^31, iterations outside [1, 64], resume not 0 or 1, workspace_bytes below
+ * clx_label_thin_workspace(nd, Z, Y, X), a workspace that is not 8-byte aligned, out == labels. */
+size_t clx_label_thin_workspace(int nd, int Z, int Y, int X);
+int clx_label_thin(const int32_t* labels, int nd, int Z, int Y, int X, int iterations, int resume,
+                   int32_t* out, int32_t* info, void* workspace, size_t workspace_bytes, clx_stream stream);
+
+/* Census of a thinned map (of any map: the definitions need no thinning), per label, slice by slice as above.
+ *   face link      two face neighbours of one label
+ *   diagonal link  two diagonal neighbours of one label, neither of whose two common face neighbours carries that label
+ *   block          a 2 x 2 window in which all four pixels carry one label
+ *   degree         of a pixel: the number of its links.  END: degree 1, JUNCTION pixel: degree >= 3, ISOLATED: degree 0
+ *   words [nid][10] int64, initialised by the call: pixels, face_links, diag_links, blocks, ends, junctions, isolated, d2_sum,
+ *             d2_min, d2_max.  Every link and block is counted once.  The last three are the sum and extremes of dist_sq over
+ *             the label's pixels; with dist_sq == NULL, and for a label without pixels, 0, CLX_DIST_INF and -1.
+ *             pixels - face_links - diag_links + blocks is the label's Euler number with 8-connectivity, on any map
+ *   bad [1]   initialised by the call.  Bit 0: a label outside [0, nid): it counts as background, for its neighbours too, and
+ *             is never an index.  Bit 1: a dist_sq outside [0, CLX_DIST_INF) under a counted pixel; that pixel's value is left
+ *             out of the three d2 words
+ * Runs of a label inside 64 pixels of a row are summed in the wave, a block combines them in a table in LDS keyed by label
+ * (then straight to global memory) which it adds to the words once.  Integer atomics only: the same bits in every run.
+ * Refused (CLX_ERR_ARG) before any launch: null skeleton, words or bad, nd not 2 or 3, nd == 2 with Z != 1, a non-positive
+ * extent, Z*Y*X >= 2^31, nid outside [1, 2^24]. */
+int clx_skeleton_census(const int32_t* skeleton, const int32_t* dist_sq, int nd, int Z, int Y, int X, int nid,
+                        long long* words, int32_t* bad, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
