@@ -1,5 +1,5 @@
-"""What the label stages (``measure``, ``relate``, ``expand``, ``split``, ``propagate``, ``fill``, ``skeleton``) share on the host around
-their device work: rank 0 reads label datasets ``[sample, bandwidth, ...]`` of the segmentation container, writes a new one
+"""What the label stages (``measure``, ``relate``, ``expand``, ``split``, ``propagate``, ``fill``, ``skeleton``, ``granularity``) share on the
+host around their device work: rank 0 reads label datasets ``[sample, bandwidth, ...]`` of the segmentation container, writes a new one
 and one or two CSV files per bandwidth.  A stage checks its own arguments on every rank, then
 
     stage = _stage.begin(who, inference_config)          # None on every rank but 0; the metadata is read

@@ -1,14 +1,16 @@
 """Console entry points ``train <toml>`` / ``infer <toml>`` (cellulus/cli.py:10-27) and the ``measure`` command
 (``python -m cellulus_amd.measure <toml> [--contacts] [--topology] [--hull] [--inscribed] [--quantiles 0.25,0.5,0.75] [--mad]
 [--texture] [--texture-levels N] [--texture-distance D] [--radial] [--radial-rings N] [--radial-width W] [--radial-wedges]
-[--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity]``) and the ``relate`` command
+[--std] [--colocalization] [--coloc-threshold F] [--weighted] [--border-intensity] [--granularity N] [--granularity-background R]
+[--granularity-levels L]``) and the ``relate`` command
 (``python -m cellulus_amd.relate <toml> --children NAME --parents NAME [--clearance] [--tertiary NAME]``) and the ``expand``
 command (``python -m cellulus_amd.expand <toml> --source NAME [--distance D --output NAME] [--neighbours [--limit D]]``) and the
 ``split`` command (``python -m cellulus_amd.split <toml> --source NAME --output NAME [--depth D] [--edge]``) and the ``fill``
 command (``python -m cellulus_amd.fill <toml> --source NAME --output NAME [--max-size N] [--planewise]``) and the ``propagate``
 command (``python -m cellulus_amd.propagate <toml> --seeds NAME --output NAME [--mask NAME] [--channel K [--levels 256]]
 [--regularisation 1] [--limit COST]``) and the ``skeleton`` command (``python -m cellulus_amd.skeleton <toml> --source NAME
---output NAME [--max-iter N] [--planewise] [--radius]``)."""
+--output NAME [--max-iter N] [--planewise] [--radius]``) and the ``granularity`` command (``python -m cellulus_amd.granularity <toml>
+--source NAME [--channel K] [--scales 16] [--levels 256] [--background R]``)."""
 
 import click
 import tomli
@@ -74,8 +76,16 @@ def infer(config_file):
 @click.option("--border-intensity", is_flag=True,
               help="add the number of border pixels of every object and per raw channel the sum, mean, standard deviation, minimum "
                    "and maximum of the intensity over them")
+@click.option("--granularity", default=None, metavar="N", type=click.IntRange(1, 64),
+              help="add per raw channel the granular spectrum at N scales: the share of the object's intensity that lies in "
+                   "bright structure of each size, and what is left")
+@click.option("--granularity-background", default=0, show_default=True, metavar="R", type=click.IntRange(0, 64),
+              help="with --granularity: remove the background with a top-hat of radius R pixels first; 0: none")
+@click.option("--granularity-levels", default=256, show_default=True, metavar="L", type=click.IntRange(2, 65536),
+              help="with --granularity: grey levels between the smallest and the largest value of each sample's channel")
 def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, texture, texture_levels, texture_distance, radial,
-            radial_rings, radial_width, radial_wedges, std, colocalization, coloc_threshold, weighted, border_intensity):
+            radial_rings, radial_width, radial_wedges, std, colocalization, coloc_threshold, weighted, border_intensity, granularity,
+            granularity_background, granularity_levels):
     from .measure import measure as measure_experiment
 
     if quantiles is not None:
@@ -87,7 +97,8 @@ def measure(config_file, contacts, topology, hull, inscribed, quantiles, mad, te
                        inscribed=inscribed, quantiles=quantiles, mad=mad, texture=texture, texture_levels=texture_levels,
                        texture_distance=texture_distance, radial=radial, radial_rings=radial_rings, radial_width=radial_width,
                        radial_wedges=radial_wedges, std=std, colocalization=colocalization, coloc_threshold=coloc_threshold,
-                       weighted=weighted, border_intensity=border_intensity)
+                       weighted=weighted, border_intensity=border_intensity, granularity=granularity,
+                       granularity_background=granularity_background, granularity_levels=granularity_levels)
 
 
 @click.command()
@@ -168,6 +179,25 @@ def skeleton(config_file, source, output, max_iter, planewise, radius):
 
     skeleton_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output, max_iter=max_iter, planewise=planewise,
                    radius=radius)
+
+
+@click.command()
+@click.argument("config_file", type=click.Path(exists=True))
+@click.option("--source", required=True, metavar="NAME",
+              help="label dataset of the segmentation container whose objects' granular spectra are measured")
+@click.option("--channel", default=None, metavar="K", type=click.IntRange(0),
+              help="channel of the raw dataset to measure [default: every channel]")
+@click.option("--scales", default=16, show_default=True, metavar="N", type=click.IntRange(1, 64),
+              help="scales of the spectrum: scale i is a diamond of radius i pixels")
+@click.option("--levels", default=256, show_default=True, metavar="L", type=click.IntRange(2, 65536),
+              help="grey levels between the smallest and the largest value of each sample's channel")
+@click.option("--background", default=0, show_default=True, metavar="R", type=click.IntRange(0, 64),
+              help="remove the background with a top-hat of radius R pixels first; 0: none")
+def granularity(config_file, source, channel, scales, levels, background):
+    from .granularity import granularity_stage
+
+    granularity_stage(ExperimentConfig(**_load(config_file)).inference_config, source, channel=channel, scales=scales, levels=levels,
+                      background=background)
 
 
 @click.command()

@@ -841,7 +841,8 @@ def border_intensity(labels, raw, k=0, device=None):
 def region_table(labels, raw=None, device=None, boundary=False, topology=False, hull=False, inscribed=False, edge=False,
                  quantiles=None, mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None,
                  radial=False, radial_rings=4, radial_width=None, radial_wedges=False, std=False, colocalization=False,
-                 coloc_threshold=0.15, weighted=False, border_intensity=False):
+                 coloc_threshold=0.15, granularity=None, granularity_background=0, granularity_levels=256, weighted=False,
+                 border_intensity=False):
     """One row per object id present in ``labels`` (2-D or 3-D integers, array or device tensor), ascending; columns
     ``label, area, bbox_min_*, bbox_max_*`` (max exclusive), ``centroid_*, cov_*, cov_eig_0..nd-1`` (descending),
     ``equivalent_diameter`` and, per channel k of ``raw`` (``None``, ``(*spatial)`` or ``(C, *spatial)``; float32,
@@ -904,19 +905,32 @@ def region_table(labels, raw=None, device=None, boundary=False, topology=False, 
     ``intensity_border_max_c{k}`` over those pixels (CellProfiler's *IntensityEdge; ``border_intensity``,
     ``border_intensity_columns``).  It has nothing to do with ``edge``, which says whether the image edge counts as background
     for the distance map.  All of channel 0's weighted columns come before channel 1's, and so do the border columns.
+    ``granularity=n`` (an integer in 1 .. 64; needs ``raw``) appends, after all of those, per channel k ``granularity_1_c{k}`` ..
+    ``granularity_{n}_c{k}`` and ``granularity_residual_c{k}``: the granular spectrum of the object in that channel, CellProfiler's
+    MeasureGranularity without its subsampling (``cellulus_amd.granularity``: ``granularity_table``, ``granularity_columns``), at
+    ``granularity_levels`` grey levels (2 .. 65536) over the whole image's range, after a top-hat of radius
+    ``granularity_background`` (0 .. 64; 0: none).
     Returns ``dict[str, np.ndarray]``.  Runs on a HIP device; there is no CPU path."""
     return _region_table(labels, raw, device, boundary, topology=topology, hull=hull, inscribed=inscribed, edge=edge, quantiles=quantiles,
                          mad=mad, texture=texture, texture_levels=texture_levels, texture_distance=texture_distance,
                          texture_range=texture_range, radial=radial, radial_rings=radial_rings, radial_width=radial_width,
                          radial_wedges=radial_wedges, std=std, colocalization=colocalization, coloc_threshold=coloc_threshold,
-                         weighted=weighted, border_intensity=border_intensity)[0]
+                         weighted=weighted, border_intensity=border_intensity, granularity=granularity,
+                         granularity_background=granularity_background, granularity_levels=granularity_levels)[0]
 
 
 def _region_table(labels, raw, device, boundary, topology=False, hull=False, inscribed=False, edge=False, quantiles=None,
                   mad=False, texture=False, texture_levels=8, texture_distance=1, texture_range=None, radial=False,
                   radial_rings=4, radial_width=None, radial_wedges=False, std=False, colocalization=False, coloc_threshold=0.15,
-                  weighted=False, border_intensity=False):
+                  granularity=None, granularity_background=0, granularity_levels=256, weighted=False, border_intensity=False):
     """region_table's columns and, with ``boundary``, contact_pairs' rows (else None)"""
+    if granularity is not None:
+        from . import granularity as _granularity
+
+        if raw is None:
+            raise ValueError("region_table: granularity needs raw")
+        granularity, granularity_levels, granularity_background = _granularity._check_table(granularity, granularity_levels,
+                                                                                              granularity_background, "region_table")
     quantiles = _check_quantiles(quantiles, mad, raw)
     coloc_threshold = _check_products(std, colocalization, coloc_threshold, labels, raw)
     _check_weighted(weighted, border_intensity, raw)
@@ -959,12 +973,15 @@ def _region_table(labels, raw, device, boundary, topology=False, hull=False, ins
         cols.update(_products_columns_of(scene, std, colocalization, coloc_threshold))
     if weighted or border_intensity:
         cols.update(_weighted_columns_of(scene, weighted, border_intensity))
+    if granularity is not None:
+        cols.update(_granularity._columns_of(scene, scene.raw, granularity, granularity_levels, None, granularity_background, "region_table"))
     return cols, pairs
 
 
 def measure(inference_config, contacts=False, topology=False, hull=False, inscribed=False, quantiles=None, mad=False, texture=False,
             texture_levels=8, texture_distance=1, radial=False, radial_rings=4, radial_width=None, radial_wedges=False, std=False,
-            colocalization=False, coloc_threshold=0.15, weighted=False, border_intensity=False) -> None:
+            colocalization=False, coloc_threshold=0.15, granularity=None, granularity_background=0, granularity_levels=256,
+            weighted=False, border_intensity=False) -> None:
     """For every bandwidth: the tables of all samples' label maps (``segmentation_dataset_config.dataset_name``) with
     every channel of the raw dataset, as ``measurements_bandwidth-<b>.csv`` in the working directory — a header line,
     then ``sample`` and ``region_table``'s columns, floats as ``%.17g``.  ``contacts=True`` adds the boundary columns
@@ -980,7 +997,9 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
     ``colocalization=True`` the colocalization columns of every pair of channels with ``coloc_threshold`` (``region_table``'s
     arguments); ``weighted=True`` the intensity-weighted centroid, covariance, mass displacement, integrated intensity and peak
     position of every channel, ``border_intensity=True`` the intensity columns over every object's border pixels
-    (``region_table``'s arguments, ``edge=False``).  Rank 0 works alone under torch.distributed."""
+    (``region_table``'s arguments, ``edge=False``); ``granularity=n`` the granular spectrum of every channel at ``n`` scales, with
+    ``granularity_background`` and ``granularity_levels`` (``region_table``'s arguments; the levels divide the range of each
+    sample's raw channel over the whole image).  Rank 0 works alone under torch.distributed."""
     from .utils import zarr_io
 
     stage = _stage.begin("measure", inference_config)
@@ -998,7 +1017,8 @@ def measure(inference_config, contacts=False, topology=False, hull=False, inscri
                                      texture_distance=texture_distance, radial=radial, radial_rings=radial_rings,
                                      radial_width=radial_width, radial_wedges=radial_wedges, std=std,
                                      colocalization=colocalization, coloc_threshold=coloc_threshold, weighted=weighted,
-                                     border_intensity=border_intensity)
+                                     border_intensity=border_intensity, granularity=granularity,
+                                     granularity_background=granularity_background, granularity_levels=granularity_levels)
         return (table, dict(zip(_CONTACTS_HEADER[1:], pairs))) if contacts else (table,)
 
     stage.run(per_sample, ("measurements", "contacts") if contacts else ("measurements",), keep={"contacts": lambda t: t["label_a"] > 0},

@@ -1539,6 +1539,63 @@ int clx_skeleton_census(const int32_t* skeleton, const int32_t* dist_sq, int nd,
                         long long* words, int32_t* bad, clx_stream stream);
 
 /* ------------------------------------------------------------------------ */
+/* "granularity" stage: grey-scale morphology on a map of grey levels        */
+/* (grey_morph.hip)                                                          */
+/* ------------------------------------------------------------------------ */
+/* Erosion, dilation and reconstruction by dilation -- the building blocks of CellProfiler's MeasureGranularity, of opening by
+ * reconstruction, top-hat, h-maxima and regional maxima -- on int32 maps [Z][Y][X], 2-D (nd == 2, Z == 1) or 3-D.
+ *   values    grey levels in [0, 65535]
+ *   mask      uint8, or NULL (all inside).  A pixel with mask[p] == 0 is OUTSIDE, and so is everything beyond the map; the ends
+ *             of rows and slices never wrap.  Outside pixels get 0 and conduct nothing
+ *   neighbours  the 4 (nd == 2) or 6 FACE neighbours: CellProfiler's footprint, the disc of radius 1
+ *   bad values  a value outside [0, 65535] under an inside pixel counts as 0 and sets a bad bit
+ *
+ * clx_grey_morph: op 0 erodes, op 1 dilates.  One step: out[p] = the min / max of in over p and its inside face neighbours;
+ * `steps` = k steps are the step applied k times: the min / max over the inside pixels reachable from p by at most k face steps
+ * through inside pixels -- without a mask the L1 ball of radius k.
+ *   steps     1 .. 16 (nd == 3: 1 .. 4): all of them are made on chip in one launch; callers chain calls for more
+ *   out       [Z][Y][X] int32, every element written; must not alias in
+ *   bad [1]   initialised by the call.  Bit 0: a value of `in` out of range under an inside pixel
+ * A block takes a tile (64 x 32, or 32 x 8 x 8) and a halo of `steps` pixels, as 16-bit values and inside bits in LDS, applies
+ * the step `steps` times between two LDS buffers, each on the region it is still exact on, and writes the tile.
+ * Refused (CLX_ERR_ARG) before any launch: null in, out or bad, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent,
+ * Z*Y*X >= 2^32, op not 0 or 1, steps outside [1, 16] (nd == 3: [1, 4]), out == in or out == mask.
+ *
+ * clx_grey_reconstruct: reconstruction by dilation of `marker` under `image`.  With m = min(marker, image) pointwise, out is
+ * the least map r >= m with r[p] = min(image[p], max(r[p], max over the inside face neighbours q of r[q])): out[p] is the
+ * maximum, over the face-connected paths of inside pixels from some q to p, of min(m[q], the smallest image value on the path).
+ * So m <= out <= image, reconstructing out again changes nothing, out is monotone in marker, and transposing the inputs
+ * transposes out.  The value only rises from m and every value it takes is that of a real path: the fixed point reached from
+ * below is the least one whatever the order of the updates, a function of the inputs alone.
+ *   out       [Z][Y][X] int32.  While info[1] != 0 it holds an intermediate state; must not alias marker, image or mask
+ *   rounds    1 .. 64: the rounds this call queues on the stream at most, without any host synchronisation
+ *   resume    0: the call initialises out and the workspace from marker, image and mask.  1: it continues from the state a call
+ *             with the same other arguments left in out and workspace, and initialises nothing but info
+ *   info [3]  cleared by the call.  [0] (resume == 0 only) bit 0: a marker value out of range under an inside pixel, bit 1: an
+ *             image value.  [1] the tiles that changed in the last round of the call: 0 means the fixed point is reached and
+ *             out holds the result.  [2] the rounds of this call in which some tile changed; summed over the calls it is the
+ *             same in every run, whatever `rounds` each call was given
+ *   workspace at least clx_grey_reconstruct_workspace(nd, Z, Y, X) bytes (a host-only function; 0: a shape the call refuses),
+ *             4-byte aligned: 16 head words, 64 round counters, one more int32 map, two flag bytes per tile and the image as
+ *             16-bit words
+ * A round is one launch: a block takes a tile (256 x 32, or 64 x 8 x 8) with a halo of one pixel, 16-bit values in LDS, and
+ * makes sweeps of directional scans -- +x, -x, +y, -y (+z, -z) -- until a sweep changes nothing, at most 16 of them (a tile cut
+ * short counts as changed), then writes its interior to the other plane (out and the workspace's alternate: no launch reads a
+ * word it writes).  Along a row 64 pixels are one wave scan over clamps x -> min(hi, max(lo, x)), whose composition is again
+ * a clamp.  A tile works only if it or a face-, edge- or corner-adjacent tile changed in the round before; the rounds after the
+ * fixed point return at once.  No block waits for another.  Integer minima and maxima only: the same bits and the same rounds
+ * in every run.  Because the fixed point is unique only info[2] depends on the inner loop.
+ * Refused (CLX_ERR_ARG) before any launch: null marker, image, out, info or workspace, nd not 2 or 3, nd == 2 with Z != 1, a
+ * non-positive extent, Z*Y*X >= 2^32, rounds outside [1, 64], resume not 0 or 1, workspace_bytes below
+ * clx_grey_reconstruct_workspace(nd, Z, Y, X), a workspace that is not 4-byte aligned, out == marker, image or mask. */
+int clx_grey_morph(const int32_t* in, const uint8_t* mask, int nd, int Z, int Y, int X, int op, int steps,
+                   int32_t* out, int32_t* bad, clx_stream stream);
+size_t clx_grey_reconstruct_workspace(int nd, int Z, int Y, int X);
+int clx_grey_reconstruct(const int32_t* marker, const int32_t* image, const uint8_t* mask,
+                         int nd, int Z, int Y, int X, int rounds, int resume, int32_t* out, int32_t* info,
+                         void* workspace, size_t workspace_bytes, clx_stream stream);
+
+/* ------------------------------------------------------------------------ */
 /* Input decoding (host side): the Blosc/LZ4 chunks zarr writes by default    */
 /* (docs/examples/2d/01-data.py:35-50, read by zarr_dataset.py:104-121)       */
 /* ------------------------------------------------------------------------ */
