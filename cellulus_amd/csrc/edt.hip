@@ -497,9 +497,15 @@ int grow_shrink_tiled(int* seg, int Z, int Y, int X, int grow, int shrink, void*
   CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, fg_mask_kernel, dim3(grid_for((npix + 3) / 4, 256)), dim3(256), 0, st, seg, mask, npix);
   const dim3 grid((X + T::TX - 1) / T::TX, (Y + T::TY - 1) / T::TY, (Z + T::TZ - 1) / T::TZ);
   const size_t smem = gs_smem_bytes<ND>(grow, shrink);
-  const int rc = (grow == 3 && shrink == 6)      // segment.py's defaults (inference_config.py:158-159)
-                     ? gs_launch<ND, 3, 6>(grid, smem, seg, mask, Z, Y, X, grow, shrink, flag, st)
-                     : gs_launch<ND, -1, -1>(grid, smem, seg, mask, Z, Y, X, grow, shrink, flag, st);
+  // segment.py's defaults (inference_config.py:158-159) are compiled in for 3-D only: in 2-D their halo of 7 always
+  // takes the bit rows
+  int rc;
+  if constexpr (ND == 3) {
+    rc = (grow == 3 && shrink == 6) ? gs_launch<3, 3, 6>(grid, smem, seg, mask, Z, Y, X, grow, shrink, flag, st)
+                                    : gs_launch<3, -1, -1>(grid, smem, seg, mask, Z, Y, X, grow, shrink, flag, st);
+  } else {
+    rc = gs_launch<ND, -1, -1>(grid, smem, seg, mask, Z, Y, X, grow, shrink, flag, st);
+  }
   if (rc) return rc;
   CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, grow_shrink_phantom, dim3(grid_for(npix, 256) < 1024 ? grid_for(npix, 256) : 1024), dim3(256), 0, st, seg, Z, Y, X,
                                                                                                shrink, flag);

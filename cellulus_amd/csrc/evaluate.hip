@@ -25,11 +25,12 @@ __global__ __launch_bounds__(256) void presence_kernel(const int32_t* __restrict
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const i32x4 v = l4[i];
-    int prev = -1;
+    int prev = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int id = v[k];
-      if (id == prev) continue;                       // label maps are piecewise constant
+      if (k > 0 && id == prev) continue;              // label maps are piecewise constant (the first id of a group has no
+                                                      // predecessor: no start value of `prev` may stand for one, -1 is an id too)
       prev = id;
       if ((unsigned)id < (unsigned)nid) present[id] = 1; else *bad = 1;
     }

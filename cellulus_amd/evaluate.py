@@ -72,7 +72,9 @@ def joint_histogram_on_device(prediction, groundtruth, device=None):
     def up(a):
         if not torch.is_tensor(a):
             a = torch.from_numpy(np.ascontiguousarray(a).astype(np.int32))
-        return a.to(device=device, dtype=torch.int32).contiguous().reshape(-1)
+        a = a.to(device=device, dtype=torch.int32).contiguous().reshape(-1)
+        # the kernels read 16-byte groups: a contiguous view that starts inside one (a[1:]) is copied
+        return a if a.data_ptr() % 16 == 0 else a.clone()
 
     p, g = up(prediction), up(groundtruth)
     assert p.numel() == g.numel(), "prediction and ground truth differ in shape"

@@ -214,8 +214,11 @@ def test_grow_shrink_bit_exact(shape, device):
 
 @pytest.mark.parametrize("shape", [(97, 131), (33, 64), (1, 5), (70, 300), (9, 21, 45), (24, 8, 33), (3, 70, 70)])
 def test_grow_shrink_tile_kernel_random_images(shape, device):
-    """the one-kernel grow/shrink (tile + halo in LDS) against the scipy-EDT oracle: ragged extents,
-    sparse / dense / empty / full label images, bounds from 0 to the fall-back of the generic path"""
+    """grow/shrink against the scipy-EDT oracle: ragged extents, sparse / dense / empty / full label images, bounds from 0
+    to the fall-back of the generic path.  The 2-D shapes reach the bit-row kernels (halo <= 16: every pair but (14, 14))
+    and the generic EDT passes ((14, 14), halo 26), never the 2-D tile kernel; the 3-D shapes reach the tile kernel (tile +
+    halo in LDS, up to 109 824 B) and with (9, 9) and (14, 14) the generic passes.  The remaining paths:
+    tests/test_gpu_infer_tail.py"""
     from cellulus_amd.segment import grow_shrink_on_device
 
     rng = np.random.default_rng(7)
