@@ -26,6 +26,18 @@ void clx_set_error(const char* fmt, ...);
     }                                                                    \
   } while (0)
 
+// The checks on the shape of a 2-D or 3-D map that the label and region entry points share (clx_core.hip), `who` in front of
+// the message; `who` == NULL sets none, for a *_workspace function that answers 0.  clx_map_dims: nd is 2 or 3, the extents
+// are positive, nd == 2 has Z == 1.  clx_map_bound: Z * Y * X of positive extents lies below 2^bits (31 or 32) -> *npix.
+// clx_map_shape: the one, then the other.  All return CLX_OK or CLX_ERR_ARG.
+int clx_map_dims(const char* who, int nd, int Z, int Y, int X);
+int clx_map_bound(const char* who, int Z, int Y, int X, int bits, long long* npix);
+int clx_map_shape(const char* who, int nd, int Z, int Y, int X, int bits, long long* npix);
+// declares `long long npix`, the pixels of the map, or returns the refusal of clx_map_shape
+#define CLX_REQUIRE_MAP(npix, who, nd, Z, Y, X, bits) \
+  long long npix = 0;                                 \
+  if (clx_map_shape(who, nd, Z, Y, X, bits, &npix) != CLX_OK) return CLX_ERR_ARG
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

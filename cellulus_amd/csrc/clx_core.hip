@@ -10,6 +10,26 @@ void clx_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+static int refuse_map(const char* who, const char* why, int bits = 0) {
+  if (who) clx_set_error(why, who, bits);
+  return CLX_ERR_ARG;
+}
+int clx_map_dims(const char* who, int nd, int Z, int Y, int X) {
+  if (nd != 2 && nd != 3) return refuse_map(who, "%s: nd must be 2 or 3");
+  if (Z <= 0 || Y <= 0 || X <= 0) return refuse_map(who, "%s: bad shape");
+  if (nd == 2 && Z != 1) return refuse_map(who, "%s: nd == 2 needs Z == 1");
+  return CLX_OK;
+}
+int clx_map_bound(const char* who, int Z, int Y, int X, int bits, long long* npix) {
+  const unsigned __int128 n = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
+  if (n >= ((unsigned __int128)1 << bits)) return refuse_map(who, "%s: Z * Y * X must be below 2^%d", bits);
+  *npix = (long long)n;
+  return CLX_OK;
+}
+int clx_map_shape(const char* who, int nd, int Z, int Y, int X, int bits, long long* npix) {
+  return clx_map_dims(who, nd, Z, Y, X) != CLX_OK ? CLX_ERR_ARG : clx_map_bound(who, Z, Y, X, bits, npix);
+}
+
 extern "C" const char* clx_last_error(void) { return g_err; }
 extern "C" int clx_abi_version(void) { return 13; }
 extern "C" int clx_device_count(void) {

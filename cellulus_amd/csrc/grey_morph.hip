@@ -27,29 +27,18 @@
 //              over (lo, hi) pairs, packed in one 32-bit word, and the carry of the pixel before goes through the result;
 //              a wave owns whole rows.  Along y and z a thread owns a line (consecutive lanes consecutive in x) and walks it
 //              up and down with the carry in a register.
-//   ping-pong  between rounds the value lies in an int32 plane; round r reads `out` and writes the workspace's plane if r is
-//              even, the other way round if odd: no launch reads a word it writes, and the state after round r is a function
-//              of the inputs.  r counts over all calls since resume == 0 and lies in the workspace's head.  The image, with
-//              the mask and the range applied, lies in the workspace as 16-bit words.
-//   activity   a tile has a changed flag per round, in two arrays that alternate like the planes.  A tile is ACTIVE in round r
-//              iff it or one of its 8 / 26 face-, edge- or corner-adjacent tiles changed in round r - 1 (round 0: all are).  An
-//              active tile always writes its interior; an inactive one clears its flag and is done.  An inactive tile would not
-//              have changed: its values and its halo are those of the round in which it last came to rest.  By induction it
-//              holds equal values in both planes, so when a round changes no tile both planes hold the fixed point.
-//   counters   a word per round of the call counts the tiles that changed in it; a launch that finds 0 in the word of the
-//              round before returns at once, as do all after it.  The last launch of a call forms info from the counters and
-//              leaves r and the last count in the head for a call with resume == 1.
+//   planes     between rounds the value lies in an int32 plane; round r reads `out` and writes the workspace's plane if r is
+//              even, the other way round if odd.  The image, with the mask and the range applied, lies in the workspace as
+//              16-bit words.  The rounds are queued, tiles at rest skipped and the call ended as tile_rounds.h says, where the
+//              proof stands that a skipped tile would not have changed.
 // Integer minima and maxima only: the same bits and the same rounds in every run.
 #include "region_scan.h"
+#include "tile_rounds.h"
 
 namespace {
 
 constexpr unsigned int MAX_LEVEL = 65535u;
-constexpr int TILE_MAX_GRID = 1024;     // blocks a launch; each takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
-constexpr int INIT_MAX_GRID = 4096;     // blocks of BLOCK pixels a trip (the first call's start values)
 constexpr int MAX_SWEEPS = 16;          // sweeps of directional scans a tile makes in LDS in one round
-constexpr int MAX_ROUNDS = 64;          // launches a call queues at most: the counters of a call
-constexpr int HEAD_WORDS = 16;          // [0] rounds so far, [1] the tiles that changed in the last of them (or 1: none yet)
 constexpr int WAVES = BLOCK / 64;
 
 template <int ND> struct MorphShape;    // the tile of clx_grey_morph and the largest halo: the steps of one launch
@@ -58,21 +47,6 @@ template <> struct MorphShape<3> { static constexpr int TZ = 8, TY = 8, TX = 32,
 template <int ND> struct ReconShape;    // the tile of clx_grey_reconstruct; TX is a multiple of 64: a wave scans 64 pixels
 template <> struct ReconShape<2> { static constexpr int TZ = 1, TY = 32, TX = 256, ZH = 0; };
 template <> struct ReconShape<3> { static constexpr int TZ = 8, TY = 8, TX = 64, ZH = 1; };
-
-struct TileGrid {
-  int ntz, nty, ntx;
-  long long ntiles;
-};
-template <typename S2, typename S3>
-inline TileGrid tile_grid(int nd, int Z, int Y, int X) {
-  TileGrid g;
-  g.ntz = nd == 2 ? 1 : (Z + S3::TZ - 1) / S3::TZ;
-  g.nty = nd == 2 ? (Y + S2::TY - 1) / S2::TY : (Y + S3::TY - 1) / S3::TY;
-  g.ntx = nd == 2 ? (X + S2::TX - 1) / S2::TX : (X + S3::TX - 1) / S3::TX;
-  g.ntiles = (long long)g.ntz * g.nty * g.ntx;
-  return g;
-}
-inline size_t flag_bytes(long long ntiles) { return ((size_t)ntiles + 3) & ~(size_t)3; }
 
 __device__ __forceinline__ unsigned int umin(unsigned int a, unsigned int b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned int umax(unsigned int a, unsigned int b) { return a > b ? a : b; }
@@ -164,10 +138,7 @@ struct Planes {
   int* out;
   int* wout;
   unsigned short* image;                // the image with the mask and the range applied: 0 on outside pixels
-  unsigned char* flag0;                 // written by the even rounds
-  unsigned char* flag1;
-  int* head;
-  int* counters;
+  Rounds w;
 };
 
 __global__ __launch_bounds__(BLOCK) void reconstruct_init(const int* __restrict__ marker, const int* __restrict__ image,
@@ -185,7 +156,7 @@ __global__ __launch_bounds__(BLOCK) void reconstruct_init(const int* __restrict_
     q.image[p] = (unsigned short)v;
     q.out[p] = (int)umin(m, v);
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) { q.head[0] = 0; q.head[1] = 1; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) rounds_reset(q.w);
   if (flags) atomicOr(info, flags);
 }
 
@@ -235,33 +206,19 @@ template <int ND>
 __global__ __launch_bounds__(BLOCK) void reconstruct_round(Planes q, int k, int Z, int Y, int X, TileGrid g) {
   typedef ReconShape<ND> S;
   constexpr int HX = S::TX + 2, HY = S::TY + 2, HZ = S::TZ + 2 * S::ZH, HN = HX * HY * HZ;
-  constexpr int NTILES_AROUND = ND == 2 ? 9 : 27;
   constexpr int NPIX = S::TZ * S::TY * S::TX, SEGS = S::TX / 64;
   __shared__ unsigned short r[HN];
   __shared__ unsigned short im[HN];
 
-  if ((k == 0 ? q.head[1] : q.counters[k - 1]) == 0) return;        // the round before changed no tile: the fixed point is reached
-  const unsigned int round = (unsigned int)q.head[0] + (unsigned int)k;
-  const bool odd = round & 1u;
-  const int* __restrict__ src = odd ? q.wout : q.out;
-  int* __restrict__ dst = odd ? q.out : q.wout;
-  const unsigned char* __restrict__ fin = odd ? q.flag0 : q.flag1;
-  unsigned char* __restrict__ fout = odd ? q.flag1 : q.flag0;
+  Round rd;
+  if (!open_round(q.w, k, rd)) return;
+  const int* __restrict__ src = rd.odd ? q.wout : q.out;
+  int* __restrict__ dst = rd.odd ? q.out : q.wout;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
   for (long long t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
     const int tx = (int)(t % g.ntx), ty = (int)((t / g.ntx) % g.nty), tz = (int)(t / ((long long)g.ntx * g.nty));
-    int active = round == 0;
-    if (round != 0 && threadIdx.x < NTILES_AROUND) {
-      const int i = threadIdx.x;
-      const int nx = tx + i % 3 - 1, ny = ty + (i / 3) % 3 - 1, nz = tz + i / 9 - (ND == 2 ? 0 : 1);
-      if ((unsigned int)nx < (unsigned int)g.ntx && (unsigned int)ny < (unsigned int)g.nty && (unsigned int)nz < (unsigned int)g.ntz)
-        active = fin[((long long)nz * g.nty + ny) * g.ntx + nx];
-    }
-    if (!__syncthreads_or(active)) {                      // the barrier also ends the reads of the tile before
-      if (threadIdx.x == 0) fout[t] = 0;
-      continue;
-    }
+    if (!tile_active<ND>(rd, g.ntz, g.nty, g.ntx, t, tz, ty, tx)) continue;
 
     const int z0 = tz * S::TZ - S::ZH, y0 = ty * S::TY - 1, x0 = tx * S::TX - 1;
     for (int i = threadIdx.x; i < HN; i += BLOCK) {
@@ -307,28 +264,8 @@ __global__ __launch_bounds__(BLOCK) void reconstruct_round(Planes q, int k, int 
       const int gz = tz * S::TZ + iz, gy = ty * S::TY + iy, gx = tx * S::TX + ix;
       if (gz < Z && gy < Y && gx < X) dst[((long long)gz * Y + gy) * X + gx] = (int)r[((iz + S::ZH) * HY + iy + 1) * HX + ix + 1];
     }
-    if (threadIdx.x == 0) {
-      fout[t] = (unsigned char)tile_changed;
-      if (tile_changed) atomicAdd(q.counters + k, 1);
-    }
+    close_tile(q.w, rd, k, t, tile_changed);
   }
-}
-
-// the last launch of a call: info from the counters, and the head for the next call
-__global__ void reconstruct_finish(int* __restrict__ head, const int* __restrict__ counters, int rounds, int* __restrict__ info) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  int busy = 0;
-  for (int k = 0; k < MAX_ROUNDS; ++k)
-    if (k < rounds && counters[k] != 0) ++busy;
-  info[1] = counters[rounds - 1];
-  info[2] = busy;
-  head[0] = (int)((unsigned int)head[0] + (unsigned int)rounds);
-  head[1] = counters[rounds - 1];
-}
-
-inline bool shape_ok(int nd, int Z, int Y, int X) {
-  return (nd == 2 || nd == 3) && Z > 0 && Y > 0 && X > 0 && (nd == 3 || Z == 1) &&
-         (unsigned __int128)Z * (unsigned)Y * (unsigned)X < ((unsigned __int128)1 << 32);
 }
 
 template <int ND, bool DILATE>
@@ -343,10 +280,7 @@ void launch_morph(const int* in, const unsigned char* mask, int Z, int Y, int X,
 extern "C" int clx_grey_morph(const int32_t* in, const uint8_t* mask, int nd, int Z, int Y, int X, int op, int steps, int32_t* out,
                               int32_t* bad, clx_stream stream) {
   CLX_REQUIRE(in && out && bad, "clx_grey_morph: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_grey_morph: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_grey_morph: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_grey_morph: nd == 2 needs Z == 1");
-  CLX_REQUIRE(shape_ok(nd, Z, Y, X), "clx_grey_morph: Z * Y * X must be below 2^32");
+  CLX_REQUIRE_MAP(npix, "clx_grey_morph", nd, Z, Y, X, 32);
   CLX_REQUIRE(op == 0 || op == 1, "clx_grey_morph: op must be 0 (erode) or 1 (dilate)");
   CLX_REQUIRE(steps >= 1 && steps <= (nd == 2 ? MorphShape<2>::HMAX : MorphShape<3>::HMAX),
               "clx_grey_morph: steps must lie in [1, 16] (nd == 3: [1, 4])");
@@ -365,49 +299,37 @@ extern "C" int clx_grey_morph(const int32_t* in, const uint8_t* mask, int nd, in
 }
 
 extern "C" size_t clx_grey_reconstruct_workspace(int nd, int Z, int Y, int X) {
-  if (!shape_ok(nd, Z, Y, X)) return 0;
-  const size_t npix = (size_t)Z * (size_t)Y * (size_t)X;
+  long long npix;
+  if (clx_map_shape(nullptr, nd, Z, Y, X, 32, &npix) != CLX_OK) return 0;
   const TileGrid g = tile_grid<ReconShape<2>, ReconShape<3>>(nd, Z, Y, X);
-  return (size_t)(HEAD_WORDS + MAX_ROUNDS) * sizeof(int) + npix * sizeof(int) + 2 * flag_bytes(g.ntiles) + npix * sizeof(unsigned short);
+  return ROUNDS_HEAD_BYTES + (size_t)npix * sizeof(int) + 2 * flag_bytes(g.ntiles) + (size_t)npix * sizeof(unsigned short);
 }
 
 extern "C" int clx_grey_reconstruct(const int32_t* marker, const int32_t* image, const uint8_t* mask, int nd, int Z, int Y, int X,
                                     int rounds, int resume, int32_t* out, int32_t* info, void* workspace, size_t workspace_bytes,
                                     clx_stream stream) {
   CLX_REQUIRE(marker && image && out && info && workspace, "clx_grey_reconstruct: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_grey_reconstruct: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_grey_reconstruct: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_grey_reconstruct: nd == 2 needs Z == 1");
-  CLX_REQUIRE(shape_ok(nd, Z, Y, X), "clx_grey_reconstruct: Z * Y * X must be below 2^32");
+  CLX_REQUIRE_MAP(npix, "clx_grey_reconstruct", nd, Z, Y, X, 32);
   CLX_REQUIRE(rounds >= 1 && rounds <= MAX_ROUNDS, "clx_grey_reconstruct: rounds must lie in [1, 64]");
   CLX_REQUIRE(resume == 0 || resume == 1, "clx_grey_reconstruct: resume must be 0 or 1");
   CLX_REQUIRE(workspace_bytes >= clx_grey_reconstruct_workspace(nd, Z, Y, X),
               "clx_grey_reconstruct: workspace_bytes is below clx_grey_reconstruct_workspace(nd, Z, Y, X)");
   CLX_REQUIRE(((uintptr_t)workspace & 3) == 0, "clx_grey_reconstruct: workspace must be 4-byte aligned");
   CLX_REQUIRE(out != marker && out != image && (const void*)out != (const void*)mask, "clx_grey_reconstruct: out must not alias an input");
-  const long long npix = (long long)Z * Y * X;
   hipStream_t st = (hipStream_t)stream;
   const TileGrid g = tile_grid<ReconShape<2>, ReconShape<3>>(nd, Z, Y, X);
   Planes q;
   q.out = out;
-  q.head = (int*)workspace;
-  q.counters = q.head + HEAD_WORDS;
-  q.wout = q.counters + MAX_ROUNDS;
-  q.flag0 = (unsigned char*)(q.wout + npix);
-  q.flag1 = q.flag0 + flag_bytes(g.ntiles);
-  q.image = (unsigned short*)(q.flag1 + flag_bytes(g.ntiles));
-  CLX_REQUIRE(hipMemsetAsync(info, 0, 3 * sizeof(int), st) == hipSuccess, "clx_grey_reconstruct: hipMemsetAsync failed");
-  CLX_REQUIRE(hipMemsetAsync(q.counters, 0, MAX_ROUNDS * sizeof(int), st) == hipSuccess, "clx_grey_reconstruct: hipMemsetAsync failed");
-  if (!resume) {
-    const long long blocks = (npix + BLOCK - 1) / BLOCK;
-    reconstruct_init<<<(int)(blocks < INIT_MAX_GRID ? blocks : INIT_MAX_GRID), BLOCK, 0, st>>>(marker, image, mask, q, npix, info);
-  }
-  const int grid = (int)(g.ntiles < TILE_MAX_GRID ? g.ntiles : TILE_MAX_GRID);
+  q.wout = rounds_carve(q.w, workspace);
+  q.image = (unsigned short*)rounds_carve_flags(q.w, q.wout + npix, g);
+  CLX_REQUIRE(rounds_begin(q.w, info, st), "clx_grey_reconstruct: hipMemsetAsync failed");
+  if (!resume) reconstruct_init<<<init_grid(npix), BLOCK, 0, st>>>(marker, image, mask, q, npix, info);
+  const int grid = round_grid(g);
   for (int k = 0; k < rounds; ++k) {
     if (nd == 2) reconstruct_round<2><<<grid, BLOCK, 0, st>>>(q, k, Z, Y, X, g);
     else reconstruct_round<3><<<grid, BLOCK, 0, st>>>(q, k, Z, Y, X, g);
   }
-  reconstruct_finish<<<1, 64, 0, st>>>(q.head, q.counters, rounds, info);
+  rounds_end(q.w, rounds, info, st);
   CLX_CHECK_LAUNCH("clx_grey_reconstruct");
   return CLX_OK;
 }

@@ -218,20 +218,6 @@ __global__ __launch_bounds__(BLOCK) void relabel_kernel(const unsigned int* __re
   if (flags) atomicOr(bad, flags);
 }
 
-struct MapShape {
-  long long npix;
-  bool ok;
-};
-// the checks on nd, Z, Y, X the three entry points share; `who` prefixes the message
-inline MapShape map_shape(int nd, int Z, int Y, int X, const char* who) {
-  if (nd != 2 && nd != 3) { clx_set_error("%s: nd must be 2 or 3", who); return {0, false}; }
-  if (Z <= 0 || Y <= 0 || X <= 0) { clx_set_error("%s: bad shape", who); return {0, false}; }
-  if (nd == 2 && Z != 1) { clx_set_error("%s: nd == 2 needs Z == 1", who); return {0, false}; }
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  if (npix128 >= ((unsigned __int128)1 << 32)) { clx_set_error("%s: Z * Y * X must be below 2^32", who); return {0, false}; }
-  return {(long long)npix128, true};
-}
-
 }  // namespace
 
 extern "C" size_t clx_label_basins_workspace(long long npix) {
@@ -243,10 +229,9 @@ extern "C" int clx_label_basins(const int32_t* labels, const int32_t* dist_sq, i
                                 int32_t* root, int32_t* summits, int32_t* info, void* workspace, size_t workspace_bytes,
                                 clx_stream stream) {
   CLX_REQUIRE(labels && dist_sq && root && summits && info && workspace, "clx_label_basins: null pointer");
-  const MapShape shape = map_shape(nd, Z, Y, X, "clx_label_basins");
-  if (!shape.ok) return CLX_ERR_ARG;
+  CLX_REQUIRE_MAP(npix, "clx_label_basins", nd, Z, Y, X, 32);
   CLX_REQUIRE(capacity >= 1 && capacity <= (1 << 30), "clx_label_basins: capacity must lie in [1, 2^30]");
-  CLX_REQUIRE(workspace_bytes >= clx_label_basins_workspace(shape.npix),
+  CLX_REQUIRE(workspace_bytes >= clx_label_basins_workspace(npix),
               "clx_label_basins: workspace_bytes is below clx_label_basins_workspace(Z * Y * X)");
   CLX_REQUIRE(((uintptr_t)workspace & 3) == 0, "clx_label_basins: workspace must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
@@ -254,14 +239,14 @@ extern "C" int clx_label_basins(const int32_t* labels, const int32_t* dist_sq, i
   unsigned int* other = (unsigned int*)(status + STATUS_WORDS);
   CLX_REQUIRE(hipMemsetAsync(status, 0, STATUS_WORDS * sizeof(int), st) == hipSuccess, "clx_label_basins: hipMemsetAsync failed");
   CLX_REQUIRE(hipMemsetAsync(info, 0, 2 * sizeof(int), st) == hipSuccess, "clx_label_basins: hipMemsetAsync failed");
-  const Tiling t = tiling_for(shape.npix);
+  const Tiling t = tiling_for(npix);
   ascent_kernel<<<t.grid, BLOCK, 0, st>>>(labels, dist_sq, other, (unsigned int*)summits, (unsigned int)capacity, (unsigned int*)info,
-                                          nd == 3, Z, Y, X, shape.npix, t.ntiles, t.per_block);
-  const int grid = map_grid(shape.npix);
+                                          nd == 3, Z, Y, X, npix, t.ntiles, t.per_block);
+  const int grid = map_grid(npix);
   for (int k = 1; k <= ROOT_LAUNCHES; ++k) {              // odd launches: workspace -> root; even ones: root -> workspace
     const bool to_root = k & 1;
     root_kernel<<<grid, BLOCK, 0, st>>>(to_root ? other : (const unsigned int*)root, to_root ? (unsigned int*)root : other,
-                                        k == 1 ? nullptr : status + k - 1, status + k, !to_root, shape.npix);
+                                        k == 1 ? nullptr : status + k - 1, status + k, !to_root, npix);
   }
   CLX_CHECK_LAUNCH("clx_label_basins");
   return CLX_OK;
@@ -271,15 +256,14 @@ extern "C" int clx_basin_passes(const int32_t* labels, const int32_t* dist_sq, c
                                 int capacity, unsigned long long* keys, unsigned long long* values, int32_t* info,
                                 clx_stream stream) {
   CLX_REQUIRE(labels && dist_sq && root && keys && values && info, "clx_basin_passes: null pointer");
-  const MapShape shape = map_shape(nd, Z, Y, X, "clx_basin_passes");
-  if (!shape.ok) return CLX_ERR_ARG;
+  CLX_REQUIRE_MAP(npix, "clx_basin_passes", nd, Z, Y, X, 32);
   CLX_REQUIRE(capacity >= 1024 && capacity <= (1 << 28) && (capacity & (capacity - 1)) == 0,
               "clx_basin_passes: capacity must be a power of two in [1024, 2^28]");
   hipStream_t st = (hipStream_t)stream;
   const ContactsOut o = contacts_out(keys, values, info, capacity);
   contacts_init<<<(capacity + 255) / 256, 256, 0, st>>>(o, capacity);
-  const Tiling t = tiling_for(shape.npix);
-  passes_kernel<<<t.grid, BLOCK, 0, st>>>(labels, dist_sq, (const unsigned int*)root, nd == 3, Z, Y, X, shape.npix, t.ntiles,
+  const Tiling t = tiling_for(npix);
+  passes_kernel<<<t.grid, BLOCK, 0, st>>>(labels, dist_sq, (const unsigned int*)root, nd == 3, Z, Y, X, npix, t.ntiles,
                                           t.per_block, o);
   CLX_CHECK_LAUNCH("clx_basin_passes");
   return CLX_OK;

@@ -179,13 +179,8 @@ extern "C" size_t clx_label_distance_workspace(long long npix) {
 extern "C" int clx_label_distance_sq(const int32_t* labels, int nd, int Z, int Y, int X, int edge, int32_t* dist_sq,
                                      void* workspace, size_t workspace_bytes, clx_stream stream) {
   CLX_REQUIRE(labels && dist_sq && workspace, "clx_label_distance_sq: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_label_distance_sq: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_label_distance_sq: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_label_distance_sq: nd == 2 needs Z == 1");
+  CLX_REQUIRE_MAP(npix, "clx_label_distance_sq", nd, Z, Y, X, 32);
   CLX_REQUIRE(edge == 0 || edge == 1, "clx_label_distance_sq: edge must be 0 or 1");
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_label_distance_sq: Z * Y * X must be below 2^32");
-  const long long npix = (long long)npix128;
   const long long dz = Z - 1, dy = Y - 1, dx = X - 1;
   CLX_REQUIRE(dz * dz + dy * dy + dx * dx < (long long)CLX_DIST_INF,
               "clx_label_distance_sq: (Z-1)^2 + (Y-1)^2 + (X-1)^2 must be below 2^30 (a finite distance stays below CLX_DIST_INF)");

@@ -266,19 +266,11 @@ __global__ __launch_bounds__(BLOCK) void holes_fill(const int* __restrict__ labe
   }
 }
 
-inline bool holes_shape(int nd, int Z, int Y, int X, long long* npix) {
-  if ((nd != 2 && nd != 3) || Z <= 0 || Y <= 0 || X <= 0 || (nd == 2 && Z != 1)) return false;
-  const unsigned __int128 n = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  if (n >= ((unsigned __int128)1 << 31)) return false;
-  *npix = (long long)n;
-  return true;
-}
-
 }  // namespace
 
 extern "C" size_t clx_label_holes_workspace(int nd, int Z, int Y, int X) {
   long long npix;
-  if (!holes_shape(nd, Z, Y, X, &npix)) return 0;
+  if (clx_map_shape(nullptr, nd, Z, Y, X, 31, &npix) != CLX_OK) return 0;
   return (size_t)npix * 4 * sizeof(int);        // parent | area and border bit | smallest | largest neighbour value
 }
 
@@ -287,12 +279,8 @@ extern "C" int clx_label_holes(const int32_t* labels, int nd, int Z, int Y, int 
   CLX_REQUIRE(labels && out && info && workspace, "clx_label_holes: null pointer");
   CLX_REQUIRE(capacity >= 0, "clx_label_holes: capacity must be >= 0");
   CLX_REQUIRE(holes || capacity == 0, "clx_label_holes: null holes with capacity > 0");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_label_holes: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_label_holes: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_label_holes: nd == 2 needs Z == 1");
+  CLX_REQUIRE_MAP(npix, "clx_label_holes", nd, Z, Y, X, 31);
   CLX_REQUIRE(planewise == 0 || (planewise == 1 && nd == 3), "clx_label_holes: planewise must be 0, or 1 with nd == 3");
-  long long npix = 0;
-  CLX_REQUIRE(holes_shape(nd, Z, Y, X, &npix), "clx_label_holes: Z * Y * X must be below 2^31");
   CLX_REQUIRE(max_size >= -1, "clx_label_holes: max_size must be >= -1");
   CLX_REQUIRE(workspace_bytes >= clx_label_holes_workspace(nd, Z, Y, X),
               "clx_label_holes: workspace_bytes is below clx_label_holes_workspace(nd, Z, Y, X)");

@@ -13,48 +13,21 @@
 //              sweeps between two LDS buffers of whole 64-bit keys -- a key is never torn -- until a sweep changes nothing, at
 //              most MAX_SWEEPS of them (a tile cut short has changed and is taken up again in the next round), and writes its
 //              interior.  No block waits for another: the halo is what the round before left.
-//   ping-pong  between rounds a key lies in two int32 planes; round r reads (owner, cost) and writes the workspace's pair if r
-//              is even, the other way round if odd: no launch reads a word it writes, and the state after round r is a
-//              function of the inputs.  r counts over all calls since resume == 0 and lies in the workspace's head.
-//   activity   a tile has a changed flag per round, in two arrays that alternate like the planes.  A tile is ACTIVE in round
-//              r iff it or one of its 8 / 26 neighbour tiles changed in round r - 1 (round 0: all are).  An active tile always
-//              writes its interior; an inactive one clears its flag and is done.  An inactive tile would not have changed: its
-//              keys and its halo are those of the round in which it last came to rest.  By induction it holds equal values in
-//              both pairs of planes: active and unchanged in round r - 1 it wrote what it read, inactive it had them already.
-//              So when a round changes no tile both pairs are equal everywhere and hold the fixed point.
-//   counters   a word per round of the call counts the tiles that changed in it; a launch that finds 0 in the word of the
-//              round before returns at once, as do all after it.  The last launch of a call forms info from the counters and
-//              leaves r and the last count in the head for a call with resume == 1.
+//   planes     between rounds a key lies in two int32 planes; round r reads (owner, cost) and writes the workspace's pair if r
+//              is even, the other way round if odd.  The rounds are queued, tiles at rest skipped and the call ended as
+//              tile_rounds.h says, where the proof stands that a skipped tile would not have changed.
 // Integers only, and minima: the same bits and the same rounds in every run.  cost <= 2^30 and a step < 2^19, so a candidate
 // fits 32 bits; one above the limit can only grow and is dropped where it arises.  Ids are only compared, never an index.
-#include "region_scan.h"
+#include "tile_rounds.h"
 
 namespace {
 
 constexpr unsigned int COST_INF = (unsigned int)CLX_COST_INF;
-constexpr int TILE_MAX_GRID = 1024;     // blocks a round; each takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
-constexpr int INIT_MAX_GRID = 4096;     // blocks of BLOCK pixels a trip (the first call's start values)
 constexpr int MAX_SWEEPS = 32;          // Jacobi sweeps a tile makes in LDS in one round
-constexpr int MAX_ROUNDS = 64;          // launches a call queues at most: the counters of a call
-constexpr int HEAD_WORDS = 16;          // [0] rounds so far, [1] the tiles that changed in the last of them (or 1: none yet)
 
 template <int ND> struct TileShape;
 template <> struct TileShape<2> { static constexpr int TZ = 1, TY = 16, TX = 64, ZH = 0; };
 template <> struct TileShape<3> { static constexpr int TZ = 8, TY = 8, TX = 16, ZH = 1; };
-
-struct TileGrid {
-  int ntz, nty, ntx;
-  long long ntiles;
-};
-inline TileGrid tile_grid(int nd, int Z, int Y, int X) {
-  TileGrid g;
-  g.ntz = nd == 2 ? 1 : (Z + TileShape<3>::TZ - 1) / TileShape<3>::TZ;
-  g.nty = nd == 2 ? (Y + TileShape<2>::TY - 1) / TileShape<2>::TY : (Y + TileShape<3>::TY - 1) / TileShape<3>::TY;
-  g.ntx = nd == 2 ? (X + TileShape<2>::TX - 1) / TileShape<2>::TX : (X + TileShape<3>::TX - 1) / TileShape<3>::TX;
-  g.ntiles = (long long)g.ntz * g.nty * g.ntx;
-  return g;
-}
-inline size_t flag_bytes(long long ntiles) { return ((size_t)ntiles + 3) & ~(size_t)3; }
 
 // the planes, the flags and the words of the workspace
 struct Planes {
@@ -65,10 +38,7 @@ struct Planes {
   int* cost;
   int* wowner;
   int* wcost;
-  unsigned char* flag0;                 // written by the even rounds
-  unsigned char* flag1;
-  int* head;
-  int* counters;
+  Rounds w;
 };
 
 __global__ __launch_bounds__(BLOCK) void propagate_init(Planes q, long long npix, int nid, int* __restrict__ info) {
@@ -83,7 +53,7 @@ __global__ __launch_bounds__(BLOCK) void propagate_init(Planes q, long long npix
     q.owner[p] = source ? s : 0;
     q.cost[p] = source ? 0 : (int)COST_INF;
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) { q.head[0] = 0; q.head[1] = 1; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) rounds_reset(q.w);
   if (flags) atomicOr(info, flags);
 }
 
@@ -93,20 +63,16 @@ __global__ __launch_bounds__(BLOCK) void propagate_round(Planes q, int k, int Z,
                                                          unsigned int limit) {
   typedef TileShape<ND> S;
   constexpr int HX = S::TX + 2, HY = S::TY + 2, HZ = S::TZ + 2 * S::ZH, HN = HX * HY * HZ;
-  constexpr int NTILES_AROUND = ND == 2 ? 9 : 27;
   __shared__ u64 keys[2][HN];
   __shared__ unsigned short wl[HN];
   __shared__ unsigned char ent[HN];
 
-  if ((k == 0 ? q.head[1] : q.counters[k - 1]) == 0) return;        // the round before changed no tile: the fixed point is reached
-  const unsigned int r = (unsigned int)q.head[0] + (unsigned int)k;
-  const bool odd = r & 1u;
-  const int* __restrict__ sid = odd ? q.wowner : q.owner;
-  const int* __restrict__ scost = odd ? q.wcost : q.cost;
-  int* __restrict__ did = odd ? q.owner : q.wowner;
-  int* __restrict__ dcost = odd ? q.cost : q.wcost;
-  const unsigned char* __restrict__ fin = odd ? q.flag0 : q.flag1;
-  unsigned char* __restrict__ fout = odd ? q.flag1 : q.flag0;
+  Round rd;
+  if (!open_round(q.w, k, rd)) return;
+  const int* __restrict__ sid = rd.odd ? q.wowner : q.owner;
+  const int* __restrict__ scost = rd.odd ? q.wcost : q.cost;
+  int* __restrict__ did = rd.odd ? q.owner : q.wowner;
+  int* __restrict__ dcost = rd.odd ? q.cost : q.wcost;
 
   // a thread's 4 pixels of the interior, BLOCK apart: consecutive lanes consecutive in x
   int li[4], iz[4], iy[4], ix[4];
@@ -121,17 +87,7 @@ __global__ __launch_bounds__(BLOCK) void propagate_round(Planes q, int k, int Z,
 
   for (long long t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
     const int tx = (int)(t % g.ntx), ty = (int)((t / g.ntx) % g.nty), tz = (int)(t / ((long long)g.ntx * g.nty));
-    int active = r == 0;
-    if (r != 0 && threadIdx.x < NTILES_AROUND) {
-      const int i = threadIdx.x;
-      const int nx = tx + i % 3 - 1, ny = ty + (i / 3) % 3 - 1, nz = tz + i / 9 - (ND == 2 ? 0 : 1);
-      if ((unsigned int)nx < (unsigned int)g.ntx && (unsigned int)ny < (unsigned int)g.nty && (unsigned int)nz < (unsigned int)g.ntz)
-        active = fin[((long long)nz * g.nty + ny) * g.ntx + nx];
-    }
-    if (!__syncthreads_or(active)) {                      // the barrier also ends the reads of the tile before
-      if (threadIdx.x == 0) fout[t] = 0;
-      continue;
-    }
+    if (!tile_active<ND>(rd, g.ntz, g.nty, g.ntx, t, tz, ty, tx)) continue;
 
     const int z0 = tz * S::TZ - S::ZH, y0 = ty * S::TY - 1, x0 = tx * S::TX - 1;
     for (int i = threadIdx.x; i < HN; i += BLOCK) {
@@ -212,80 +168,52 @@ __global__ __launch_bounds__(BLOCK) void propagate_round(Planes q, int k, int Z,
         dcost[p] = (int)(unsigned int)(key >> 32);
       }
     }
-    if (threadIdx.x == 0) {
-      fout[t] = (unsigned char)tile_changed;
-      if (tile_changed) atomicAdd(q.counters + k, 1);
-    }
+    close_tile(q.w, rd, k, t, tile_changed);
   }
-}
-
-// the last launch of a call: info from the counters, and the head for the next call
-__global__ void propagate_finish(int* __restrict__ head, const int* __restrict__ counters, int rounds, int* __restrict__ info) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  int busy = 0;
-  for (int k = 0; k < MAX_ROUNDS; ++k)
-    if (k < rounds && counters[k] != 0) ++busy;
-  info[1] = counters[rounds - 1];
-  info[2] = busy;
-  head[0] = (int)((unsigned int)head[0] + (unsigned int)rounds);
-  head[1] = counters[rounds - 1];
 }
 
 }  // namespace
 
 extern "C" size_t clx_label_propagate_workspace(int nd, int Z, int Y, int X) {
-  if ((nd != 2 && nd != 3) || Z <= 0 || Y <= 0 || X <= 0 || (nd == 2 && Z != 1)) return 0;
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  if (npix128 >= ((unsigned __int128)1 << 32)) return 0;
-  const TileGrid g = tile_grid(nd, Z, Y, X);
-  return (size_t)(HEAD_WORDS + MAX_ROUNDS) * sizeof(int) + (size_t)npix128 * 2 * sizeof(int) + 2 * flag_bytes(g.ntiles);
+  long long npix;
+  if (clx_map_shape(nullptr, nd, Z, Y, X, 32, &npix) != CLX_OK) return 0;
+  const TileGrid g = tile_grid<TileShape<2>, TileShape<3>>(nd, Z, Y, X);
+  return ROUNDS_HEAD_BYTES + (size_t)npix * 2 * sizeof(int) + 2 * flag_bytes(g.ntiles);
 }
 
 extern "C" int clx_label_propagate(const int32_t* seeds, const uint8_t* mask, const int32_t* weight, int nd, int Z, int Y, int X,
                                    int nid, int reg, int limit, int rounds, int resume, int32_t* owner, int32_t* cost, int32_t* info,
                                    void* workspace, size_t workspace_bytes, clx_stream stream) {
   CLX_REQUIRE(seeds && owner && cost && info && workspace, "clx_label_propagate: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_label_propagate: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_label_propagate: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_label_propagate: nd == 2 needs Z == 1");
+  CLX_REQUIRE_MAP(npix, "clx_label_propagate", nd, Z, Y, X, 32);
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_label_propagate: nid must lie in [1, 2^24]");
   CLX_REQUIRE(reg >= 0 && reg <= 65535, "clx_label_propagate: reg must lie in [0, 65535]");
   CLX_REQUIRE(limit >= -1 && limit < CLX_COST_INF, "clx_label_propagate: limit must lie in [-1, 2^30)");
   CLX_REQUIRE(rounds >= 1 && rounds <= MAX_ROUNDS, "clx_label_propagate: rounds must lie in [1, 64]");
   CLX_REQUIRE(resume == 0 || resume == 1, "clx_label_propagate: resume must be 0 or 1");
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_label_propagate: Z * Y * X must be below 2^32");
-  const long long npix = (long long)npix128;
   CLX_REQUIRE(workspace_bytes >= clx_label_propagate_workspace(nd, Z, Y, X),
               "clx_label_propagate: workspace_bytes is below clx_label_propagate_workspace(nd, Z, Y, X)");
   CLX_REQUIRE(((uintptr_t)workspace & 3) == 0, "clx_label_propagate: workspace must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const TileGrid g = tile_grid(nd, Z, Y, X);
+  const TileGrid g = tile_grid<TileShape<2>, TileShape<3>>(nd, Z, Y, X);
   Planes q;
   q.seeds = seeds;
   q.mask = mask;
   q.weight = weight;
   q.owner = owner;
   q.cost = cost;
-  q.head = (int*)workspace;
-  q.counters = q.head + HEAD_WORDS;
-  q.wowner = q.counters + MAX_ROUNDS;
+  q.wowner = rounds_carve(q.w, workspace);
   q.wcost = q.wowner + npix;
-  q.flag0 = (unsigned char*)(q.wcost + npix);
-  q.flag1 = q.flag0 + flag_bytes(g.ntiles);
-  CLX_REQUIRE(hipMemsetAsync(info, 0, 3 * sizeof(int), st) == hipSuccess, "clx_label_propagate: hipMemsetAsync failed");
-  CLX_REQUIRE(hipMemsetAsync(q.counters, 0, MAX_ROUNDS * sizeof(int), st) == hipSuccess, "clx_label_propagate: hipMemsetAsync failed");
-  if (!resume) {
-    const long long blocks = (npix + BLOCK - 1) / BLOCK;
-    propagate_init<<<(int)(blocks < INIT_MAX_GRID ? blocks : INIT_MAX_GRID), BLOCK, 0, st>>>(q, npix, nid, info);
-  }
-  const int grid = (int)(g.ntiles < TILE_MAX_GRID ? g.ntiles : TILE_MAX_GRID);
+  rounds_carve_flags(q.w, q.wcost + npix, g);
+  CLX_REQUIRE(rounds_begin(q.w, info, st), "clx_label_propagate: hipMemsetAsync failed");
+  if (!resume) propagate_init<<<init_grid(npix), BLOCK, 0, st>>>(q, npix, nid, info);
+  const int grid = round_grid(g);
   const unsigned int lim = limit < 0 ? COST_INF - 1u : (unsigned int)limit;
   for (int k = 0; k < rounds; ++k) {
     if (nd == 2) propagate_round<2><<<grid, BLOCK, 0, st>>>(q, k, Z, Y, X, g, nid, (unsigned int)reg, lim);
     else propagate_round<3><<<grid, BLOCK, 0, st>>>(q, k, Z, Y, X, g, nid, (unsigned int)reg, lim);
   }
-  propagate_finish<<<1, 64, 0, st>>>(q.head, q.counters, rounds, info);
+  rounds_end(q.w, rounds, info, st);
   CLX_CHECK_LAUNCH("clx_label_propagate");
   return CLX_OK;
 }

@@ -22,18 +22,17 @@
 //              the state after launch r is the global synchronous schedule's, whatever the tiles.
 //   ping-pong  launch r (counted over all calls since resume == 0) reads alive plane r & 1 and writes the tile to the other:
 //              no launch reads a word it writes.
-//   activity   a tile has a deleted-something flag per launch, in two arrays that alternate like the planes.  A tile is ACTIVE
-//              in launch r iff it or one of its 8 neighbour tiles of the slice deleted a pixel in launch r - 1 (launch 0: all
-//              are).  The halo reaches into the neighbour tiles only (or beyond the map), so an inactive tile sees the state its
-//              last launch started from, in which a whole iteration deleted nothing in it and around it: it would delete
-//              nothing again.  It clears its flag and is done.  Both planes are equal on it: active and unchanged it wrote
-//              what it read, inactive it had them already.
+//   activity   a tile has a deleted-something flag per launch, and a tile none of whose 9 tiles of the slice deleted a pixel
+//              in the launch before is skipped: tile_rounds.h has the rule and the proof, with "deleted a pixel" for "changed".
+//              It holds here because the halo reaches into the neighbour tiles only (or beyond the map) and a launch runs
+//              whole iterations: an inactive tile sees the state its last launch started from, in which a whole iteration
+//              deleted nothing in it and around it.
 //   counters   two words per launch of a call: the pixels deleted in the launch, and in its last iteration.  A launch that
 //              finds 0 in the second word of the launch before returns at once, as do all after it.  `finish` forms info and
 //              leaves the launch count and the last word in the head for a call with resume == 1; `write` forms out from the
 //              labels and the current plane.
 // Integers only, in fact bits; the labels are compared and never an index.  The same bits in every run.
-#include "region_scan.h"
+#include "tile_rounds.h"
 
 namespace {
 
@@ -47,7 +46,6 @@ constexpr int MAX_ITERATIONS = 64;              // iterations a call queues at m
 constexpr int MAX_LAUNCHES = MAX_ITERATIONS / LAUNCH_ITERATIONS;
 constexpr int THIN_MAX_GRID = 1024;             // blocks a launch; each takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
 constexpr int PLANE_MAX_GRID = 2048;            // blocks of the passes over the words (init, write, census)
-constexpr int HEAD_WORDS = 16;                  // [0] launches so far, [1] pixels deleted in the last iteration (or 1: none yet)
 constexpr int PAD = 16;                         // zero words before and after an LDS buffer: a neighbour is at most 9 words away
 constexpr int NWORDS = 10;                      // words per label of the census
 
@@ -59,7 +57,7 @@ struct Shape {
 };
 
 struct Bits {                                   // the workspace
-  int* head;
+  int* head;                                    // [HEAD_WORDS]: [0] launches so far, [1] pixels the last iteration deleted (or 1)
   int* counters;                                // [MAX_LAUNCHES][2]
   u64* same;                                    // [8][nwords]: N, NE, E, SE, S, SW, W, NW
   u64* alive0;                                  // read by the even launches
@@ -68,19 +66,18 @@ struct Bits {                                   // the workspace
   unsigned char* flag1;
 };
 
-inline bool thin_shape(int nd, int Z, int Y, int X, Shape* s) {
-  if ((nd != 2 && nd != 3) || Z <= 0 || Y <= 0 || X <= 0 || (nd == 2 && Z != 1)) return false;
-  const unsigned __int128 n = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  if (n >= ((unsigned __int128)1 << 31)) return false;
-  s->Z = Z;
-  s->Y = Y;
-  s->X = X;
-  s->W = (X + 63) / 64;
-  s->nwords = (long long)Z * Y * s->W;
-  s->ntx = (s->W + TW - 1) / TW;
-  s->nty = (Y + TR - 1) / TR;
-  s->ntiles = (long long)Z * s->nty * s->ntx;
-  return true;
+// the words and the tiles of a checked map: Z * Y * X < 2^31
+inline Shape thin_shape(int Z, int Y, int X) {
+  Shape s;
+  s.Z = Z;
+  s.Y = Y;
+  s.X = X;
+  s.W = (X + 63) / 64;
+  s.nwords = (long long)Z * Y * s.W;
+  s.ntx = (s.W + TW - 1) / TW;
+  s.nty = (Y + TR - 1) / TR;
+  s.ntiles = (long long)Z * s.nty * s.ntx;
+  return s;
 }
 inline size_t thin_flag_bytes(long long ntiles) { return ((size_t)ntiles + 7) & ~(size_t)7; }
 inline int plane_grid(long long nwords) {
@@ -160,12 +157,9 @@ __global__ __launch_bounds__(BLOCK) void thin_steps(Bits b, int k, int iteration
   __shared__ int sums[2][BLOCK / 64];
 
   if ((k == 0 ? b.head[1] : b.counters[2 * (k - 1) + 1]) == 0) return;       // the iteration before deleted nothing: the fixed point
-  const unsigned int r = (unsigned int)b.head[0] + (unsigned int)k;
-  const bool odd = r & 1u;
-  const u64* __restrict__ src = odd ? b.alive1 : b.alive0;
-  u64* __restrict__ dst = odd ? b.alive0 : b.alive1;
-  const unsigned char* __restrict__ fin = odd ? b.flag0 : b.flag1;
-  unsigned char* __restrict__ fout = odd ? b.flag1 : b.flag0;
+  const Round rd = round_at((unsigned int)b.head[0] + (unsigned int)k, b.flag0, b.flag1);
+  const u64* __restrict__ src = rd.odd ? b.alive1 : b.alive0;
+  u64* __restrict__ dst = rd.odd ? b.alive0 : b.alive1;
 
   if (threadIdx.x < PAD) {
     buf[0][threadIdx.x] = buf[1][threadIdx.x] = 0ull;
@@ -176,18 +170,8 @@ __global__ __launch_bounds__(BLOCK) void thin_steps(Bits b, int k, int iteration
   int total = 0, last = 0;                                                  // pixels this thread deleted in tiles: all, last iteration
 
   for (long long t = blockIdx.x; t < s.ntiles; t += gridDim.x) {
-    const int tx = (int)(t % s.ntx), ty = (int)((t / s.ntx) % s.nty);
-    const long long tz = t / ((long long)s.ntx * s.nty);
-    int active = r == 0;
-    if (r != 0 && threadIdx.x < 9) {
-      const int nx = tx + (int)threadIdx.x % 3 - 1, ny = ty + (int)threadIdx.x / 3 - 1;
-      if ((unsigned int)nx < (unsigned int)s.ntx && (unsigned int)ny < (unsigned int)s.nty)
-        active = fin[(tz * s.nty + ny) * s.ntx + nx];
-    }
-    if (!__syncthreads_or(active)) {                    // the barrier also ends the reads of the tile before
-      if (threadIdx.x == 0) fout[t] = 0;
-      continue;
-    }
+    const int tx = (int)(t % s.ntx), ty = (int)((t / s.ntx) % s.nty), tz = (int)(t / ((long long)s.ntx * s.nty));
+    if (!tile_active<2>(rd, s.Z, s.nty, s.ntx, t, tz, ty, tx)) continue;      // the slice stands for the tile's z
 
     const int wc = tx * TW - HALO_W + c;
     u64 same[WPT][8];
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(BLOCK) void thin_steps(Bits b, int k, int iteration
       const int er = er0 + m * (BLOCK / EW);
       const int y = ty * TR - HALO_R + er;
       const bool in = (unsigned int)wc < (unsigned int)s.W && (unsigned int)y < (unsigned int)s.Y;
-      gw[m] = (tz * s.Y + y) * s.W + wc;
+      gw[m] = ((long long)tz * s.Y + y) * s.W + wc;
       mine[m] = in && cin && er >= HALO_R && er < ER - HALO_R;
       const u64 a = in ? src[gw[m]] : 0ull;
       buf[0][PAD + threadIdx.x + m * BLOCK] = a;
@@ -234,7 +218,7 @@ __global__ __launch_bounds__(BLOCK) void thin_steps(Bits b, int k, int iteration
       if (mine[m]) dst[gw[m]] = buf[cur][PAD + threadIdx.x + m * BLOCK];
     total += tile_total;
     const int changed = __syncthreads_or(tile_total);   // the barrier also ends the reads of this tile
-    if (threadIdx.x == 0) fout[t] = (unsigned char)(changed != 0);
+    if (threadIdx.x == 0) rd.fout[t] = (unsigned char)(changed != 0);
   }
 
 #pragma unroll
@@ -385,19 +369,17 @@ __global__ __launch_bounds__(BLOCK) void census_kernel(const int* __restrict__ l
 }  // namespace
 
 extern "C" size_t clx_label_thin_workspace(int nd, int Z, int Y, int X) {
-  Shape s;
-  if (!thin_shape(nd, Z, Y, X, &s)) return 0;
+  long long npix;
+  if (clx_map_shape(nullptr, nd, Z, Y, X, 31, &npix) != CLX_OK) return 0;
+  const Shape s = thin_shape(Z, Y, X);
   return (size_t)(HEAD_WORDS + 2 * MAX_LAUNCHES) * sizeof(int) + (size_t)s.nwords * 10 * sizeof(u64) + 2 * thin_flag_bytes(s.ntiles);
 }
 
 extern "C" int clx_label_thin(const int32_t* labels, int nd, int Z, int Y, int X, int iterations, int resume, int32_t* out,
                               int32_t* info, void* workspace, size_t workspace_bytes, clx_stream stream) {
   CLX_REQUIRE(labels && out && info && workspace, "clx_label_thin: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_label_thin: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_label_thin: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_label_thin: nd == 2 needs Z == 1");
-  Shape s;
-  CLX_REQUIRE(thin_shape(nd, Z, Y, X, &s), "clx_label_thin: Z * Y * X must be below 2^31");
+  CLX_REQUIRE_MAP(npix, "clx_label_thin", nd, Z, Y, X, 31);
+  const Shape s = thin_shape(Z, Y, X);
   CLX_REQUIRE(iterations >= 1 && iterations <= MAX_ITERATIONS, "clx_label_thin: iterations must lie in [1, 64]");
   CLX_REQUIRE(resume == 0 || resume == 1, "clx_label_thin: resume must be 0 or 1");
   CLX_REQUIRE(workspace_bytes >= clx_label_thin_workspace(nd, Z, Y, X),
@@ -432,11 +414,8 @@ extern "C" int clx_label_thin(const int32_t* labels, int nd, int Z, int Y, int X
 extern "C" int clx_skeleton_census(const int32_t* skeleton, const int32_t* dist_sq, int nd, int Z, int Y, int X, int nid,
                                    long long* words, int32_t* bad, clx_stream stream) {
   CLX_REQUIRE(skeleton && words && bad, "clx_skeleton_census: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_skeleton_census: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_skeleton_census: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_skeleton_census: nd == 2 needs Z == 1");
-  Shape s;
-  CLX_REQUIRE(thin_shape(nd, Z, Y, X, &s), "clx_skeleton_census: Z * Y * X must be below 2^31");
+  CLX_REQUIRE_MAP(npix, "clx_skeleton_census", nd, Z, Y, X, 31);
+  const Shape s = thin_shape(Z, Y, X);
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_skeleton_census: nid must lie in [1, 2^24]");
   hipStream_t st = (hipStream_t)stream;
   const long long cells = (long long)nid * NWORDS, blocks = (cells + 255) / 256;

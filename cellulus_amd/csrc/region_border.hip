@@ -191,13 +191,8 @@ extern "C" int clx_region_border_intensity(const int32_t* labels, const void* ra
   const char* who = "clx_region_border_intensity";
   CLX_REQUIRE(labels && raw && out && bad, "%s: null pointer", who);
   CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "%s: raw_type must be 0 (f32), 1 (f64) or 2 (i32)", who);
-  CLX_REQUIRE(nd == 2 || nd == 3, "%s: nd must be 2 or 3", who);
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "%s: bad shape", who);
-  CLX_REQUIRE(nd == 3 || Z == 1, "%s: nd == 2 needs Z == 1", who);
+  CLX_REQUIRE_MAP(npix, who, nd, Z, Y, X, 32);
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "%s: nid must lie in [1, 2^24]", who);
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "%s: Z * Y * X must be below 2^32", who);
-  const long long npix = (long long)npix128;
   hipStream_t st = (hipStream_t)stream;
   const Tiling t = tiling_for(npix);
   BorderArgs a;

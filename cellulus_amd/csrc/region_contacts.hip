@@ -118,15 +118,10 @@ __global__ __launch_bounds__(BLOCK) void contacts_kernel(const int* __restrict__
 extern "C" int clx_region_contacts(const int32_t* labels, int nd, int Z, int Y, int X, int nid, int capacity,
                                    unsigned long long* keys, unsigned long long* counts, int32_t* info, clx_stream stream) {
   CLX_REQUIRE(labels && keys && counts && info, "clx_region_contacts: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_region_contacts: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_region_contacts: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_region_contacts: nd == 2 needs Z == 1");
+  CLX_REQUIRE_MAP(npix, "clx_region_contacts", nd, Z, Y, X, 32);
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_region_contacts: nid must lie in [1, 2^24]");
   CLX_REQUIRE(capacity >= 1024 && capacity <= (1 << 28) && (capacity & (capacity - 1)) == 0,
               "clx_region_contacts: capacity must be a power of two in [1024, 2^28]");
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_region_contacts: Z * Y * X must be below 2^32");
-  const long long npix = (long long)npix128;
   hipStream_t st = (hipStream_t)stream;
   const ContactsOut o = contacts_out(keys, counts, info, capacity);
   contacts_init<<<(capacity + 255) / 256, 256, 0, st>>>(o, capacity);

@@ -266,13 +266,9 @@ extern "C" int clx_region_hull(const int32_t* labels, int nd, int Z, int Y, int 
                                const long long* row_base, long long rows, void* workspace, size_t workspace_bytes,
                                long long* hull, int32_t* bad, clx_stream stream) {
   CLX_REQUIRE(labels && bbox && row_base && workspace && hull && bad, "clx_region_hull: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_region_hull: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_region_hull: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_region_hull: nd == 2 needs Z == 1");
+  CLX_REQUIRE_MAP(npix, "clx_region_hull", nd, Z, Y, X, 32);
   CLX_REQUIRE(Z < (1 << 30) && Y < (1 << 30) && X < (1 << 30), "clx_region_hull: Z, Y and X must be below 2^30 (F2 is 64-bit)");
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_region_hull: nid must lie in [1, 2^24]");
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_region_hull: Z * Y * X must be below 2^32");
   CLX_REQUIRE(nd == 3 || ((long long)Y + 1) * ((long long)X + 1) <= (1ll << 31),
               "clx_region_hull: nd == 2 needs (Y + 1) * (X + 1) <= 2^31 (C^2 is 64-bit)");
   // an id has at most Z * Y rows
@@ -280,7 +276,6 @@ extern "C" int clx_region_hull(const int32_t* labels, int nd, int Z, int Y, int 
   CLX_REQUIRE(workspace_bytes >= clx_region_hull_workspace(rows),
               "clx_region_hull: workspace_bytes is below clx_region_hull_workspace(rows)");
   CLX_REQUIRE(((uintptr_t)workspace & 7) == 0, "clx_region_hull: workspace must be 8-byte aligned");
-  const long long npix = (long long)npix128;
   hipStream_t st = (hipStream_t)stream;
   int* ws = (int*)workspace;
   const HullWs w = {ws, ws + rows, ws + 2 * rows, ws + 4 * rows};

@@ -249,9 +249,8 @@ extern "C" int clx_region_moments(const int32_t* labels, int Z, int Y, int X, in
   CLX_REQUIRE(labels && area && bbox && sum1 && sum2 && bad, "clx_region_moments: null pointer");
   CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_region_moments: bad shape");
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_region_moments: nid must lie in [1, 2^24]");
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_region_moments: Z * Y * X must be below 2^32");
-  const long long npix = (long long)npix128;
+  long long npix = 0;
+  if (clx_map_bound("clx_region_moments", Z, Y, X, 32, &npix) != CLX_OK) return CLX_ERR_ARG;
   const unsigned long long m = (unsigned long long)((Z > Y ? (Z > X ? Z : X) : (Y > X ? Y : X)) - 1);
   CLX_REQUIRE((unsigned __int128)(m * m) * (unsigned __int128)npix < ((unsigned __int128)1 << 63),
               "clx_region_moments: (largest extent - 1)^2 * Z * Y * X must be below 2^63 (the second moments are 64-bit)");

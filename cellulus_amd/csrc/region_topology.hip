@@ -293,13 +293,8 @@ __global__ __launch_bounds__(BLOCK) void topology_kernel(const int* __restrict__
 extern "C" int clx_region_topology(const int32_t* labels, int nd, int Z, int Y, int X, int nid, long long* counts, int32_t* bad,
                                    clx_stream stream) {
   CLX_REQUIRE(labels && counts && bad, "clx_region_topology: null pointer");
-  CLX_REQUIRE(nd == 2 || nd == 3, "clx_region_topology: nd must be 2 or 3");
-  CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "clx_region_topology: bad shape");
-  CLX_REQUIRE(nd == 3 || Z == 1, "clx_region_topology: nd == 2 needs Z == 1");
+  CLX_REQUIRE_MAP(npix, "clx_region_topology", nd, Z, Y, X, 32);
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_region_topology: nid must lie in [1, 2^24]");
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "clx_region_topology: Z * Y * X must be below 2^32");
-  const long long npix = (long long)npix128;
   hipStream_t st = (hipStream_t)stream;
   topology_init<<<(nid + 255) / 256, 256, 0, st>>>(counts, bad, nid);
   const Tiling t = tiling_for(npix);

@@ -270,9 +270,8 @@ extern "C" int clx_region_weighted(const int32_t* labels, const void* raw, int r
   CLX_REQUIRE(labels && raw && out && bad, "%s: null pointer", who);
   if (require_raw_channel(who, raw_type, nid) != CLX_OK) return CLX_ERR_ARG;
   CLX_REQUIRE(Z > 0 && Y > 0 && X > 0, "%s: bad shape", who);
-  const unsigned __int128 npix128 = (unsigned __int128)Z * (unsigned)Y * (unsigned)X;
-  CLX_REQUIRE(npix128 < ((unsigned __int128)1 << 32), "%s: Z * Y * X must be below 2^32", who);
-  const long long npix = (long long)npix128;
+  long long npix = 0;
+  if (clx_map_bound(who, Z, Y, X, 32, &npix) != CLX_OK) return CLX_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const Tiling t = tiling_for(npix, Z > 1 ? GRID_3D : MAX_GRID);
   WeightedArgs a;

@@ -37,13 +37,13 @@ import numpy as np
 import torch
 
 from . import _clx, _stage
-from .measure import FLAGS, LABELS_CHANGED, _check_map, _in_type_of, _resolve_device, _scene, _Scene, _workspace
+from .measure import (FLAGS, LABELS_CHANGED, ROUNDS_PER_CALL, _check_map, _device_mask, _in_type_of, _resolve_device, _scene, _Scene,
+                      _settle, _workspace)
 from .measure_columns import _exact_div
 from .propagate import image_levels
 
 MAX_LEVEL = 65535                       # clx_grey_morph / clx_grey_reconstruct: values lie in [0, 65535]
 MORPH_STEPS = {2: 16, 3: 4}             # clx_grey_morph: the steps of one call, by the map's dimensions
-ROUNDS_PER_CALL = 8                     # reconstruction rounds queued between two looks at info[1]
 MAX_SCALES, MAX_BACKGROUND = 64, 64
 _RAW_I32 = 2                            # CLX_RAW_I32: clx_region_intensity sums the values as they are
 _OUT_OF_RANGE = f"{{who}}: {{name}} must lie in [0, {MAX_LEVEL}]"
@@ -90,14 +90,6 @@ def _device_levels(image, device, who, name="image"):
     return torch.from_numpy(np.ascontiguousarray(image).astype(np.int32)).to(device).reshape(-1)
 
 
-def _device_mask(mask, device):
-    """anything that ``!= 0`` makes boolean -> flat uint8 on the device (None stays None)"""
-    if mask is None:
-        return None
-    m = mask.to(device) != 0 if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0)).to(device)
-    return m.to(torch.uint8).contiguous().reshape(-1)
-
-
 def _grey_scene(image, device, who):
     """the ``_Scene`` of a checked map of grey levels: ``lab`` holds the levels, and there are no ids"""
     device = _resolve_device(image, device)
@@ -120,26 +112,15 @@ def _morph(scene, values, mask_d, op, steps, name="image"):
 
 
 def _reconstruct(scene, marker, image, mask_d):
-    """the clx_grey_reconstruct calls of one reconstruction, ROUNDS_PER_CALL rounds each, until no tile changes -> (the
-    result, flat int32 on the device; the rounds in which a tile changed)"""
-    npix = image.numel()
+    """the clx_grey_reconstruct calls of one reconstruction (``_settle``) -> (the result, flat int32 on the device; the rounds
+    in which a tile changed)"""
     workspace, nbytes = _workspace(scene, "clx_grey_reconstruct_workspace", scene.nd, scene.Z, scene.Y, scene.X)
-    out = torch.empty(npix, dtype=torch.int32, device=scene.device)
-    info = torch.empty(3, dtype=torch.int32, device=scene.device)
-    total, resume = 0, 0
-    while True:
-        _clx.call("clx_grey_reconstruct", _clx.ptr(marker), _clx.ptr(image), _clx.ptr(mask_d), scene.nd, scene.Z, scene.Y, scene.X,
-                  ROUNDS_PER_CALL, resume, _clx.ptr(out), _clx.ptr(info), _clx.ptr(workspace), nbytes, _clx.stream_ptr(scene.device))
-        flags, changed, busy = info.tolist()
-        if flags & 1:
-            raise ValueError(_OUT_OF_RANGE.format(who=scene.who, name="marker"))
-        if flags & 2:
-            raise ValueError(_OUT_OF_RANGE.format(who=scene.who, name="image"))
-        total, resume = total + busy, 1
-        if changed == 0:
-            return out, total
-        if total > npix + 1:                                  # every changing round settles one more pixel of some best path
-            raise RuntimeError(f"{scene.who}: {total} rounds changed a map of {npix} pixels: the reconstruction does not come to rest")
+    out = torch.empty(image.numel(), dtype=torch.int32, device=scene.device)
+    total = _settle(scene, lambda resume, info: _clx.call(
+        "clx_grey_reconstruct", _clx.ptr(marker), _clx.ptr(image), _clx.ptr(mask_d), scene.nd, scene.Z, scene.Y, scene.X,
+        ROUNDS_PER_CALL, resume, _clx.ptr(out), _clx.ptr(info), _clx.ptr(workspace), nbytes, _clx.stream_ptr(scene.device)),
+        {1: _OUT_OF_RANGE.format(who=scene.who, name="marker"), 2: _OUT_OF_RANGE.format(who=scene.who, name="image")}, "reconstruction")
+    return out, total
 
 
 def _morphology(image, steps, mask, device, who, ops):

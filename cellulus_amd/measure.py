@@ -288,6 +288,42 @@ def _workspace(scene, entry, *args, below="2^32"):
     return torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=scene.device), nbytes
 
 
+ROUNDS_PER_CALL = 8                     # rounds a call of a round-driven entry point queues between two looks at info[1]
+
+
+def _settle(scene, call, errors, what):
+    """the library calls of one fixed point reached in rounds (clx_label_propagate, clx_grey_reconstruct), ROUNDS_PER_CALL
+    rounds each, until no tile changes.  ``call(resume, info)`` makes one call through ``_clx.call``; ``errors``: {bit of
+    info[0]: message}, raised as ValueError in that order; ``what`` names the iteration where it does not end -> the rounds
+    in which a tile changed"""
+    import torch
+
+    npix = scene.lab.numel()
+    info = torch.empty(3, dtype=torch.int32, device=scene.device)
+    total, resume = 0, 0
+    while True:
+        call(resume, info)
+        flags, changed, busy = info.tolist()
+        for bit, message in errors.items():
+            if flags & bit:
+                raise ValueError(message)
+        total, resume = total + busy, 1
+        if changed == 0:
+            return total
+        if total > npix + 1:                                  # every changing round settles one more pixel of some best path
+            raise RuntimeError(f"{scene.who}: {total} rounds changed a map of {npix} pixels: the {what} does not come to rest")
+
+
+def _device_mask(mask, device):
+    """anything that ``!= 0`` makes boolean -> flat uint8 on the device (None stays None)"""
+    import torch
+
+    if mask is None:
+        return None
+    m = mask.to(device) != 0 if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0)).to(device)
+    return m.to(torch.uint8).contiguous().reshape(-1)
+
+
 def _result_scene(scene, lab):
     """a map ``lab`` made of the scene's (flat int32 on the device, the same ids) as a measured scene of its own, which must
     hold the objects the scene holds"""

@@ -34,12 +34,12 @@ import numpy as np
 import torch
 
 from . import _clx, _stage
-from .measure import LABELS_OUT_OF_RANGE, _check_map, _in_type_of, _inscribed_of, _result_scene, _scene, _workspace
+from .measure import (LABELS_OUT_OF_RANGE, ROUNDS_PER_CALL, _check_map, _device_mask, _in_type_of, _inscribed_of, _result_scene, _scene,
+                      _settle, _workspace)
 from .measure_columns import DIST_INF, _exact_div, _extents, _raster_columns
 
 COST_INF = DIST_INF                     # CLX_COST_INF: the cost of a pixel that no path reaches
 MAX_WEIGHT = 65535                      # clx_label_propagate: weight and reg lie in [0, 65535]
-ROUNDS_PER_CALL = 8                     # relaxation rounds queued between two looks at info[1]
 _WEIGHT_OUT_OF_RANGE = f"{{who}}: weight must lie in [0, {MAX_WEIGHT}]"
 
 
@@ -114,14 +114,6 @@ def _check_inputs(seeds, mask, weight, regularisation, limit, who):
     return reg, limit
 
 
-def _device_mask(mask, device):
-    """anything that ``!= 0`` makes boolean -> flat uint8 on the device (None stays None)"""
-    if mask is None:
-        return None
-    m = mask.to(device) != 0 if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0)).to(device)
-    return m.to(torch.uint8).contiguous().reshape(-1)
-
-
 def _device_weight(weight, device, who):
     if weight is None:
         return None
@@ -134,28 +126,17 @@ def _device_weight(weight, device, who):
 
 
 def _propagate(scene, mask_d, weight_d, reg, limit):
-    """the clx_label_propagate calls of one map, ROUNDS_PER_CALL rounds each, until no tile changes -> (owner, cost), flat int32
-    device tensors"""
+    """the clx_label_propagate calls of one map (``_settle``) -> (owner, cost), flat int32 device tensors"""
     npix = scene.lab.numel()
     workspace, nbytes = _workspace(scene, "clx_label_propagate_workspace", scene.nd, scene.Z, scene.Y, scene.X)
     owner = torch.empty(npix, dtype=torch.int32, device=scene.device)
     cost = torch.empty(npix, dtype=torch.int32, device=scene.device)
-    info = torch.empty(3, dtype=torch.int32, device=scene.device)
-    total, resume = 0, 0
-    while True:
-        _clx.call("clx_label_propagate", _clx.ptr(scene.lab), _clx.ptr(mask_d), _clx.ptr(weight_d), scene.nd, scene.Z, scene.Y, scene.X,
-                  scene.nid, reg, limit, ROUNDS_PER_CALL, resume, _clx.ptr(owner), _clx.ptr(cost), _clx.ptr(info), _clx.ptr(workspace),
-                  nbytes, _clx.stream_ptr(scene.device))
-        flags, changed, busy = info.tolist()
-        if flags & 1:
-            raise ValueError(LABELS_OUT_OF_RANGE.format(who=scene.who))
-        if flags & 2:
-            raise ValueError(_WEIGHT_OUT_OF_RANGE.format(who=scene.who))
-        if changed == 0:
-            return owner, cost
-        total, resume = total + busy, 1
-        if total > npix + 1:                                  # every changing round settles one more pixel of every best path
-            raise RuntimeError(f"{scene.who}: {total} rounds changed a map of {npix} pixels: the relaxation does not come to rest")
+    _settle(scene, lambda resume, info: _clx.call(
+        "clx_label_propagate", _clx.ptr(scene.lab), _clx.ptr(mask_d), _clx.ptr(weight_d), scene.nd, scene.Z, scene.Y, scene.X,
+        scene.nid, reg, limit, ROUNDS_PER_CALL, resume, _clx.ptr(owner), _clx.ptr(cost), _clx.ptr(info), _clx.ptr(workspace), nbytes,
+        _clx.stream_ptr(scene.device)),
+        {1: LABELS_OUT_OF_RANGE.format(who=scene.who), 2: _WEIGHT_OUT_OF_RANGE.format(who=scene.who)}, "relaxation")
+    return owner, cost
 
 
 def _front(seeds, mask, weight, regularisation, limit, device, who):

@@ -57,6 +57,21 @@ def test_measure_helpers_are_defined_once():
     assert [n for n in names if "enum { RAW_F32" in text[n]] == []
 
 
+def test_round_frame_and_map_check_are_defined_once():
+    # the frame of the round-queued kernels (propagate, reconstruction; thinning's activity test) has one copy, tile_rounds.h,
+    # and the wording of the map-shape refusals one, beside clx_map_shape
+    csrc = os.path.join(ROOT, "cellulus_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    text = {n: open(os.path.join(csrc, n), encoding="utf-8").read() for n in names}
+    for piece in ("struct TileGrid", "size_t flag_bytes(", "constexpr int MAX_ROUNDS", "constexpr int TILE_MAX_GRID", "bool tile_active(",
+                  "__global__ void rounds_finish("):
+        assert [n for n in names if piece in text[n]] == ["tile_rounds.h"], piece
+    assert [n for n in names if "_finish(int* __restrict__ head" in text[n]] == ["label_thin.hip", "tile_rounds.h"]
+    # (": " in front: clx_region_moments' bound on (largest extent - 1)^2 * Z * Y * X is another check and ends in the same words)
+    for piece in (": Z * Y * X must be below 2^", "int clx_map_shape(const char* who, int nd, int Z, int Y, int X, int bits, long long* npix) {"):
+        assert [n for n in names if piece in text[n]] == ["clx_core.hip"], piece
+
+
 def test_compile_command_ignores_the_environment(monkeypatch):
     from cellulus_amd import _build
 

@@ -4,8 +4,9 @@ point).  Everything is integer work: out, bad and info[0] must be EQUAL in every
 prefilled with 0xAB bytes and sit between guard words that must stay untouched.
 
 The constants below mirror csrc/grey_morph.hip: MorphShape / ReconShape, the extents of a tile (2-D: TY, TX; 3-D: TZ, TY, TX);
-MORPH_STEPS (HMAX), the largest halo and so the steps of one call; TILE_MAX_GRID, the blocks of a launch, beyond which a block
-takes more than one tile; MAX_SWEEPS, the sweeps a tile makes in one round; MAX_ROUNDS, the rounds of a call."""
+MORPH_STEPS (HMAX), the largest halo and so the steps of one call; MAX_SWEEPS, the sweeps a tile makes in one round; and
+csrc/tile_rounds.h: TILE_MAX_GRID, the blocks of a launch, beyond which a block takes more than one tile; MAX_ROUNDS, the rounds
+of a call."""
 
 import ctypes
 import itertools

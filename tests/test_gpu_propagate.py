@@ -3,8 +3,8 @@ the large maps the Jacobi relaxation over shifted views).  Everything is integer
 every element.  Outputs and the workspace are prefilled with 0xAB bytes and sit between guard words that must stay untouched.
 
 The constants below mirror csrc/label_propagate.hip: TileShape<2> (TY, TX) and TileShape<3> (TZ, TY, TX), the extents of a tile;
-TILE_MAX_GRID, the blocks of a round, beyond which a block takes more than one tile; MAX_SWEEPS, the sweeps a tile makes in one
-round; MAX_ROUNDS, the rounds of a call."""
+MAX_SWEEPS, the sweeps a tile makes in one round; and csrc/tile_rounds.h: TILE_MAX_GRID, the blocks of a round, beyond which a
+block takes more than one tile; MAX_ROUNDS, the rounds of a call."""
 
 import ctypes
 import itertools
