@@ -234,6 +234,8 @@ PROTOTYPES = {
     "clx_label_thin_workspace": (c_size_t, [_I, _I, _I, _I]),
     "clx_label_thin": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, c_size_t, _P]),
     "clx_skeleton_census": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "clx_skeleton_graph_workspace": (c_size_t, [_I, _I, _I, _I]),
+    "clx_skeleton_graph": (_I, [_P, _P, _I, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "clx_grey_morph": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "clx_grey_reconstruct_workspace": (c_size_t, [_I, _I, _I, _I]),
     "clx_grey_reconstruct": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, c_size_t, _P]),

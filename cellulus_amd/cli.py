@@ -9,7 +9,7 @@ command (``python -m cellulus_amd.expand <toml> --source NAME [--distance D --ou
 command (``python -m cellulus_amd.fill <toml> --source NAME --output NAME [--max-size N] [--planewise]``) and the ``propagate``
 command (``python -m cellulus_amd.propagate <toml> --seeds NAME --output NAME [--mask NAME] [--channel K [--levels 256]]
 [--regularisation 1] [--limit COST]``) and the ``skeleton`` command (``python -m cellulus_amd.skeleton <toml> --source NAME
---output NAME [--max-iter N] [--planewise] [--radius]``) and the ``granularity`` command (``python -m cellulus_amd.granularity <toml>
+--output NAME [--max-iter N] [--planewise] [--radius] [--prune L] [--graph]``) and the ``granularity`` command (``python -m cellulus_amd.granularity <toml>
 --source NAME [--channel K] [--scales 16] [--levels 256] [--background R]``)."""
 
 import click
@@ -174,11 +174,18 @@ def fill(config_file, source, output, max_size, planewise):
               help="stop after N iterations (two sub-iterations each); 0 changes nothing [default: until nothing is deleted]")
 @click.option("--planewise", is_flag=True, help="3-D: thin every slice as a 2-D map of its own (3-D maps need it)")
 @click.option("--radius", is_flag=True, help="add the smallest, largest and mean squared distance to the object's edge along the skeleton")
-def skeleton(config_file, source, output, max_iter, planewise, radius):
+@click.option("--prune", default=None, metavar="L", type=click.FloatRange(0.0, 2.0 ** 20 - 2.0 ** -10),    # ceil(L * 1024) < 2^30
+              help="remove the spurs (branches from a free end to a junction) shorter than L pixels, in one round [default: none]")
+@click.option("--graph", is_flag=True,
+              help="add the branch graph's columns (branches, junctions, cycles, spurs, components, branch lengths, longest path) "
+                   "and write skeleton_branches_bandwidth-<b>.csv, one row per branch")
+def skeleton(config_file, source, output, max_iter, planewise, radius, prune, graph):
     from .skeleton import skeleton_stage
 
+    if prune is not None and prune != prune:                 # (a NaN passes every range check)
+        raise click.BadParameter("nan is not a length", param_hint="--prune")
     skeleton_stage(ExperimentConfig(**_load(config_file)).inference_config, source, output, max_iter=max_iter, planewise=planewise,
-                   radius=radius)
+                   radius=radius, graph=graph, prune=prune)
 
 
 @click.command()

@@ -32,6 +32,7 @@
 //              leaves the launch count and the last word in the head for a call with resume == 1; `write` forms out from the
 //              labels and the current plane.
 // Integers only, in fact bits; the labels are compared and never an index.  The same bits in every run.
+#include "skeleton_links.h"
 #include "tile_rounds.h"
 
 namespace {
@@ -315,14 +316,9 @@ __global__ __launch_bounds__(BLOCK) void census_kernel(const int* __restrict__ l
     if ((unsigned int)v >= (unsigned int)nid) { v = 0; flags |= 1; }
     Census r = {0u, 0u, 0ull, CLX_DIST_INF, -1};
     if (v != 0) {
-      bool nb[8];                       // E, S, W, N, SE, SW, NW, NE carry v (v lies in [1, nid): so does such a neighbour)
-      constexpr int DX[8] = {1, 0, -1, 0, 1, -1, -1, 1}, DY[8] = {0, 1, 0, -1, 1, 1, -1, -1};
-#pragma unroll
-      for (int q = 0; q < 8; ++q) nb[q] = has_neighbour(a, s, DX[q], DY[q]) && lab[a.p + (long long)DY[q] * s.X + DX[q]] == v;
-      const bool e = nb[0], so = nb[1], we = nb[2], no = nb[3];
-      const bool se = nb[4] && !so && !e, sw = nb[5] && !so && !we, nw = nb[6] && !no && !we, ne = nb[7] && !no && !e;
-      const int degree = e + so + we + no + se + sw + nw + ne;
-      r.c0 = 1u | (unsigned int)(e + so) << 8 | (unsigned int)(se + sw) << 16 | (unsigned int)(e && so && nb[4]) << 24;
+      const Links l = links_at(lab, a.p, a.x, a.y, s.Y, s.X, v);      // (v lies in [1, nid): so does a neighbour that carries v)
+      const int degree = l.degree();
+      r.c0 = 1u | (unsigned int)l.owned_face() << 8 | (unsigned int)l.owned_diag() << 16 | (unsigned int)l.block << 24;
       r.c1 = (unsigned int)(degree == 1) | (unsigned int)(degree >= 3) << 8 | (unsigned int)(degree == 0) << 16;
       if (dist) {
         const int d = dist[a.p];

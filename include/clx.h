@@ -1538,6 +1538,70 @@ int clx_label_thin(const int32_t* labels, int nd, int Z, int Y, int X, int itera
 int clx_skeleton_census(const int32_t* skeleton, const int32_t* dist_sq, int nd, int Z, int Y, int X, int nid,
                         long long* words, int32_t* bad, clx_stream stream);
 
+/* Branch graph of a thinned map (of any map: the definitions need no thinning), slice by slice as above (skeleton_graph.hip):
+ * skan's summarize, CellProfiler's MeasureObjectSkeleton, ImageJ's AnalyzeSkeleton -- the census's pixel graph contracted to
+ * nodes and branches, one row each, and one round of spur pruning.
+ *   input     one int32 map [Z][Y][X], 2-D (nd == 2, Z == 1) or 3-D.  Every non-zero value is an OBJECT pixel; the value is
+ *             compared and never used as an index, so no nid argument is needed.  With nd == 3 every slice is a 2-D map of its
+ *             own.  The ends of rows and slices never wrap
+ *   links and degree  exactly the census's: a face link joins two face neighbours of one label, a diagonal link two diagonal
+ *             neighbours of one label neither of whose two common face neighbours carries it; a pixel's degree is the number
+ *             of its links
+ *   pixel kinds  a PATH pixel has degree 2, an END pixel degree 1, a JUNCTION pixel degree >= 3, an ISOLATED pixel degree 0
+ *   node      a maximal set of junction pixels connected by links between two junction pixels (kind 3); an end pixel alone
+ *             (kind 1); an isolated pixel alone (kind 0).  A node's ID is its smallest raster index
+ *   branch    (a) a maximal set of path pixels connected by links between two path pixels, together with every link from one of
+ *             them to a pixel that is no path pixel (a TERMINAL link); its FIRST is its smallest path pixel.  (b) a DIRECT
+ *             branch: a single link between an end pixel and a junction pixel or between two end pixels; it has 0 path pixels
+ *             and its first is the end pixel, the smaller one of two.  Links between two junction pixels belong to their node
+ *             and are no branches
+ *   terminals a path pixel has two links, so a branch of kind (a) has two terminal links or none; with none it is a CYCLE.  A
+ *             full 2 x 2 block of one label on its own is a cycle of 4 pixels: each of its pixels has two face links and no
+ *             diagonal one
+ *   branch kind  0 end-end, 1 end-junction (a SPUR), 2 junction-junction (both terminals on one node included), 3 cycle
+ *   branches  [capacity_b][13] int64: first, label, kind, path_pixels, face_links, diag_links (the terminal links included),
+ *             pixel_a, pixel_b (the two pixels beyond the terminal links as raster indices, a <= b; -1, -1 for a cycle),
+ *             node_a, node_b (the ids of the nodes these pixels belong to; -1, -1 for a cycle), d2_sum, d2_min, d2_max (the sum
+ *             and extremes of dist_sq over the path pixels; with dist_sq == NULL, and for a branch without path pixels, 0,
+ *             CLX_DIST_INF and -1)
+ *   nodes     [capacity_n][7] int64: first (the id), label, kind, pixels, links_out (the branch terminals attached to the node;
+ *             a branch with both ends on the node counts twice), inner_face, inner_diag (the links between two of its junction
+ *             pixels, each counted once)
+ *             Every link of the map lies in exactly one branch or inside exactly one node; every object pixel is a path pixel
+ *             of one branch or a pixel of one node.  The order of the rows is unspecified; the host sorts them by first
+ *   pruning   limit_q10 is a length in units of 1/1024 pixel.  A spur is PRUNED iff face_links + sqrt(2) diag_links <
+ *             limit_q10 / 1024, decided in integers: with F = 1024 face_links, D = 1024 diag_links, T = limit_q10 it is not
+ *             pruned if F >= T or D >= T, otherwise iff 2 D^2 < (T - F)^2 (no tie is possible but with diag_links == 0, where
+ *             the test is F < T; T < 2^30 keeps the squares in 64 bits).  End-end branches, junction-junction branches and
+ *             cycles are never pruned.  One call is one round: the junction a spur left may have become a path or an end pixel,
+ *             so a second round is a second call on out
+ *   branch_map  [Z][Y][X] int32 or NULL, every element written: first + 1 of its branch on a path pixel, -(node id + 1) on a
+ *             node pixel, 0 on background
+ *   out       [Z][Y][X] int32, every element written: labels with the path pixels and the end pixel of every pruned spur set
+ *             to 0; the junction stays.  With limit_q10 == 0 out equals labels.  NULL is allowed with limit_q10 == 0
+ *   info [6]  cleared by the call.  [0] the branches found, [1] the nodes found: they may exceed the capacities -- rows beyond
+ *             capacity are dropped; branch_map, out and info are complete regardless.  [2] the pixels pruned.  [3] the spurs
+ *             pruned.  [4] bad bits; bit 1: a dist_sq outside [0, CLX_DIST_INF) under a path pixel; that pixel's value is left
+ *             out of the three d2 words.  [5] reserved, 0
+ *   workspace at least clx_skeleton_graph_workspace(nd, Z, Y, X) = 40 * Z * Y * X bytes (a host-only function; 0: a shape the
+ *             call refuses), 8-byte aligned: over raster indices the parent plane of a union-find, and at a root seven 32-bit
+ *             words and one 64-bit word -- of a branch its path pixels, face links, diagonal links, smallest and largest
+ *             terminal pixel and the three d2 words; of a node, in the first four of these planes, its pixels, links out, inner
+ *             face links and inner diagonal links
+ * Six plain launches on the stream and no host synchronisation: classify, link (lock-free atomicMin unions of path pixels with
+ * path pixels and of junction pixels with junction pixels, each link taken once by the pixel that has it towards E, S, SE or
+ * SW), flatten, reduce (the attributes at the roots), emit (the rows; a wave reserves those of 8 segments of 64 pixels with one
+ * add to each counter), write.  No block waits for another; integer atomics only; ids are 32-bit raster indices.  Everything
+ * written is a function of the input alone but the order of the rows.
+ * Refused (CLX_ERR_ARG) before any launch: null labels, info or workspace, null branches with capacity_b > 0, null nodes with
+ * capacity_n > 0, nd not 2 or 3, nd == 2 with Z != 1, a non-positive extent, Z*Y*X >= 2^31, a negative capacity, limit_q10
+ * outside [0, 2^30), limit_q10 > 0 with a null out, workspace_bytes below clx_skeleton_graph_workspace(nd, Z, Y, X), a workspace
+ * that is not 8-byte aligned, out == labels, branch_map == labels, out == branch_map. */
+size_t clx_skeleton_graph_workspace(int nd, int Z, int Y, int X);
+int clx_skeleton_graph(const int32_t* labels, const int32_t* dist_sq, int nd, int Z, int Y, int X, long long limit_q10,
+                       int capacity_b, int capacity_n, int32_t* branch_map, int32_t* out, long long* branches,
+                       long long* nodes, int32_t* info, void* workspace, size_t workspace_bytes, clx_stream stream);
+
 /* ------------------------------------------------------------------------ */
 /* "granularity" stage: grey-scale morphology on a map of grey levels        */
 /* (grey_morph.hip)                                                          */
