@@ -17,7 +17,7 @@
 //                        workspace).  Union-find over the horizontal runs of every pixel, then five passes over pixels.
 //   label-list pipeline  every other 2-D image.  `out` is the parent array, and the passes after the strip pass work on
 //                        the few thousand strip-local labels instead of on pixels.
-#include "clx_common.h"
+#include "segments.h"                   // the frame of the run pipeline's first three passes
 #include "union_find.h"                 // uf_find, uf_find_halve, uf_union
 
 namespace {
@@ -27,45 +27,23 @@ namespace {
 // cc_number_roots, cc_write.  Workspace: [L | size | block counts].
 // ---------------------------------------------------------------------------------------------
 
-// Wave w of the grid owns 64 consecutive pixels of one row ("segment").  Returns the pixel index
-// of lane 0, the row's first pixel index and x of this lane; valid = inside the row.
-struct SegPos { long long i; int x; bool valid; };
-__device__ __forceinline__ SegPos seg_pos(long long w, int nseg, int X, int lane) {
-  const long long row = w / nseg;
-  const int sg = (int)(w - row * nseg);
-  SegPos p;
-  p.x = sg * 64 + lane;
-  p.valid = p.x < X;
-  p.i = row * X + p.x;
-  return p;
-}
-
-// lane of the first pixel of this lane's horizontal run of equal non-zero values inside the
-// segment (background lanes: themselves)
-__device__ __forceinline__ int run_start_lane(int v, int lane, unsigned long long* starts_out) {
-  const int vl = __shfl_up(v, 1, 64);
-  const bool same_left = lane > 0 && v != 0 && vl == v;
-  const unsigned long long starts = __ballot(!same_left);
-  if (starts_out) *starts_out = starts;
-  const unsigned long long upto = starts & ((2ull << lane) - 1ull);
-  return 63 - __builtin_clzll(upto);
-}
+constexpr int CC_MAX_GRID = 8192;       // blocks of the grid-stride launches of both pipelines
 
 // pass 1: L[i] = first pixel of i's run inside its 64-pixel segment (background: -1).  Runs,
 // not pixels, are what the union-find links: a 32-pixel-wide object costs one union per row
 // instead of ~100 (every pixel with each of its 4 / 13 backward neighbours).
-__global__ __launch_bounds__(256) void cc_init_runs(const int* __restrict__ seg, int* __restrict__ L,
-                                                    int* __restrict__ size, int X, int nseg,
-                                                    long long nwaves) {
+__global__ __launch_bounds__(BLOCK) void cc_init_runs(const int* __restrict__ seg, int* __restrict__ L,
+                                                      int* __restrict__ size, Segments s) {
   const int lane = threadIdx.x & 63;
-  for (long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwaves;
-       w += ((long long)gridDim.x * blockDim.x) >> 6) {
-    const SegPos p = seg_pos(w, nseg, X, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const int v = p.valid ? seg[p.i] : 0;
-    const int s = run_start_lane(v, lane, nullptr);
+    // the horizontal runs of equal non-zero values inside the segment (background lanes: runs of their own)
+    const int left = __shfl_up(v, 1, 64);
+    const int start = run_start_lane(v != 0 && v == left, lane).start;
     if (p.valid) {
-      L[p.i] = v ? (int)(p.i - lane + s) : -1;
-      if (s == lane) size[p.i] = 0;        // sizes live at run starts (the only possible roots)
+      L[p.i] = v ? (int)(p.i - lane + start) : -1;
+      if (start == lane) size[p.i] = 0;        // sizes live at run starts (the only possible roots)
     }
   }
 }
@@ -77,17 +55,14 @@ __global__ __launch_bounds__(256) void cc_init_runs(const int* __restrict__ seg,
 //   c and not b and no right pixel in my run-> union with (r, x+1)  [else the right pixel does]
 // plus the run continuation across a segment boundary.  Every adjacency is covered by a chain
 // of these unions; nothing else touches an atomic.
-__global__ __launch_bounds__(256) void cc_merge_runs(const int* __restrict__ seg, int* L, int Z, int Y,
-                                                     int X, int nseg, long long nwaves) {
+__global__ __launch_bounds__(BLOCK) void cc_merge_runs(const int* __restrict__ seg, int* L, Segments s) {
   const int lane = threadIdx.x & 63;
-  for (long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwaves;
-       w += ((long long)gridDim.x * blockDim.x) >> 6) {
-    const SegPos p = seg_pos(w, nseg, X, lane);
+  const int Y = s.Y, X = s.X;
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos<false>(w, s, lane);
     const int v = p.valid ? seg[p.i] : 0;
     if (v == 0) continue;
-    const int x = p.x;
-    const long long row = (p.i - x) / X;
-    const int y = (int)(row % Y), z = (int)(row / Y);
+    const int x = p.x, y = (int)(p.row % Y), z = (int)(p.row / Y);       // only now: segments.h says why
     const bool left = x > 0 && seg[p.i - 1] == v;
     const bool right = x + 1 < X && seg[p.i + 1] == v;
     if (lane == 0 && left) uf_union(L, (int)p.i, (int)p.i - 1);
@@ -109,24 +84,19 @@ __global__ __launch_bounds__(256) void cc_merge_runs(const int* __restrict__ seg
 
 // pass 3: every pixel learns its root (one find per run, broadcast inside the wave) and every
 // run adds its length to the root's size (one atomic per run)
-__global__ __launch_bounds__(256) void cc_flatten_count(const int* __restrict__ seg, int* L, int* size,
-                                                        int X, int nseg, long long nwaves) {
+__global__ __launch_bounds__(BLOCK) void cc_flatten_count(const int* __restrict__ seg, int* L, int* size, Segments s) {
   const int lane = threadIdx.x & 63;
-  for (long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nwaves;
-       w += ((long long)gridDim.x * blockDim.x) >> 6) {
-    const SegPos p = seg_pos(w, nseg, X, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const int v = p.valid ? seg[p.i] : 0;
-    unsigned long long starts;
-    const int s = run_start_lane(v, lane, &starts);
+    const int left = __shfl_up(v, 1, 64);
+    const Runs runs = run_start_lane(v != 0 && v == left, lane);
     int root = -1;
-    if (v != 0 && s == lane) {
+    if (v != 0 && runs.start == lane) {
       root = uf_find(L, (int)p.i);
-      // run length = distance to the next run start (or the end of the segment)
-      const unsigned long long above = (lane == 63) ? 0ull : (starts >> (lane + 1));
-      const int len = above ? __builtin_ctzll(above) + 1 : 64 - lane;
-      atomicAdd(&size[root], len);
+      atomicAdd(&size[root], run_lanes(runs.starts, lane));
     }
-    root = __shfl(root, s, 64);
+    root = __shfl(root, runs.start, 64);
     if (v != 0) L[p.i] = root;    // roots keep pointing at themselves
   }
 }
@@ -588,13 +558,6 @@ __global__ __launch_bounds__(256) void cc_rewrite_masked(int* out, const int* __
   }
 }
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
 
 extern "C" size_t clx_cc_workspace(long long npix) {
@@ -637,19 +600,19 @@ extern "C" int clx_cc_label_filter(const int* seg, int* out, int Z, int Y, int X
   const bool fits = (size_t)((unsigned char*)(chunk + nchunks) - (unsigned char*)workspace) <= clx_cc_workspace(npix);
   if (Z == 1 && fits && ((uintptr_t)out & 15) == 0) {          // (16-byte groups of `out` in the rewrite)
     const int nstrips = (Y + STRIP_ROWS - 1) / STRIP_ROWS;
-    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_strip1, dim3(grid_for((long long)nstrips * nseg * 64, 256)), dim3(256), 0, st, seg, out, sz, labelmask, fgmask, colL, colR, Y, X, nseg, nstrips);
+    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_strip1, dim3(grid_for((long long)nstrips * nseg * 64, 256, CC_MAX_GRID)), dim3(256), 0, st, seg, out, sz, labelmask, fgmask, colL, colR, Y, X, nseg, nstrips);
     const long long nb = (long long)(nstrips - 1) * X + (long long)(nseg - 1) * Y;
-    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_link1, dim3(grid_for(nb > nwords ? nb : nwords, 256)), dim3(256), 0, st, seg, out, colL, colR, Y, X, nseg, nstrips, STRIP_ROWS, bitmap, nwords);
-    const int lgrid = grid_for(nmask, 256);
+    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_link1, dim3(grid_for(nb > nwords ? nb : nwords, 256, CC_MAX_GRID)), dim3(256), 0, st, seg, out, colL, colR, Y, X, nseg, nstrips, STRIP_ROWS, bitmap, nwords);
+    const int lgrid = grid_for(nmask, 256, CC_MAX_GRID);
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_fold, dim3(lgrid), dim3(256), 0, st, out, sz, labelmask, nmask, nseg, X);
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_mark, dim3(lgrid), dim3(256), 0, st, out, sz, labelmask, nmask, nseg, X, min_size, bitmap);
-    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_word_prefix, dim3(grid_for((long long)nchunks * 64, 256)), dim3(256), 0, st, bitmap, nwords, (int)(rank_chunk / 32), nchunks, wprefix, chunk);
+    CLX_LAUNCH_KIND(CLX_PROF_CC, cc_word_prefix, dim3(grid_for((long long)nchunks * 64, 256, CC_MAX_GRID)), dim3(256), 0, st, bitmap, nwords, (int)(rank_chunk / 32), nchunks, wprefix, chunk);
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_scan_counts, dim3(1), dim3(1024), 0, st, chunk, nchunks, ncomp_out);
     CLX_LAUNCH_KIND(CLX_PROF_CC, cc_rank, dim3(lgrid), dim3(256), 0, st, out, sz, labelmask, nmask, nseg, X, bitmap, chunk, wprefix, (int)rank_chunk);
     if (X % 4 == 0) {
       CLX_LAUNCH_KIND(CLX_PROF_CC, cc_rewrite_masked, dim3((X / 4 + 255) / 256, (Y + 7) / 8 < 32768 ? (Y + 7) / 8 : 32768), dim3(256), 0, st, out, sz, fgmask, Y, X, nseg);
     } else {
-      CLX_LAUNCH_KIND(CLX_PROF_CC, cc_rewrite, dim3(grid_for(npix / 4 + 1, 256)), dim3(256), 0, st, out, sz, npix);
+      CLX_LAUNCH_KIND(CLX_PROF_CC, cc_rewrite, dim3(grid_for(npix / 4 + 1, 256, CC_MAX_GRID)), dim3(256), 0, st, out, sz, npix);
     }
     CLX_CHECK_LAUNCH("clx_cc_label_filter");
     return CLX_OK;
@@ -659,15 +622,15 @@ extern "C" int clx_cc_label_filter(const int* seg, int* out, int Z, int Y, int X
   int* size = L + npix;
   int* counts = size + npix;
   const int nblocks = (int)((npix + SCAN_BLOCK - 1) / SCAN_BLOCK);
-  const long long nwaves = (long long)Z * Y * nseg;
-  const int wgrid = grid_for(nwaves * 64, 256);
-  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_init_runs, dim3(wgrid), dim3(256), 0, st, seg, L, size, X, nseg, nwaves);
-  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_merge_runs, dim3(wgrid), dim3(256), 0, st, seg, L, Z, Y, X, nseg, nwaves);
-  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_flatten_count, dim3(wgrid), dim3(256), 0, st, seg, L, size, X, nseg, nwaves);
+  const Segments s = segments_of(Z, Y, X);
+  const int wgrid = segment_grid(s.nwaves, CC_MAX_GRID);
+  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_init_runs, dim3(wgrid), dim3(BLOCK), 0, st, seg, L, size, s);
+  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_merge_runs, dim3(wgrid), dim3(BLOCK), 0, st, seg, L, s);
+  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_flatten_count, dim3(wgrid), dim3(BLOCK), 0, st, seg, L, size, s);
   CLX_LAUNCH_KIND(CLX_PROF_CC, cc_count_roots, dim3(nblocks), dim3(256), 0, st, seg, L, size, min_size, npix, counts);
   CLX_LAUNCH_KIND(CLX_PROF_CC, cc_scan_counts, dim3(1), dim3(1024), 0, st, counts, nblocks, ncomp_out);
   CLX_LAUNCH_KIND(CLX_PROF_CC, cc_number_roots, dim3(nblocks), dim3(256), 0, st, seg, L, size, min_size, npix, counts);
-  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_write, dim3(grid_for(npix, 256)), dim3(256), 0, st, seg, L, size, out, npix);
+  CLX_LAUNCH_KIND(CLX_PROF_CC, cc_write, dim3(grid_for(npix, 256, CC_MAX_GRID)), dim3(256), 0, st, seg, L, size, out, npix);
   CLX_CHECK_LAUNCH("clx_cc_label_filter");
   return CLX_OK;
 }

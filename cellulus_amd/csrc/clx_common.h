@@ -69,6 +69,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
 }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// blocks of a grid-stride launch over `items`, `per_block` of them a block and trip: at least 1, at most `cap`.  (Where a
+// caller's items are the pixels, words or tiles of a map that CLX_REQUIRE_MAP has checked there are some, and the floor is idle.)
+static inline int grid_for(long long items, int per_block, int cap) {
+  const long long g = (items + per_block - 1) / per_block;
+  return (int)(g < 1 ? 1 : g < cap ? g : cap);
+}
 
 // geometry of a convolution descriptor (conv_igemm.hip): nsrc, extents, kernel 1..3, padding < kernel, input >= kernel,
 // per source channels / ld / alignment / factors / crop / "covers the logical input", M < 2^31.  `who` prefixes the message.

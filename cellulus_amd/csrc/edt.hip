@@ -19,12 +19,8 @@ namespace {
 
 constexpr int EDT_INF = 1 << 29;
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 16384) g = 16384;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int EDT_MAX_GRID = 16384;   // blocks of a grid-stride launch
+constexpr int PHANTOM_MAX_GRID = 1024;  // ... of grow_shrink_phantom
 
 __global__ void edt_pass_x(const unsigned char* __restrict__ in, int* __restrict__ g, int X,
                            long long npix, int cap, int* __restrict__ any_zero) {
@@ -101,7 +97,7 @@ __global__ void zero_where_lt(int* __restrict__ seg, const int* __restrict__ d, 
 // tmp: npix ints + 1 flag int.  cap <= 0: unlimited search.
 int edt_run(const unsigned char* in, int* out, int Z, int Y, int X, int* tmp, int cap, hipStream_t st) {
   const long long npix = (long long)Z * Y * X;
-  const int grid = grid_for(npix, 256);
+  const int grid = grid_for(npix, 256, EDT_MAX_GRID);
   int* any_zero = tmp + npix;
   const int big = 1 << 20;
   const int cx = cap > 0 ? (cap < X ? cap : X) : X;
@@ -455,13 +451,13 @@ int grow_shrink_bitrows(int* seg, int Y, int X, int grow, int shrink, void* work
   if (hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) return CLX_ERR_LAUNCH;
   const long long w1 = (long long)Y * W64, w2 = (long long)ntiles_y * W64;
   if (X % 4 == 0 && ((uintptr_t)seg & 15) == 0)
-    CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, gs_bits4_kernel, dim3(grid_for((long long)Y * ((W64 + 3) / 4) * 64, 256)), dim3(256), 0, st, seg, bits, Y, X, W64);
+    CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, gs_bits4_kernel, dim3(grid_for((long long)Y * ((W64 + 3) / 4) * 64, 256, EDT_MAX_GRID)), dim3(256), 0, st, seg, bits, Y, X, W64);
   else
-    CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, gs_bits_kernel, dim3(grid_for(w1 * 64, 256)), dim3(256), 0, st, seg, bits, Y, X, W64);
-  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, gs_rows_kernel, dim3(grid_for(w2 * 64, 256)), dim3(256), 0, st, seg, bits, Y, X, W64, grow, shrink, rows_per_wave, ntiles_y,
+    CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, gs_bits_kernel, dim3(grid_for(w1 * 64, 256, EDT_MAX_GRID)), dim3(256), 0, st, seg, bits, Y, X, W64);
+  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, gs_rows_kernel, dim3(grid_for(w2 * 64, 256, EDT_MAX_GRID)), dim3(256), 0, st, seg, bits, Y, X, W64, grow, shrink, rows_per_wave, ntiles_y,
                                                          flag);
   const long long npix = (long long)Y * X;
-  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, grow_shrink_phantom, dim3(grid_for(npix, 256) < 1024 ? grid_for(npix, 256) : 1024), dim3(256), 0, st, seg, 1, Y, X, shrink, flag);
+  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, grow_shrink_phantom, dim3(grid_for(npix, 256, PHANTOM_MAX_GRID)), dim3(256), 0, st, seg, 1, Y, X, shrink, flag);
   return CLX_OK;
 }
 
@@ -494,7 +490,7 @@ int grow_shrink_tiled(int* seg, int Z, int Y, int X, int grow, int shrink, void*
   int* flag = (int*)workspace;
   unsigned char* mask = (unsigned char*)workspace + 16;
   if (hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) return CLX_ERR_LAUNCH;
-  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, fg_mask_kernel, dim3(grid_for((npix + 3) / 4, 256)), dim3(256), 0, st, seg, mask, npix);
+  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, fg_mask_kernel, dim3(grid_for((npix + 3) / 4, 256, EDT_MAX_GRID)), dim3(256), 0, st, seg, mask, npix);
   const dim3 grid((X + T::TX - 1) / T::TX, (Y + T::TY - 1) / T::TY, (Z + T::TZ - 1) / T::TZ);
   const size_t smem = gs_smem_bytes<ND>(grow, shrink);
   // segment.py's defaults (inference_config.py:158-159) are compiled in for 3-D only: in 2-D their halo of 7 always
@@ -507,7 +503,7 @@ int grow_shrink_tiled(int* seg, int Z, int Y, int X, int grow, int shrink, void*
     rc = gs_launch<ND, -1, -1>(grid, smem, seg, mask, Z, Y, X, grow, shrink, flag, st);
   }
   if (rc) return rc;
-  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, grow_shrink_phantom, dim3(grid_for(npix, 256) < 1024 ? grid_for(npix, 256) : 1024), dim3(256), 0, st, seg, Z, Y, X,
+  CLX_LAUNCH_KIND(CLX_PROF_GROW_SHRINK, grow_shrink_phantom, dim3(grid_for(npix, 256, PHANTOM_MAX_GRID)), dim3(256), 0, st, seg, Z, Y, X,
                                                                                                shrink, flag);
   return CLX_OK;
 }
@@ -558,7 +554,7 @@ extern "C" int clx_grow_shrink(int* seg, int Z, int Y, int X, int grow, int shri
   int* tmp = (int*)workspace;
   int* dist = tmp + npix + 4;
   unsigned char* mask = (unsigned char*)(dist + npix);
-  const int grid = grid_for(npix, 256);
+  const int grid = grid_for(npix, 256, EDT_MAX_GRID);
   hipStream_t st = (hipStream_t)stream;
   // d1 = edt(seg == 0); expanded = d1 < grow
   mask_eq_zero<<<grid, 256, 0, st>>>(seg, mask, npix);

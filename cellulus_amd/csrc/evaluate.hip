@@ -7,12 +7,7 @@
 
 namespace {
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int EVAL_MAX_GRID = 2048;   // blocks of a grid-stride launch
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -79,7 +74,7 @@ extern "C" int clx_label_presence(const int32_t* labels, long long n, int nid, i
                                   clx_stream stream) {
   CLX_REQUIRE(labels && present && bad && n > 0 && nid > 0, "clx_label_presence: bad arguments");
   CLX_REQUIRE(((uintptr_t)labels & 15) == 0, "clx_label_presence: labels must be 16-byte aligned");
-  presence_kernel<<<grid_for(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(labels, n, nid, present, bad);
+  presence_kernel<<<grid_for(n / 4 + 1, 256, EVAL_MAX_GRID), 256, 0, (hipStream_t)stream>>>(labels, n, nid, present, bad);
   CLX_CHECK_LAUNCH("clx_label_presence");
   return CLX_OK;
 }
@@ -88,7 +83,7 @@ extern "C" int clx_joint_histogram(const int32_t* pred, const int32_t* gt, long 
                                    const int32_t* gt_col, int ncol, unsigned long long* joint, clx_stream stream) {
   CLX_REQUIRE(pred && gt && pred_row && gt_col && joint && n > 0 && ncol > 0, "clx_joint_histogram: bad arguments");
   CLX_REQUIRE((((uintptr_t)pred | (uintptr_t)gt) & 15) == 0, "clx_joint_histogram: label maps must be 16-byte aligned");
-  joint_kernel<<<grid_for(n / 8 + 1, 256), 256, 0, (hipStream_t)stream>>>(pred, gt, n, pred_row, gt_col, ncol, joint);
+  joint_kernel<<<grid_for(n / 8 + 1, 256, EVAL_MAX_GRID), 256, 0, (hipStream_t)stream>>>(pred, gt, n, pred_row, gt_col, ncol, joint);
   CLX_CHECK_LAUNCH("clx_joint_histogram");
   return CLX_OK;
 }

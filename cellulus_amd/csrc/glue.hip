@@ -7,12 +7,7 @@
 
 namespace {
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int GLUE_MAX_GRID = 8192;   // blocks of a grid-stride launch
 
 // Linear index -> (4-channel group, x, y, z, batch) with host-prepared multiply-shift divisors: the
 // 64-bit `%` / `/` chain this replaces cost more VALU time than the kernels' memory traffic
@@ -289,7 +284,7 @@ extern "C" int clx_maxpool_fwd(const float* x, float* y, int B, int D, int H, in
   const int OD = D / fz, OH = H / fy, OW = W / fx;
   const long long total = (long long)B * OD * OH * OW * (C / 4);
   CLX_REQUIRE((long long)B * D * H * W * (C / 4) < (1ll << 31), "clx_maxpool_fwd: tensor too large");
-  maxpool_fwd_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  maxpool_fwd_kernel<<<grid_for(total, 256, GLUE_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       x, y, D, H, W, C / 4, fz, fy, fx, OD, OH, OW, make_dec(C / 4, OW, OH, OD), (uint32_t)total);
   CLX_CHECK_LAUNCH("clx_maxpool_fwd");
   return CLX_OK;
@@ -308,7 +303,7 @@ extern "C" int clx_maxpool_bwd(const float* x, const float* y, const float* dy_p
   CLX_REQUIRE(total < (1ll << 31), "clx_maxpool_bwd: tensor too large");
   // extents divide (checked above): every pixel belongs to exactly one window
   const long long wtotal = total / ((long long)fz * fy * fx);
-  maxpool_bwd_window_kernel<<<grid_for(wtotal, 256), 256, 0, (hipStream_t)stream>>>(
+  maxpool_bwd_window_kernel<<<grid_for(wtotal, 256, GLUE_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       x, dy_pool, dskip, ld_skip, SD, SH, SW, cz, cy, cx, dx, D, H, W, C / 4, fz, fy, fx,
       make_dec(C / 4, W / fx, H / fy, D / fz), (uint32_t)wtotal);
   CLX_CHECK_LAUNCH("clx_maxpool_bwd");
@@ -325,7 +320,7 @@ extern "C" int clx_upsample_bwd(const float* dcat, int ld_cat, int coff, int LD,
   CLX_REQUIRE(ld_cat % 4 == 0 && coff % 4 == 0 && coff + C <= ld_cat, "clx_upsample_bwd: bad ld/coff");
   const long long total = (long long)B * D * H * W * (C / 4);
   CLX_REQUIRE(total < (1ll << 31), "clx_upsample_bwd: tensor too large");
-  upsample_bwd_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  upsample_bwd_kernel<<<grid_for(total, 256, GLUE_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       dcat, ld_cat, coff, LD, LH, LW, oz, oy, ox, y, dy, D, H, W, C / 4, fz, fy, fx, make_dec(C / 4, W, H, D),
       (uint32_t)total);
   CLX_CHECK_LAUNCH("clx_upsample_bwd");
@@ -334,7 +329,7 @@ extern "C" int clx_upsample_bwd(const float* dcat, int ld_cat, int coff, int LD,
 
 static int noise_stats_launch(const float* preds, float* out, int T, int C, long long n, unsigned int* minmax,
                               hipStream_t st, int* grid_out = nullptr) {
-  int g = grid_for(n, 256);
+  int g = grid_for(n, 256, GLUE_MAX_GRID);
   if (minmax != nullptr && g > NOISE_MM_BLOCKS) g = NOISE_MM_BLOCKS;
   if (grid_out) *grid_out = g;
   if (T <= 32)
@@ -342,7 +337,7 @@ static int noise_stats_launch(const float* preds, float* out, int T, int C, long
   else if (T <= 64)
     CLX_LAUNCH_KIND(CLX_PROF_NOISE_STATS, (noise_stats_reg_kernel<64>), dim3(g), dim3(256), 0, st, preds, out, T, C, n, minmax);
   else
-    CLX_LAUNCH_KIND(CLX_PROF_NOISE_STATS, noise_stats_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, preds, out, T, C, n);
+    CLX_LAUNCH_KIND(CLX_PROF_NOISE_STATS, noise_stats_kernel, dim3(grid_for(n, 256, GLUE_MAX_GRID)), dim3(256), 0, st, preds, out, T, C, n);
   return CLX_OK;
 }
 
@@ -494,9 +489,9 @@ extern "C" int clx_noise_inject(const float* rnd, const float* raw, float* out, 
   hipStream_t st = (hipStream_t)stream;
   const bool vec = n % 4 == 0 && ((((uintptr_t)rnd | (uintptr_t)raw | (uintptr_t)out) & 15) == 0);
   if (vec)
-    noise_inject_kernel<4><<<grid_for((long long)T * (n / 4), 256), 256, 0, st>>>(rnd, raw, out, T, n_half, n / 4, p);
+    noise_inject_kernel<4><<<grid_for((long long)T * (n / 4), 256, GLUE_MAX_GRID), 256, 0, st>>>(rnd, raw, out, T, n_half, n / 4, p);
   else
-    noise_inject_kernel<1><<<grid_for((long long)T * n, 256), 256, 0, st>>>(rnd, raw, out, T, n_half, n, p);
+    noise_inject_kernel<1><<<grid_for((long long)T * n, 256, GLUE_MAX_GRID), 256, 0, st>>>(rnd, raw, out, T, n_half, n, p);
   CLX_CHECK_LAUNCH("clx_noise_inject");
   return CLX_OK;
 }
@@ -531,7 +526,7 @@ extern "C" int clx_gather_rows_f64(const double* src, const int* rows, long long
                                    clx_stream stream) {
   CLX_REQUIRE(n >= 0 && width > 0 && (n == 0 || (src && rows && dst)), "clx_gather_rows_f64: bad arguments");
   if (n == 0) return CLX_OK;
-  gather_rows_f64_kernel<<<grid_for(n * width, 256), 256, 0, (hipStream_t)stream>>>(src, rows, n, width, dst);
+  gather_rows_f64_kernel<<<grid_for(n * width, 256, GLUE_MAX_GRID), 256, 0, (hipStream_t)stream>>>(src, rows, n, width, dst);
   CLX_CHECK_LAUNCH("clx_gather_rows_f64");
   return CLX_OK;
 }
@@ -545,9 +540,9 @@ static int subpixel_launch(bool to_space, const float* src, float* dst, int ld_l
   CLX_REQUIRE(ld_lo % 4 == 0 && ld_lo >= fz * fy * fx * N && ld_hi % 4 == 0 && ld_hi >= N, "%s: bad strides", who);
   const long long total = (long long)B * D * H * W * fz * fy * fx * (N / 4);
   if (to_space)
-    subpixel_kernel<true><<<grid_for(total, 256), 256, 0, st>>>(src, dst, ld_lo, ld_hi, D, H, W, N / 4, fz, fy, fx, total);
+    subpixel_kernel<true><<<grid_for(total, 256, GLUE_MAX_GRID), 256, 0, st>>>(src, dst, ld_lo, ld_hi, D, H, W, N / 4, fz, fy, fx, total);
   else
-    subpixel_kernel<false><<<grid_for(total, 256), 256, 0, st>>>(src, dst, ld_lo, ld_hi, D, H, W, N / 4, fz, fy, fx, total);
+    subpixel_kernel<false><<<grid_for(total, 256, GLUE_MAX_GRID), 256, 0, st>>>(src, dst, ld_lo, ld_hi, D, H, W, N / 4, fz, fy, fx, total);
   CLX_CHECK_LAUNCH(who);
   return CLX_OK;
 }

@@ -271,7 +271,7 @@ __global__ __launch_bounds__(BLOCK) void reconstruct_round(Planes q, int k, int 
 template <int ND, bool DILATE>
 void launch_morph(const int* in, const unsigned char* mask, int Z, int Y, int X, int steps, int* out, int* bad, hipStream_t st) {
   const TileGrid g = tile_grid<MorphShape<2>, MorphShape<3>>(ND, Z, Y, X);
-  const int grid = (int)(g.ntiles < TILE_MAX_GRID ? g.ntiles : TILE_MAX_GRID);
+  const int grid = round_grid(g);
   grey_morph_kernel<ND, DILATE><<<grid, BLOCK, 0, st>>>(in, mask, Z, Y, X, g, steps, out, bad);
 }
 

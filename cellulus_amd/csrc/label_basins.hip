@@ -36,11 +36,6 @@ constexpr int MAP_MAX_GRID = 4096;              // blocks of BLOCK pixels a trip
 
 __device__ __forceinline__ u64 height(unsigned int d2, unsigned int p) { return ((u64)d2 << 32) | (u64)(NONE - p); }
 
-inline int map_grid(long long npix) {
-  const long long g = (npix + BLOCK - 1) / BLOCK;
-  return (int)(g < MAP_MAX_GRID ? g : MAP_MAX_GRID);
-}
-
 // pixel j * BLOCK + thread of tile t: the 4 pixels of a thread lie BLOCK apart, a wave reads 64 consecutive ones
 __device__ __forceinline__ long long thread_pixel(long long t, int j) { return t * TILE + (long long)j * BLOCK + threadIdx.x; }
 
@@ -242,7 +237,7 @@ extern "C" int clx_label_basins(const int32_t* labels, const int32_t* dist_sq, i
   const Tiling t = tiling_for(npix);
   ascent_kernel<<<t.grid, BLOCK, 0, st>>>(labels, dist_sq, other, (unsigned int*)summits, (unsigned int)capacity, (unsigned int*)info,
                                           nd == 3, Z, Y, X, npix, t.ntiles, t.per_block);
-  const int grid = map_grid(npix);
+  const int grid = grid_for(npix, BLOCK, MAP_MAX_GRID);
   for (int k = 1; k <= ROOT_LAUNCHES; ++k) {              // odd launches: workspace -> root; even ones: root -> workspace
     const bool to_root = k & 1;
     root_kernel<<<grid, BLOCK, 0, st>>>(to_root ? other : (const unsigned int*)root, to_root ? (unsigned int*)root : other,
@@ -282,7 +277,7 @@ extern "C" int clx_basin_relabel(const int32_t* root, long long npix, const int3
   CLX_REQUIRE(hipMemsetAsync(id_of, 0, (size_t)npix * sizeof(int), st) == hipSuccess, "clx_basin_relabel: hipMemsetAsync failed");
   CLX_REQUIRE(hipMemsetAsync(bad, 0, sizeof(int), st) == hipSuccess, "clx_basin_relabel: hipMemsetAsync failed");
   if (n > 0) relabel_scatter<<<(n + 255) / 256, 256, 0, st>>>((const unsigned int*)summits, ids, n, npix, id_of, bad);
-  relabel_kernel<<<map_grid(npix), BLOCK, 0, st>>>((const unsigned int*)root, id_of, out, npix, bad);
+  relabel_kernel<<<grid_for(npix, BLOCK, MAP_MAX_GRID), BLOCK, 0, st>>>((const unsigned int*)root, id_of, out, npix, bad);
   CLX_CHECK_LAUNCH("clx_basin_relabel");
   return CLX_OK;
 }

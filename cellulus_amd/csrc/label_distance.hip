@@ -22,11 +22,6 @@ namespace {
 constexpr unsigned int DIST_INF = (unsigned int)CLX_DIST_INF;
 constexpr int PASS_MAX_GRID = 4096;     // blocks of BLOCK pixels a trip
 
-inline int pass_grid(long long npix) {
-  const long long g = (npix + BLOCK - 1) / BLOCK;
-  return (int)(g < PASS_MAX_GRID ? g : PASS_MAX_GRID);
-}
-
 // candidates the padding adds along an axis of extent n at coordinate c: min(c + 1, n - c)^2 (n <= 2^15: at most 2^30)
 __device__ __forceinline__ unsigned int padding_sq(int c, int n) {
   const unsigned int m = (unsigned int)min(c + 1, n - c);
@@ -188,7 +183,7 @@ extern "C" int clx_label_distance_sq(const int32_t* labels, int nd, int Z, int Y
               "clx_label_distance_sq: workspace_bytes is below clx_label_distance_workspace(Z * Y * X)");
   CLX_REQUIRE(((uintptr_t)workspace & 3) == 0, "clx_label_distance_sq: workspace must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const int grid = pass_grid(npix);
+  const int grid = grid_for(npix, BLOCK, PASS_MAX_GRID);
   int* ws = (int*)workspace;
   // 2-D: X -> workspace, Y -> dist_sq.  3-D: X -> dist_sq, Y -> workspace, Z -> dist_sq.
   int* first = nd == 2 ? ws : dist_sq;

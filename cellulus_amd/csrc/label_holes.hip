@@ -2,10 +2,10 @@
 //   clx_label_holes   out = labels with every hole of a label L (a face-connected component of zeros that does not reach the
 //                     border and whose object face neighbours all carry L) of at most max_size pixels set to L; one row per hole
 //
-// The zeros are labelled by the lock-free union-find of cc_label.hip (union_find.h) over their horizontal RUNS, with face
-// connectivity: the complement of the 8 / 26-connectivity the objects have there.  A wave owns 64 consecutive pixels of a row
-// (a SEGMENT).  Five plain launches on the stream, no host synchronisation, and between two of them nothing but the kernel
-// boundary:
+// The zeros are labelled by the lock-free union-find of union_find.h over their horizontal RUNS, with face connectivity: the
+// complement of the 8 / 26-connectivity the objects have in cc_label.hip.  The passes walk the map segment by segment
+// (segments.h has the frame).  Five plain launches on the stream, no host synchronisation, and between two of them nothing but
+// the kernel boundary:
 //   1 runs     parent[i] = the first pixel of i's run of zeros inside its segment, -1 on object pixels.  The run starts are the
 //              only possible roots: their attributes (area | border bit, smallest and largest neighbour value) are cleared here
 //   2 link     a zero unions with the zero straight above it (and, outside planewise, straight before it in z) unless its left
@@ -22,24 +22,22 @@
 //              info[1] (one add per block)
 // A component that does not reach the border has an object face neighbour (left of its first pixel), so "all neighbours carry
 // one value" is min == max and needs no bit of its own.
-// Correctness across blocks and XCDs rests on the values returned by atomics and on kernel boundaries alone (cc_label.hip's
+// Correctness across blocks and XCDs rests on the values returned by atomics and on kernel boundaries alone (union_find.h's
 // rule): no block waits for another, every loop ends because a parent strictly decreases.  Integers only; ids are 32-bit raster
 // indices (npix < 2^31); values of the map are compared, never an index.  The result is a function of the input; the ORDER of
 // the hole rows is not (the host sorts them by `first`).
 #include <limits.h>
+#include "segments.h"
 #include "union_find.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int MAX_GRID = 2048;                  // blocks of launches 1 to 4: 8192 waves; a wave takes the segments w, w + 8192, ...
+constexpr int HOLES_MAX_GRID = 2048;            // blocks of launches 1 to 4: 8192 waves; a wave takes the segments w, w + 8192, ...
 constexpr int FILL_SEGS = 8;                    // segments a wave of the last launch takes a trip
 constexpr int FILL_MAX_GRID = 1024;             // blocks of the last launch: 32768 segments a trip
 constexpr unsigned int BORDER = 0x80000000u;    // of area[root]; the low 31 bits are the area (npix < 2^31)
 
-struct Shape {
-  int Z, Y, X, nseg;
-  long long nwaves;                             // Z * Y * nseg
+struct Shape : Segments {
   int zlinks;                                   // 3-D without planewise: z neighbours exist
 };
 
@@ -50,39 +48,14 @@ struct Attr {                                   // planes of the workspace, read
   int* hi;
 };
 
-struct Pos { long long i; int x, y, z; bool valid; };
-__device__ __forceinline__ Pos pos_of(long long w, const Shape& s, int lane) {
-  const long long row = w / s.nseg;
-  Pos p;
-  p.x = (int)(w - row * s.nseg) * 64 + lane;
-  p.valid = p.x < s.X;
-  p.y = (int)(row % s.Y);
-  p.z = (int)(row / s.Y);
-  p.i = row * s.X + p.x;
-  return p;
-}
-
-// lane of the first pixel of this lane's run of zeros inside the segment (other lanes: themselves); all lanes call it
-__device__ __forceinline__ int zero_run_start(bool zero, int lane, unsigned long long* starts_out) {
-  const int zl = __shfl_up((int)zero, 1, 64);
-  const bool same_left = lane > 0 && zero && zl;
-  const unsigned long long starts = __ballot(!same_left);
-  *starts_out = starts;
-  return 63 - __builtin_clzll(starts & ((2ull << lane) - 1ull));
-}
-__device__ __forceinline__ bool run_ends_here(unsigned long long starts, int lane) { return lane == 63 || ((starts >> (lane + 1)) & 1ull); }
-
-#define HOLES_FOR_EACH_SEGMENT(w)                                                                       \
-  for (long long w = ((long long)blockIdx.x * BLOCK + threadIdx.x) >> 6; w < s.nwaves;                   \
-       w += ((long long)gridDim.x * BLOCK) >> 6)
-
 __global__ __launch_bounds__(BLOCK) void holes_runs(const int* __restrict__ labels, Attr a, Shape s) {
   const int lane = threadIdx.x & 63;
-  HOLES_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const bool zero = p.valid && labels[p.i] == 0;
-    unsigned long long starts;
-    const int st = zero_run_start(zero, lane, &starts);
+    const bool left_zero = __shfl_up((int)zero, 1, 64);
+    const Runs runs = run_start_lane(zero && left_zero, lane);         // the runs of zeros
+    const int st = runs.start;
     if (!p.valid) continue;
     a.parent[p.i] = zero ? (int)(p.i - lane + st) : -1;
     if (zero && st == lane) {
@@ -96,8 +69,8 @@ __global__ __launch_bounds__(BLOCK) void holes_runs(const int* __restrict__ labe
 __global__ __launch_bounds__(BLOCK) void holes_link(const int* __restrict__ labels, int* parent, Shape s) {
   const int lane = threadIdx.x & 63;
   const long long slice = (long long)s.Y * s.X;
-  HOLES_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const bool zero = p.valid && labels[p.i] == 0;
     const bool left_in_run = __shfl_up((int)zero, 1, 64) && lane > 0;     // the left lane is a zero of this run
     if (!zero) continue;
@@ -111,17 +84,18 @@ __global__ __launch_bounds__(BLOCK) void holes_link(const int* __restrict__ labe
 
 __global__ __launch_bounds__(BLOCK) void holes_flatten(Attr a, Shape s) {
   const int lane = threadIdx.x & 63;
-  HOLES_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const bool zero = p.valid && a.parent[p.i] >= 0;
     if (__ballot(zero) == 0ull) continue;
-    unsigned long long starts;
-    const int st = zero_run_start(zero, lane, &starts);
+    const bool left_zero = __shfl_up((int)zero, 1, 64);
+    const Runs runs = run_start_lane(zero && left_zero, lane);         // the runs of zeros
+    const int st = runs.start;
     int root = (zero && st == lane) ? uf_find(a.parent, (int)p.i) : -1;
     root = __shfl(root, st, 64);
     if (zero) a.parent[p.i] = root;                      // roots keep pointing at themselves
     const bool row_on_border = p.y == 0 || p.y == s.Y - 1 || (s.zlinks && (p.z == 0 || p.z == s.Z - 1));
-    const bool touches = zero && run_ends_here(starts, lane) && (row_on_border || p.x == s.X - 1 || p.x - (lane - st) == 0);
+    const bool touches = zero && run_ends_here(runs.starts, lane) && (row_on_border || p.x == s.X - 1 || p.x - (lane - st) == 0);
     // one atomic per root and wave; a look first (it may be stale: then the atomic is merely repeated, the bit is only ever set)
     for (unsigned long long todo = __ballot(touches); todo != 0ull;) {
       const int leader = __builtin_ctzll(todo);
@@ -136,15 +110,16 @@ __global__ __launch_bounds__(BLOCK) void holes_flatten(Attr a, Shape s) {
 __global__ __launch_bounds__(BLOCK) void holes_reduce(const int* __restrict__ labels, Attr a, Shape s) {
   const int lane = threadIdx.x & 63;
   const long long slice = (long long)s.Y * s.X;
-  HOLES_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const int root = p.valid ? a.parent[p.i] : -1;
     const bool zero = root >= 0;
     // (the border bits are final: the launch before set them)
     const bool inner = zero && !(a.area[zero ? root : 0] & BORDER);
     if (__ballot(inner) == 0ull) continue;
-    unsigned long long starts;
-    const int st = zero_run_start(zero, lane, &starts);
+    const bool left_zero = __shfl_up((int)zero, 1, 64);
+    const Runs runs = run_start_lane(zero && left_zero, lane);         // the runs of zeros
+    const int st = runs.start;
     int mn = INT_MAX, mx = INT_MIN;
     if (inner) {
       // an inner component does not reach the border: its pixels have all their face neighbours inside the map
@@ -165,7 +140,7 @@ __global__ __launch_bounds__(BLOCK) void holes_reduce(const int* __restrict__ la
       const int tn = __shfl_up(mn, d, 64), tx = __shfl_up(mx, d, 64);
       if (lane - d >= st) { mn = min(mn, tn); mx = max(mx, tx); }
     }
-    if (inner && run_ends_here(starts, lane)) {
+    if (inner && run_ends_here(runs.starts, lane)) {
       atomicAdd(&a.area[root], (unsigned int)(lane - st + 1));
       if (mn <= mx) {
         atomicMin(&a.lo[root], mn);
@@ -183,7 +158,6 @@ __global__ __launch_bounds__(BLOCK) void holes_fill(const int* __restrict__ labe
   constexpr int WAVES = BLOCK / 64;
   __shared__ int wave_holes[WAVES];
   __shared__ int block_base;
-  __shared__ int wave_sums[2][WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long ngroups = (s.nwaves + WAVES * FILL_SEGS - 1) / (WAVES * FILL_SEGS);
   int ncomp = 0, filled = 0;                    // of this lane's pixels; summed over the block after the loop
@@ -199,7 +173,7 @@ __global__ __launch_bounds__(BLOCK) void holes_fill(const int* __restrict__ labe
       first[r] = owner[r] = size[r] = 0;
       kept[r] = false;
       if (w < s.nwaves) {
-        const Pos p = pos_of(w, s, lane);
+        const SegPos p = seg_pos(w, s, lane);
         const int v = p.valid ? labels[p.i] : 1;
         int value = v;
         if (v == 0) {
@@ -237,7 +211,7 @@ __global__ __launch_bounds__(BLOCK) void holes_fill(const int* __restrict__ labe
     for (int k = 0; k < wave; ++k) slot += wave_holes[k];
 #pragma unroll
     for (int r = 0; r < FILL_SEGS; ++r) {
-      const int at = slot + __popcll(hb[r] & ((1ull << lane) - 1ull));
+      const int at = slot + rank_below(hb[r], lane);
       if (((hb[r] >> lane) & 1ull) && at < capacity) {
         int* row = holes + 4ll * at;
         row[0] = first[r];
@@ -249,21 +223,7 @@ __global__ __launch_bounds__(BLOCK) void holes_fill(const int* __restrict__ labe
     }
     __syncthreads();                            // the next trip writes wave_holes and block_base again
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ncomp += __shfl_down(ncomp, o, 64);
-    filled += __shfl_down(filled, o, 64);
-  }
-  if (lane == 0) {
-    wave_sums[0][wave] = filled;
-    wave_sums[1][wave] = ncomp;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    int total = 0;
-    for (int k = 0; k < WAVES; ++k) total += wave_sums[threadIdx.x][k];
-    if (total) atomicAdd(&info[1 + threadIdx.x], total);
-  }
+  block_add2(filled, ncomp, info + 1);
 }
 
 }  // namespace
@@ -287,27 +247,19 @@ extern "C" int clx_label_holes(const int32_t* labels, int nd, int Z, int Y, int 
   CLX_REQUIRE(((uintptr_t)workspace & 3) == 0, "clx_label_holes: workspace must be 4-byte aligned");
   CLX_REQUIRE(out != labels, "clx_label_holes: in-place operation is not supported");
   hipStream_t st = (hipStream_t)stream;
-  Shape s;
-  s.Z = Z;
-  s.Y = Y;
-  s.X = X;
-  s.nseg = (X + 63) / 64;
-  s.nwaves = (long long)Z * Y * s.nseg;
-  s.zlinks = nd == 3 && !planewise;
+  const Shape s = {segments_of(Z, Y, X), nd == 3 && !planewise};
   Attr a;
   a.parent = (int*)workspace;
   a.area = (unsigned int*)(a.parent + npix);
   a.lo = (int*)(a.area + npix);
   a.hi = a.lo + npix;
-  const long long blocks = (s.nwaves * 64 + BLOCK - 1) / BLOCK;
-  const int grid = (int)(blocks < MAX_GRID ? blocks : MAX_GRID);
+  const int grid = segment_grid(s.nwaves, HOLES_MAX_GRID);
   CLX_REQUIRE(hipMemsetAsync(info, 0, 4 * sizeof(int), st) == hipSuccess, "clx_label_holes: hipMemsetAsync failed");
   holes_runs<<<grid, BLOCK, 0, st>>>(labels, a, s);
   holes_link<<<grid, BLOCK, 0, st>>>(labels, a.parent, s);
   holes_flatten<<<grid, BLOCK, 0, st>>>(a, s);
   holes_reduce<<<grid, BLOCK, 0, st>>>(labels, a, s);
-  const long long groups = (s.nwaves + (BLOCK / 64) * FILL_SEGS - 1) / ((BLOCK / 64) * FILL_SEGS);
-  holes_fill<<<(int)(groups < FILL_MAX_GRID ? groups : FILL_MAX_GRID), BLOCK, 0, st>>>(labels, a, s, max_size, capacity, out, holes, info);
+  holes_fill<<<grid_for(s.nwaves, (BLOCK / 64) * FILL_SEGS, FILL_MAX_GRID), BLOCK, 0, st>>>(labels, a, s, max_size, capacity, out, holes, info);
   CLX_CHECK_LAUNCH("clx_label_holes");
   return CLX_OK;
 }

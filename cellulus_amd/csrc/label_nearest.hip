@@ -116,11 +116,6 @@ __global__ __launch_bounds__(BLOCK) void nearest_pass_axis(const int* __restrict
   }
 }
 
-inline int grid_for(long long items, int per_block) {
-  const long long g = (items + per_block - 1) / per_block;
-  return (int)(g < PASS_MAX_GRID ? g : PASS_MAX_GRID);
-}
-
 }  // namespace
 
 extern "C" size_t clx_label_nearest_workspace(long long npix) {
@@ -151,8 +146,8 @@ extern "C" int clx_label_nearest(const int32_t* labels, int nd, int Z, int Y, in
   int* bid = nd == 2 ? nearest : wid;
   int* bd2 = nd == 2 ? dist_sq : wd2;
   const long long rows = (long long)Z * Y;
-  const int grid = grid_for(npix, BLOCK);
-  nearest_pass_x<<<grid_for(rows, ROW_WAVES), BLOCK, 0, st>>>(labels, aid, ad2, X, rows, nid, cap, bad);
+  const int grid = grid_for(npix, BLOCK, PASS_MAX_GRID);
+  nearest_pass_x<<<grid_for(rows, ROW_WAVES, PASS_MAX_GRID), BLOCK, 0, st>>>(labels, aid, ad2, X, rows, nid, cap, bad);
   nearest_pass_axis<<<grid, BLOCK, 0, st>>>(aid, ad2, bid, bd2, Y, (long long)X, npix, cap);
   if (nd == 3) nearest_pass_axis<<<grid, BLOCK, 0, st>>>(bid, bd2, nearest, dist_sq, Z, (long long)X * Y, npix, cap);
   CLX_CHECK_LAUNCH("clx_label_nearest");

@@ -5,9 +5,10 @@
 //
 // Thinning is a synchronous rule on 3 x 3 neighbourhoods, a boolean function of nine bits: the pixel is alive, and for each of
 // its eight neighbours "it lies in the slice, carries my label and is alive".  The labels are read ONCE:
-//   init       a wave takes 64 pixels of a row and ballots ten bit planes, one 64-bit word per 64 pixels along x (bit i of word
-//              w of a row is pixel x = 64 w + i): the alive plane, twice, and eight SAME planes, "neighbour k lies in my slice
-//              and has my non-zero label".  Since alive pixels are object pixels, Pk = SAME_k & alive(neighbour k) from then on
+//   init       a wave takes a segment (segments.h has the frame of this pass, of write and of the census) and ballots ten bit
+//              planes, one 64-bit word per segment (bit i of word w of a row is pixel x = 64 w + i): the alive plane, twice,
+//              and eight SAME planes, "neighbour k lies in my slice and has my non-zero label".  Since alive pixels are object
+//              pixels, Pk = SAME_k & alive(neighbour k) from then on
 //   steps      one launch advances the whole map by up to 8 iterations (16 sub-iterations).  A block of 256 threads takes an
 //              EXTENT of 8 words x 128 rows (512 x 128 pixels): a TILE of 6 words x 96 rows and a halo of one word (64 pixels)
 //              left and right and 16 rows above and below.  A thread owns 4 words of the extent: their SAME words stay in its
@@ -32,6 +33,7 @@
 //              leaves the launch count and the last word in the head for a call with resume == 1; `write` forms out from the
 //              labels and the current plane.
 // Integers only, in fact bits; the labels are compared and never an index.  The same bits in every run.
+#include "segments.h"
 #include "skeleton_links.h"
 #include "tile_rounds.h"
 
@@ -47,12 +49,11 @@ constexpr int MAX_ITERATIONS = 64;              // iterations a call queues at m
 constexpr int MAX_LAUNCHES = MAX_ITERATIONS / LAUNCH_ITERATIONS;
 constexpr int THIN_MAX_GRID = 1024;             // blocks a launch; each takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
 constexpr int PLANE_MAX_GRID = 2048;            // blocks of the passes over the words (init, write, census)
+constexpr int CENSUS_INIT_MAX_GRID = 1024;      // blocks of 256 words of the census table
 constexpr int PAD = 16;                         // zero words before and after an LDS buffer: a neighbour is at most 9 words away
 constexpr int NWORDS = 10;                      // words per label of the census
 
-struct Shape {
-  int Z, Y, X, W;                               // W: words per row
-  long long nwords;                             // Z * Y * W
+struct Shape : Segments {                       // a word of a bit plane is a segment: nseg words per row, nwaves in all
   int ntx, nty;                                 // tiles per slice
   long long ntiles;
 };
@@ -60,7 +61,7 @@ struct Shape {
 struct Bits {                                   // the workspace
   int* head;                                    // [HEAD_WORDS]: [0] launches so far, [1] pixels the last iteration deleted (or 1)
   int* counters;                                // [MAX_LAUNCHES][2]
-  u64* same;                                    // [8][nwords]: N, NE, E, SE, S, SW, W, NW
+  u64* same;                                    // [8][nwaves]: N, NE, E, SE, S, SW, W, NW
   u64* alive0;                                  // read by the even launches
   u64* alive1;
   unsigned char* flag0;                         // written by the even launches
@@ -69,49 +70,25 @@ struct Bits {                                   // the workspace
 
 // the words and the tiles of a checked map: Z * Y * X < 2^31
 inline Shape thin_shape(int Z, int Y, int X) {
-  Shape s;
-  s.Z = Z;
-  s.Y = Y;
-  s.X = X;
-  s.W = (X + 63) / 64;
-  s.nwords = (long long)Z * Y * s.W;
-  s.ntx = (s.W + TW - 1) / TW;
+  Shape s = {segments_of(Z, Y, X), 0, 0, 0};
+  s.ntx = (s.nseg + TW - 1) / TW;
   s.nty = (Y + TR - 1) / TR;
   s.ntiles = (long long)Z * s.nty * s.ntx;
   return s;
 }
 inline size_t thin_flag_bytes(long long ntiles) { return ((size_t)ntiles + 7) & ~(size_t)7; }
-inline int plane_grid(long long nwords) {
-  const long long blocks = (nwords * 64 + BLOCK - 1) / BLOCK;
-  return (int)(blocks < PLANE_MAX_GRID ? blocks : PLANE_MAX_GRID);
-}
 
-#define THIN_FOR_EACH_WORD(w)                                                                           \
-  for (long long w = ((long long)blockIdx.x * BLOCK + threadIdx.x) >> 6; w < s.nwords;                   \
-       w += ((long long)gridDim.x * BLOCK) >> 6)
-
-// a lane's pixel of word w
-struct At { long long p; int x, y; bool in; };
-__device__ __forceinline__ At at_of(long long w, const Shape& s, int lane) {
-  const long long row = w / s.W;
-  At a;
-  a.x = (int)(w - row * s.W) * 64 + lane;
-  a.y = (int)(row % s.Y);
-  a.in = a.x < s.X;
-  a.p = row * s.X + a.x;
-  return a;
-}
 // does neighbour (dx, dy) of the pixel lie in its slice?
-__device__ __forceinline__ bool has_neighbour(const At& a, const Shape& s, int dx, int dy) {
+__device__ __forceinline__ bool has_neighbour(const SegPos& a, const Shape& s, int dx, int dy) {
   return (dx < 0 ? a.x > 0 : dx > 0 ? a.x < s.X - 1 : true) && (dy < 0 ? a.y > 0 : dy > 0 ? a.y < s.Y - 1 : true);
 }
 
 __global__ __launch_bounds__(BLOCK) void thin_init(const int* __restrict__ labels, Bits b, Shape s) {
   const int lane = threadIdx.x & 63;
   if (blockIdx.x == 0 && threadIdx.x == 0) { b.head[0] = 0; b.head[1] = 1; }
-  THIN_FOR_EACH_WORD(w) {
-    const At a = at_of(w, s, lane);
-    const int v = a.in ? labels[a.p] : 0;
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos a = seg_pos(w, s, lane);
+    const int v = a.valid ? labels[a.i] : 0;
     const bool obj = v != 0;
     const u64 alive = __ballot(obj);
     if (lane == 8) b.alive0[w] = alive;
@@ -119,9 +96,9 @@ __global__ __launch_bounds__(BLOCK) void thin_init(const int* __restrict__ label
     constexpr int DX[8] = {0, 1, 1, 1, 0, -1, -1, -1}, DY[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const bool same = obj && has_neighbour(a, s, DX[k], DY[k]) && labels[a.p + (long long)DY[k] * s.X + DX[k]] == v;
+      const bool same = obj && has_neighbour(a, s, DX[k], DY[k]) && labels[a.i + (long long)DY[k] * s.X + DX[k]] == v;
       const u64 m = __ballot(same);
-      if (lane == k) b.same[k * s.nwords + w] = m;
+      if (lane == k) b.same[k * s.nwaves + w] = m;
     }
   }
 }
@@ -182,13 +159,13 @@ __global__ __launch_bounds__(BLOCK) void thin_steps(Bits b, int k, int iteration
     for (int m = 0; m < WPT; ++m) {
       const int er = er0 + m * (BLOCK / EW);
       const int y = ty * TR - HALO_R + er;
-      const bool in = (unsigned int)wc < (unsigned int)s.W && (unsigned int)y < (unsigned int)s.Y;
-      gw[m] = ((long long)tz * s.Y + y) * s.W + wc;
+      const bool in = (unsigned int)wc < (unsigned int)s.nseg && (unsigned int)y < (unsigned int)s.Y;
+      gw[m] = ((long long)tz * s.Y + y) * s.nseg + wc;
       mine[m] = in && cin && er >= HALO_R && er < ER - HALO_R;
       const u64 a = in ? src[gw[m]] : 0ull;
       buf[0][PAD + threadIdx.x + m * BLOCK] = a;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) same[m][q] = a ? b.same[q * s.nwords + gw[m]] : 0ull;     // a dead word stays dead
+      for (int q = 0; q < 8; ++q) same[m][q] = a ? b.same[q * s.nwaves + gw[m]] : 0ull;     // a dead word stays dead
     }
     __syncthreads();
 
@@ -259,10 +236,10 @@ __global__ void thin_finish(int* __restrict__ head, const int* __restrict__ coun
 __global__ __launch_bounds__(BLOCK) void thin_write(const int* __restrict__ labels, Bits b, Shape s, int* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const u64* __restrict__ alive = ((unsigned int)b.head[0] & 1u) ? b.alive1 : b.alive0;
-  THIN_FOR_EACH_WORD(w) {
-    const At a = at_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos a = seg_pos(w, s, lane);
     const u64 bits = alive[w];
-    if (a.in) out[a.p] = ((bits >> lane) & 1ull) ? labels[a.p] : 0;
+    if (a.valid) out[a.i] = ((bits >> lane) & 1ull) ? labels[a.i] : 0;
   }
 }
 
@@ -310,18 +287,18 @@ __global__ __launch_bounds__(BLOCK) void census_kernel(const int* __restrict__ l
 
   const int lane = threadIdx.x & 63;
   int flags = 0;
-  THIN_FOR_EACH_WORD(w) {
-    const At a = at_of(w, s, lane);
-    int v = a.in ? lab[a.p] : 0;
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos a = seg_pos(w, s, lane);
+    int v = a.valid ? lab[a.i] : 0;
     if ((unsigned int)v >= (unsigned int)nid) { v = 0; flags |= 1; }
     Census r = {0u, 0u, 0ull, CLX_DIST_INF, -1};
     if (v != 0) {
-      const Links l = links_at(lab, a.p, a.x, a.y, s.Y, s.X, v);      // (v lies in [1, nid): so does a neighbour that carries v)
+      const Links l = links_at(lab, a.i, a.x, a.y, s.Y, s.X, v);      // (v lies in [1, nid): so does a neighbour that carries v)
       const int degree = l.degree();
       r.c0 = 1u | (unsigned int)l.owned_face() << 8 | (unsigned int)l.owned_diag() << 16 | (unsigned int)l.block << 24;
       r.c1 = (unsigned int)(degree == 1) | (unsigned int)(degree >= 3) << 8 | (unsigned int)(degree == 0) << 16;
       if (dist) {
-        const int d = dist[a.p];
+        const int d = dist[a.i];
         if (d < 0 || d >= CLX_DIST_INF) flags |= 2;
         else { r.sum = (u64)d; r.mn = r.mx = d; }
       }
@@ -368,7 +345,7 @@ extern "C" size_t clx_label_thin_workspace(int nd, int Z, int Y, int X) {
   long long npix;
   if (clx_map_shape(nullptr, nd, Z, Y, X, 31, &npix) != CLX_OK) return 0;
   const Shape s = thin_shape(Z, Y, X);
-  return (size_t)(HEAD_WORDS + 2 * MAX_LAUNCHES) * sizeof(int) + (size_t)s.nwords * 10 * sizeof(u64) + 2 * thin_flag_bytes(s.ntiles);
+  return (size_t)(HEAD_WORDS + 2 * MAX_LAUNCHES) * sizeof(int) + (size_t)s.nwaves * 10 * sizeof(u64) + 2 * thin_flag_bytes(s.ntiles);
 }
 
 extern "C" int clx_label_thin(const int32_t* labels, int nd, int Z, int Y, int X, int iterations, int resume, int32_t* out,
@@ -387,15 +364,15 @@ extern "C" int clx_label_thin(const int32_t* labels, int nd, int Z, int Y, int X
   b.head = (int*)workspace;
   b.counters = b.head + HEAD_WORDS;
   b.same = (u64*)(b.counters + 2 * MAX_LAUNCHES);
-  b.alive0 = b.same + 8 * s.nwords;
-  b.alive1 = b.alive0 + s.nwords;
-  b.flag0 = (unsigned char*)(b.alive1 + s.nwords);
+  b.alive0 = b.same + 8 * s.nwaves;
+  b.alive1 = b.alive0 + s.nwaves;
+  b.flag0 = (unsigned char*)(b.alive1 + s.nwaves);
   b.flag1 = b.flag0 + thin_flag_bytes(s.ntiles);
   CLX_REQUIRE(hipMemsetAsync(info, 0, 3 * sizeof(int), st) == hipSuccess, "clx_label_thin: hipMemsetAsync failed");
   CLX_REQUIRE(hipMemsetAsync(b.counters, 0, 2 * MAX_LAUNCHES * sizeof(int), st) == hipSuccess, "clx_label_thin: hipMemsetAsync failed");
-  const int pgrid = plane_grid(s.nwords);
+  const int pgrid = segment_grid(s.nwaves, PLANE_MAX_GRID);
   if (!resume) thin_init<<<pgrid, BLOCK, 0, st>>>(labels, b, s);
-  const int grid = (int)(s.ntiles < THIN_MAX_GRID ? s.ntiles : THIN_MAX_GRID);
+  const int grid = grid_for(s.ntiles, 1, THIN_MAX_GRID);
   const int launches = (iterations + LAUNCH_ITERATIONS - 1) / LAUNCH_ITERATIONS;
   for (int k = 0; k < launches; ++k) {
     const int left = iterations - k * LAUNCH_ITERATIONS;
@@ -414,9 +391,8 @@ extern "C" int clx_skeleton_census(const int32_t* skeleton, const int32_t* dist_
   const Shape s = thin_shape(Z, Y, X);
   CLX_REQUIRE(nid >= 1 && nid <= (1 << 24), "clx_skeleton_census: nid must lie in [1, 2^24]");
   hipStream_t st = (hipStream_t)stream;
-  const long long cells = (long long)nid * NWORDS, blocks = (cells + 255) / 256;
-  census_init<<<(int)(blocks < 1024 ? blocks : 1024), 256, 0, st>>>(words, bad, nid);
-  census_kernel<<<plane_grid(s.nwords), BLOCK, 0, st>>>(skeleton, dist_sq, s, nid, words, bad);
+  census_init<<<grid_for((long long)nid * NWORDS, 256, CENSUS_INIT_MAX_GRID), 256, 0, st>>>(words, bad, nid);
+  census_kernel<<<segment_grid(s.nwaves, PLANE_MAX_GRID), BLOCK, 0, st>>>(skeleton, dist_sq, s, nid, words, bad);
   CLX_CHECK_LAUNCH("clx_skeleton_census");
   return CLX_OK;
 }

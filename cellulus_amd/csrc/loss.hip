@@ -7,12 +7,7 @@
 namespace {
 
 // (every block ends with three float64 atomics on the SAME three addresses: few, fat blocks)
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 1024) g = 1024;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int LOSS_MAX_GRID = 1024;   // blocks of a grid-stride launch
 
 // linear index of coordinate row `co` (x = last axis first) in a (Z, Y, X) grid, with the
 // index rules of the advanced indexing the reference uses (unet.py:113-118): -n..-1 wrap
@@ -308,7 +303,7 @@ extern "C" int clx_sample_pairs(long long* anchor, long long* reference, const i
               "clx_sample_pairs: bad extents");
   for (int d = 0; d < ND; ++d) CLX_REQUIRE(hi[d] >= lo, "clx_sample_pairs: empty anchor range");
   const long long total = (long long)B * num_anchors * num_refs;
-  sample_pairs_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  sample_pairs_kernel<<<grid_for(total, 256, LOSS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       anchor, reference, offsets, noffsets, num_anchors, num_refs, ND, lo, hi[0], hi[1], ND == 3 ? hi[2] : hi[1],
       seed, stream_id, total);
   CLX_CHECK_LAUNCH("clx_sample_pairs");
@@ -324,7 +319,7 @@ extern "C" int clx_gather_add_fwd(const float* offsets, const long long* coords,
   CLX_REQUIRE(ND == 3 || Z == 1, "clx_gather_add_fwd: Z must be 1 for 2-D");
   if (P == 0) return CLX_OK;
   const long long total = (long long)B * P;
-  gather_add_fwd_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  gather_add_fwd_kernel<<<grid_for(total, 256, LOSS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       offsets, coords, sel, P, ND, Z, Y, X, (long long)Z * Y * X, total, oob_count);
   CLX_CHECK_LAUNCH("clx_gather_add_fwd");
   return CLX_OK;
@@ -339,7 +334,7 @@ extern "C" int clx_gather_add_bwd(const float* dsel, const long long* coords, fl
   CLX_REQUIRE(ND == 3 || Z == 1, "clx_gather_add_bwd: Z must be 1 for 2-D");
   if (P == 0) return CLX_OK;
   const long long total = (long long)B * P;
-  gather_add_bwd_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  gather_add_bwd_kernel<<<grid_for(total, 256, LOSS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       dsel, coords, doffsets, P, ND, Z, Y, X, (long long)Z * Y * X, total, oob_count);
   CLX_CHECK_LAUNCH("clx_gather_add_bwd");
   return CLX_OK;
@@ -352,7 +347,7 @@ extern "C" int clx_oce_loss_fwd_bwd(const float* a, const float* r, float* da, d
   CLX_REQUIRE(npairs >= 0 && (ND == 2 || ND == 3), "clx_oce_loss_fwd_bwd: bad extents");
   CLX_REQUIRE(temperature != 0.f, "clx_oce_loss_fwd_bwd: temperature must be non-zero");
   if (npairs == 0) return CLX_OK;
-  const int grid = grid_for(npairs, 256);
+  const int grid = grid_for(npairs, 256, LOSS_MAX_GRID);
   if (ND == 2)
     oce_loss_kernel<2><<<grid, 256, 0, (hipStream_t)stream>>>(a, r, da, sums, npairs, temperature, reg_weight, grad_scale);
   else
@@ -372,7 +367,7 @@ extern "C" int clx_oce_pairs_fused(const float* offsets, const long long* anchor
   CLX_REQUIRE(temperature != 0.f, "clx_oce_pairs_fused: temperature must be non-zero");
   if (P == 0) return CLX_OK;
   const long long total = (long long)B * P, npix = (long long)Z * Y * X;
-  const int grid = grid_for(total, 256);
+  const int grid = grid_for(total, 256, LOSS_MAX_GRID);
   if (ND == 2)
     oce_pairs_fused_kernel<2><<<grid, 256, 0, (hipStream_t)stream>>>(
         offsets, anchor, reference, doffsets, sums, P, Z, Y, X, npix, total, temperature, reg_weight);
@@ -402,7 +397,7 @@ extern "C" int clx_adam_step_guarded(float* param, const float* grad, float* exp
   const double bc2 = 1.0 - pow(beta2, (double)step);
   const float step_size = (float)(lr / bc1);
   const float bc2_sqrt = (float)sqrt(bc2);
-  adam_kernel<<<grid_for(n, 256), 256, 0, (hipStream_t)stream>>>(
+  adam_kernel<<<grid_for(n, 256, LOSS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       param, grad, exp_avg, exp_avg_sq, n, (float)(1.0 - beta1), (float)beta2,
       (float)(1.0 - beta2), (float)eps, (float)weight_decay, step_size, bc2_sqrt, skip_if_positive);
   CLX_CHECK_LAUNCH("clx_adam_step");

@@ -170,12 +170,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const int* __restrict__ seg
   }
 }
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int NUCLEUS_MAX_GRID = 4096;   // blocks of a grid-stride launch
 
 }  // namespace
 
@@ -187,7 +182,7 @@ extern "C" int clx_inst_stats(const int32_t* seg, const void* raw, int raw_type,
   hipStream_t st = (hipStream_t)stream;
   stats_init<<<(nid + 255) / 256, 256, 0, st>>>(bbox, vkey, nid);
   const long long npix = (long long)Z * Y * X;
-  const int grid = grid_for(npix, 256);
+  const int grid = grid_for(npix, 256, NUCLEUS_MAX_GRID);
   if (raw_type == CLX_RAW_F32) stats_kernel<float><<<grid, 256, 0, st>>>(seg, (const float*)raw, Z, Y, X, nid, bbox, vkey);
   else if (raw_type == CLX_RAW_F64) stats_kernel<double><<<grid, 256, 0, st>>>(seg, (const double*)raw, Z, Y, X, nid, bbox, vkey);
   else stats_kernel<int><<<grid, 256, 0, st>>>(seg, (const int*)raw, Z, Y, X, nid, bbox, vkey);
@@ -202,7 +197,7 @@ extern "C" int clx_inst_histogram(const int32_t* seg, const void* raw, int raw_t
   CLX_REQUIRE(npix > 0 && nid > 0 && nbins > 0, "clx_inst_histogram: bad sizes");
   CLX_REQUIRE(raw_type >= CLX_RAW_F32 && raw_type <= CLX_RAW_I32, "clx_inst_histogram: raw_type must be 0 (f32), 1 (f64) or 2 (i32)");
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for(npix, 256);
+  const int grid = grid_for(npix, 256, NUCLEUS_MAX_GRID);
   if (raw_type == CLX_RAW_F32)
     inst_hist_kernel<float><<<grid, 256, 0, st>>>(seg, (const float*)raw, npix, slot, nid, (const float*)edges_or_min, nbins, counts);
   else if (raw_type == CLX_RAW_F64)

@@ -146,12 +146,7 @@ __global__ void subpixel_fold_kernel(const float* __restrict__ g_skip, const flo
   }
 }
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int PACK_MAX_GRID = 4096;   // blocks of a grid-stride launch
 
 }  // namespace
 
@@ -189,7 +184,7 @@ extern "C" int clx_pack_weights(const float* w, float* wp, int cout, int cin, in
   CLX_REQUIRE(mode == CLX_PACK_FWD || mode == CLX_PACK_DGRAD, "clx_pack_weights: bad mode");
   const long long total = (mode == CLX_PACK_FWD) ? (long long)cout * taps * cin_pad
                                                  : (long long)cin_pad * taps * cout_pad;
-  pack_weights_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  pack_weights_kernel<<<grid_for(total, 256, PACK_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       w, wp, cout, cin, taps, cin_pad, cout_pad, mode, total);
   CLX_CHECK_LAUNCH("clx_pack_weights");
   return CLX_OK;
@@ -201,7 +196,7 @@ extern "C" int clx_unpack_wgrad(const float* dwpack, float* dw, int cout, int ci
   CLX_REQUIRE(cout > 0 && cin > 0 && taps > 0 && cin_pad >= cin && rows >= cout,
               "clx_unpack_wgrad: bad extents");
   const long long total = (long long)cout * cin * taps;
-  unpack_wgrad_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  unpack_wgrad_kernel<<<grid_for(total, 256, PACK_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       dwpack, dw, rows, cin, taps, cin_pad, total);
   CLX_CHECK_LAUNCH("clx_unpack_wgrad");
   return CLX_OK;
@@ -212,7 +207,7 @@ extern "C" int clx_planar_to_pixel(const float* planar, float* pixel, int B, int
   CLX_REQUIRE(planar && pixel && B > 0 && C > 0 && n > 0 && ld >= C,
               "clx_planar_to_pixel: bad arguments");
   const long long total = (long long)B * n;
-  planar_to_pixel_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  planar_to_pixel_kernel<<<grid_for(total, 256, PACK_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       planar, pixel, C, n, ld, total);
   CLX_CHECK_LAUNCH("clx_planar_to_pixel");
   return CLX_OK;
@@ -223,7 +218,7 @@ extern "C" int clx_pixel_to_planar(const float* pixel, float* planar, int B, int
   CLX_REQUIRE(planar && pixel && B > 0 && C > 0 && n > 0 && ld >= C,
               "clx_pixel_to_planar: bad arguments");
   const long long total = (long long)B * n;
-  pixel_to_planar_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+  pixel_to_planar_kernel<<<grid_for(total, 256, PACK_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       pixel, planar, C, n, ld, total);
   CLX_CHECK_LAUNCH("clx_pixel_to_planar");
   return CLX_OK;
@@ -250,7 +245,7 @@ extern "C" int clx_subpixel_split_weights(const float* w, float* w_skip, float* 
   if (rc) return rc;
   const long long n_skip = (long long)cout * C0 * kd * kh * kw;
   const long long n_eff = (long long)fz * fy * fx * N * g.C1 * g.zk[0] * g.zk[1] * g.zk[2];
-  subpixel_split_kernel<<<grid_for(n_skip + n_eff, 256), 256, 0, (hipStream_t)stream>>>(w, w_skip, weff, g, n_skip, n_eff);
+  subpixel_split_kernel<<<grid_for(n_skip + n_eff, 256, PACK_MAX_GRID), 256, 0, (hipStream_t)stream>>>(w, w_skip, weff, g, n_skip, n_eff);
   CLX_CHECK_LAUNCH("clx_subpixel_split_weights");
   return CLX_OK;
 }
@@ -264,7 +259,7 @@ extern "C" int clx_subpixel_fold_grads(const float* g_skip, const float* g_eff, 
   const int rc = sp_geom(g, cout, cin, C0, N, k, f, "clx_subpixel_fold_grads");
   if (rc) return rc;
   const long long total = (long long)cout * cin * kd * kh * kw;
-  subpixel_fold_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(g_skip, g_eff, gw, g, total);
+  subpixel_fold_kernel<<<grid_for(total, 256, PACK_MAX_GRID), 256, 0, (hipStream_t)stream>>>(g_skip, g_eff, gw, g, total);
   CLX_CHECK_LAUNCH("clx_subpixel_fold_grads");
   return CLX_OK;
 }

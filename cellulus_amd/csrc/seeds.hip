@@ -14,12 +14,7 @@
 
 namespace {
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 16384) g = 16384;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int SEEDS_MAX_GRID = 16384;   // blocks of a grid-stride launch
 
 __global__ void magnitude_kernel(const double* __restrict__ emb, double* __restrict__ out, int ND, long long npix) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix;
@@ -102,7 +97,7 @@ __global__ void negate_kernel(const double* __restrict__ in, double* __restrict_
 
 extern "C" int clx_offset_magnitude(const double* emb, double* out, int ND, long long npix, clx_stream stream) {
   CLX_REQUIRE(emb && out && ND >= 1 && npix > 0, "clx_offset_magnitude: bad arguments");
-  magnitude_kernel<<<grid_for(npix, 256), 256, 0, (hipStream_t)stream>>>(emb, out, ND, npix);
+  magnitude_kernel<<<grid_for(npix, 256, SEEDS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(emb, out, ND, npix);
   CLX_CHECK_LAUNCH("clx_offset_magnitude");
   return CLX_OK;
 }
@@ -115,7 +110,7 @@ extern "C" int clx_gaussian_filter_f64(const double* in, double* out, double* tm
   const long long npix = (long long)Z * Y * X;
   CLX_REQUIRE(npix < (1ll << 40), "clx_gaussian_filter_f64: too many pixels");
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for(npix, 256);
+  const int grid = grid_for(npix, 256, SEEDS_MAX_GRID);
   // axis order of scipy.ndimage.gaussian_filter: first axis first.  2-D: y, x.  3-D: z, y, x.
   // Ping-pong so that the last pass lands in `out`.
   if (Z > 1) {
@@ -132,7 +127,7 @@ extern "C" int clx_gaussian_filter_f64(const double* in, double* out, double* tm
 
 extern "C" int clx_negate_f64(const double* in, double* out, long long n, clx_stream stream) {
   CLX_REQUIRE(in && out && n > 0, "clx_negate_f64: bad arguments");
-  negate_kernel<<<grid_for(n, 256), 256, 0, (hipStream_t)stream>>>(in, out, n);
+  negate_kernel<<<grid_for(n, 256, SEEDS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(in, out, n);
   CLX_CHECK_LAUNCH("clx_negate_f64");
   return CLX_OK;
 }
@@ -147,7 +142,7 @@ extern "C" int clx_peak_local_max(const double* img, int Z, int Y, int X, const 
     clx_set_error("clx_peak_local_max: memset failed");
     return CLX_ERR_LAUNCH;
   }
-  peaks_kernel<<<grid_for((long long)Z * Y * X, 256), 256, 0, st>>>(img, Z, Y, X, minmax, peaks, capacity, npeaks);
+  peaks_kernel<<<grid_for((long long)Z * Y * X, 256, SEEDS_MAX_GRID), 256, 0, st>>>(img, Z, Y, X, minmax, peaks, capacity, npeaks);
   CLX_CHECK_LAUNCH("clx_peak_local_max");
   return CLX_OK;
 }

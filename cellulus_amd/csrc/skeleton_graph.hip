@@ -6,8 +6,8 @@
 // from the degree -- isolated 0, end 1, path 2, junction >= 3.  Nothing about a pixel is stored: a kernel that needs the kind
 // of a linked neighbour takes it from the labels again (object pixels are a few per cent of a thinned map).  Path pixels are
 // united over the links between two of them and junction pixels over the links between two of them by the lock-free union-find
-// of cc_label.hip (union_find.h) over raster indices; a set's root is its smallest pixel: a branch's `first`, a node's id.  A
-// wave owns 64 consecutive pixels of a row (a SEGMENT).  Six plain launches on the stream, no host synchronisation, and
+// of union_find.h over raster indices; a set's root is its smallest pixel: a branch's `first`, a node's id.  The passes walk
+// the map segment by segment (segments.h has the frame).  Six plain launches on the stream, no host synchronisation, and
 // between two of them nothing but the kernel boundary:
 //   1 classify  parent[i] = i on path and junction pixels, -1 elsewhere; these are the only possible roots: their attributes
 //               are cleared here
@@ -26,11 +26,12 @@
 //               single link
 // A path pixel has two links, so a branch has two terminal links or none (a cycle): the smallest and the largest terminal
 // pixel are all its terminals.
-// Correctness across blocks and XCDs rests on the values returned by atomics and on kernel boundaries alone (cc_label.hip's
+// Correctness across blocks and XCDs rests on the values returned by atomics and on kernel boundaries alone (union_find.h's
 // rule): no block waits for another, every loop ends because a parent strictly decreases.  Integer atomics only; ids are 32-bit
 // raster indices (npix < 2^31); values of the map are compared, never an index.  Everything the call writes is a function of
 // the input but the ORDER of the rows (the host sorts them by `first`).
 #include <limits.h>
+#include "segments.h"
 #include "skeleton_links.h"
 #include "union_find.h"
 
@@ -44,11 +45,6 @@ constexpr int BRANCH_WORDS = 13, NODE_WORDS = 7;
 constexpr int ISOLATED = 0, END = 1, PATH = 2, JUNCTION = 3;    // a pixel's kind; ISOLATED, END and JUNCTION are a node's too
 constexpr int END_END = 0, SPUR = 1, JUNCTION_JUNCTION = 2, CYCLE = 3;
 
-struct Shape {
-  int Z, Y, X, nseg;
-  long long nwaves;                             // Z * Y * nseg
-};
-
 struct Planes {                                 // the workspace: planes over raster indices, all but `parent` read at roots only
   u64* sum;                                     // branch: the sum of dist_sq over the path pixels
   int* parent;
@@ -61,30 +57,20 @@ struct Planes {                                 // the workspace: planes over ra
   int* mx;
 };
 
-struct Pos { long long i; int x, y; bool valid; };
-__device__ __forceinline__ Pos pos_of(long long w, const Shape& s, int lane) {
-  const long long row = w / s.nseg;
-  Pos p;
-  p.x = (int)(w - row * s.nseg) * 64 + lane;
-  p.valid = p.x < s.X;
-  p.y = (int)(row % s.Y);
-  p.i = row * s.X + p.x;
-  return p;
-}
 // the neighbour of p in direction k; it lies in the slice wherever p has a link in that direction
-__device__ __forceinline__ Pos towards(const Pos& p, const Shape& s, int k) {
-  return {p.i + (long long)LINK_DY[k] * s.X + LINK_DX[k], p.x + LINK_DX[k], p.y + LINK_DY[k], true};
+__device__ __forceinline__ SegPos towards(const SegPos& p, const Segments& s, int k) {
+  return {p.i + (long long)LINK_DY[k] * s.X + LINK_DX[k], p.row + LINK_DY[k], p.x + LINK_DX[k], p.y + LINK_DY[k], p.z, true};
 }
-__device__ __forceinline__ Pos pos_at(int i, const Shape& s) {
+__device__ __forceinline__ SegPos pos_at(int i, const Segments& s) {
   const int row = i / s.X;
-  return {(long long)i, i - row * s.X, row % s.Y, true};
+  return {(long long)i, (long long)row, i - row * s.X, row % s.Y, row / s.Y, true};
 }
 
 __device__ __forceinline__ int kind_of(const Links& l) {
   const int degree = l.degree();
   return degree >= 3 ? JUNCTION : degree;
 }
-__device__ __forceinline__ int kind_at(const int* __restrict__ lab, const Shape& s, const Pos& p, int v) {
+__device__ __forceinline__ int kind_at(const int* __restrict__ lab, const Segments& s, const SegPos& p, int v) {
   return kind_of(links_at(lab, p.i, p.x, p.y, s.Y, s.X, v));
 }
 
@@ -95,14 +81,10 @@ __device__ __forceinline__ bool spur_pruned(long long face, long long diag, long
   return 2 * D * D < (T - F) * (T - F);
 }
 
-#define GRAPH_FOR_EACH_SEGMENT(w)                                                                       \
-  for (long long w = ((long long)blockIdx.x * BLOCK + threadIdx.x) >> 6; w < s.nwaves;                   \
-       w += ((long long)gridDim.x * BLOCK) >> 6)
-
-__global__ __launch_bounds__(BLOCK) void graph_classify(const int* __restrict__ lab, Planes a, Shape s) {
+__global__ __launch_bounds__(BLOCK) void graph_classify(const int* __restrict__ lab, Planes a, Segments s) {
   const int lane = threadIdx.x & 63;
-  GRAPH_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     if (!p.valid) continue;
     const int v = lab[p.i];
     const int kind = v != 0 ? kind_at(lab, s, p, v) : ISOLATED;
@@ -119,10 +101,10 @@ __global__ __launch_bounds__(BLOCK) void graph_classify(const int* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(BLOCK) void graph_link(const int* __restrict__ lab, int* parent, Shape s) {
+__global__ __launch_bounds__(BLOCK) void graph_link(const int* __restrict__ lab, int* parent, Segments s) {
   const int lane = threadIdx.x & 63;
-  GRAPH_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const int v = p.valid ? lab[p.i] : 0;
     if (v == 0) continue;
     const Links l = links_at(lab, p.i, p.x, p.y, s.Y, s.X, v);
@@ -131,26 +113,26 @@ __global__ __launch_bounds__(BLOCK) void graph_link(const int* __restrict__ lab,
 #pragma unroll
     for (int k = 0; k < LINKS_OWNED; ++k)
       if (l.on[k]) {
-        const Pos q = towards(p, s, k);
+        const SegPos q = towards(p, s, k);
         if (kind_at(lab, s, q, v) == kind) uf_union(parent, (int)p.i, (int)q.i);
       }
   }
 }
 
-__global__ __launch_bounds__(BLOCK) void graph_flatten(int* parent, Shape s) {
+__global__ __launch_bounds__(BLOCK) void graph_flatten(int* parent, Segments s) {
   const int lane = threadIdx.x & 63;
-  GRAPH_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     if (p.valid && parent[p.i] >= 0) parent[p.i] = uf_find(parent, (int)p.i);        // roots keep pointing at themselves
   }
 }
 
-__global__ __launch_bounds__(BLOCK) void graph_reduce(const int* __restrict__ lab, const int* __restrict__ dist, Planes a, Shape s,
+__global__ __launch_bounds__(BLOCK) void graph_reduce(const int* __restrict__ lab, const int* __restrict__ dist, Planes a, Segments s,
                                                       int* __restrict__ info) {
   const int lane = threadIdx.x & 63;
   int flags = 0;
-  GRAPH_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     const int v = p.valid ? lab[p.i] : 0;
     if (v == 0) continue;
     const Links l = links_at(lab, p.i, p.x, p.y, s.Y, s.X, v);
@@ -161,7 +143,7 @@ __global__ __launch_bounds__(BLOCK) void graph_reduce(const int* __restrict__ la
 #pragma unroll
     for (int k = 0; k < 8; ++k)
       if (l.on[k]) {
-        const Pos q = towards(p, s, k);
+        const SegPos q = towards(p, s, k);
         const bool inner = kind_at(lab, s, q, v) == kind;
         if (kind == PATH) {
           if (!inner) {
@@ -199,7 +181,7 @@ struct Item {
   int other, other_kind;                // of an end pixel: the pixel its link leads to
   bool other_face;
 };
-__device__ __forceinline__ Item item_of(const int* __restrict__ lab, const int* __restrict__ parent, const Shape& s, const Pos& p) {
+__device__ __forceinline__ Item item_of(const int* __restrict__ lab, const int* __restrict__ parent, const Segments& s, const SegPos& p) {
   Item it = {0, ISOLATED, false, false, -1, ISOLATED, false};
   it.v = p.valid ? lab[p.i] : 0;
   if (it.v == 0) return it;
@@ -216,7 +198,7 @@ __device__ __forceinline__ Item item_of(const int* __restrict__ lab, const int* 
 #pragma unroll
     for (int k = 0; k < 8; ++k)
       if (l.on[k]) {
-        const Pos q = towards(p, s, k);
+        const SegPos q = towards(p, s, k);
         it.other = (int)q.i;
         it.other_kind = kind_at(lab, s, q, it.v);
         it.other_face = link_is_face(k);
@@ -226,11 +208,10 @@ __device__ __forceinline__ Item item_of(const int* __restrict__ lab, const int* 
   return it;
 }
 
-__global__ __launch_bounds__(BLOCK) void graph_emit(const int* __restrict__ lab, Planes a, Shape s, long long limit_q10, int capacity_b,
+__global__ __launch_bounds__(BLOCK) void graph_emit(const int* __restrict__ lab, Planes a, Segments s, long long limit_q10, int capacity_b,
                                                     int capacity_n, long long* __restrict__ branches, long long* __restrict__ nodes,
                                                     int* info) {
   constexpr int WAVES = BLOCK / 64;
-  __shared__ int wave_sums[2][WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long ngroups = (s.nwaves + EMIT_SEGS - 1) / EMIT_SEGS;
   int pruned_pixels = 0, pruned_spurs = 0;      // of this lane's pixels; summed over the block after the loop
@@ -241,7 +222,7 @@ __global__ __launch_bounds__(BLOCK) void graph_emit(const int* __restrict__ lab,
     for (int r = 0; r < EMIT_SEGS; ++r) {
       const long long w = g * EMIT_SEGS + r;
       Item it = {0, ISOLATED, false, false, -1, ISOLATED, false};
-      if (w < s.nwaves) it = item_of(lab, a.parent, s, pos_of(w, s, lane));
+      if (w < s.nwaves) it = item_of(lab, a.parent, s, seg_pos(w, s, lane));
       bb[r] = __ballot(it.branch);
       nb[r] = __ballot(it.node);
       nbranch += __popcll(bb[r]);
@@ -256,14 +237,13 @@ __global__ __launch_bounds__(BLOCK) void graph_emit(const int* __restrict__ lab,
     nslot = __shfl(nslot, 0, 64);
 #pragma unroll
     for (int r = 0; r < EMIT_SEGS; ++r) {
-      const u64 below = (1ull << lane) - 1ull;
       const bool has_branch = (bb[r] >> lane) & 1ull, has_node = (nb[r] >> lane) & 1ull;
       if (has_branch || has_node) {
-        const Pos p = pos_of(g * EMIT_SEGS + r, s, lane);
+        const SegPos p = seg_pos(g * EMIT_SEGS + r, s, lane);
         const int i = (int)p.i;
         const Item it = item_of(lab, a.parent, s, p);
         if (has_node) {
-          const int at = nslot + __popcll(nb[r] & below);
+          const int at = nslot + rank_below(nb[r], lane);
           if (at < capacity_n) {
             long long* row = nodes + (long long)NODE_WORDS * at;
             const bool cluster = it.kind == JUNCTION;
@@ -312,7 +292,7 @@ __global__ __launch_bounds__(BLOCK) void graph_emit(const int* __restrict__ lab,
             pruned_pixels += (int)pixels + 1;
             pruned_spurs += 1;
           }
-          const int at = bslot + __popcll(bb[r] & below);
+          const int at = bslot + rank_below(bb[r], lane);
           if (at < capacity_b) {
             long long* row = branches + (long long)BRANCH_WORDS * at;
             row[0] = i;
@@ -335,28 +315,14 @@ __global__ __launch_bounds__(BLOCK) void graph_emit(const int* __restrict__ lab,
       nslot += __popcll(nb[r]);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    pruned_pixels += __shfl_down(pruned_pixels, o, 64);
-    pruned_spurs += __shfl_down(pruned_spurs, o, 64);
-  }
-  if (lane == 0) {
-    wave_sums[0][wave] = pruned_pixels;
-    wave_sums[1][wave] = pruned_spurs;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    int total = 0;
-    for (int k = 0; k < WAVES; ++k) total += wave_sums[threadIdx.x][k];
-    if (total) atomicAdd(&info[2 + threadIdx.x], total);
-  }
+  block_add2(pruned_pixels, pruned_spurs, info + 2);
 }
 
-__global__ __launch_bounds__(BLOCK) void graph_write(const int* __restrict__ lab, Planes a, Shape s, long long limit_q10,
+__global__ __launch_bounds__(BLOCK) void graph_write(const int* __restrict__ lab, Planes a, Segments s, long long limit_q10,
                                                      int* __restrict__ branch_map, int* __restrict__ out) {
   const int lane = threadIdx.x & 63;
-  GRAPH_FOR_EACH_SEGMENT(w) {
-    const Pos p = pos_of(w, s, lane);
+  FOR_EACH_SEGMENT(w, s) {
+    const SegPos p = seg_pos(w, s, lane);
     if (!p.valid) continue;
     const int v = lab[p.i];
     int id = 0;                                 // of the branch map
@@ -374,7 +340,7 @@ __global__ __launch_bounds__(BLOCK) void graph_write(const int* __restrict__ lab
 #pragma unroll
           for (int k = 0; k < 8; ++k)
             if (l.on[k]) {
-              const Pos q = towards(p, s, k);
+              const SegPos q = towards(p, s, k);
               const int other = kind_at(lab, s, q, v);
               if (other == PATH) pruned = (unsigned int)a.pixels[a.parent[q.i]] & PRUNED;
               if (other == JUNCTION) pruned = spur_pruned(link_is_face(k), !link_is_face(k), limit_q10);
@@ -411,12 +377,7 @@ extern "C" int clx_skeleton_graph(const int32_t* labels, const int32_t* dist_sq,
   CLX_REQUIRE(out != labels && branch_map != labels, "clx_skeleton_graph: in-place operation is not supported");
   CLX_REQUIRE(!out || out != branch_map, "clx_skeleton_graph: out and branch_map must not be one buffer");
   hipStream_t st = (hipStream_t)stream;
-  Shape s;
-  s.Z = Z;
-  s.Y = Y;
-  s.X = X;
-  s.nseg = (X + 63) / 64;
-  s.nwaves = (long long)Z * Y * s.nseg;
+  const Segments s = segments_of(Z, Y, X);
   Planes a;
   a.sum = (u64*)workspace;
   a.parent = (int*)(a.sum + npix);
@@ -427,16 +388,14 @@ extern "C" int clx_skeleton_graph(const int32_t* labels, const int32_t* dist_sq,
   a.hi = a.lo + npix;
   a.mn = a.hi + npix;
   a.mx = a.mn + npix;
-  const long long blocks = (s.nwaves * 64 + BLOCK - 1) / BLOCK;
-  const int grid = (int)(blocks < GRAPH_MAX_GRID ? blocks : GRAPH_MAX_GRID);
+  const int grid = segment_grid(s.nwaves, GRAPH_MAX_GRID);
   CLX_REQUIRE(hipMemsetAsync(info, 0, 6 * sizeof(int), st) == hipSuccess, "clx_skeleton_graph: hipMemsetAsync failed");
   graph_classify<<<grid, BLOCK, 0, st>>>(labels, a, s);
   graph_link<<<grid, BLOCK, 0, st>>>(labels, a.parent, s);
   graph_flatten<<<grid, BLOCK, 0, st>>>(a.parent, s);
   graph_reduce<<<grid, BLOCK, 0, st>>>(labels, dist_sq, a, s, info);
-  const long long groups = (s.nwaves + (BLOCK / 64) * EMIT_SEGS - 1) / ((BLOCK / 64) * EMIT_SEGS);
-  graph_emit<<<(int)(groups < EMIT_MAX_GRID ? groups : EMIT_MAX_GRID), BLOCK, 0, st>>>(labels, a, s, limit_q10, capacity_b, capacity_n,
-                                                                                        branches, nodes, info);
+  graph_emit<<<grid_for(s.nwaves, (BLOCK / 64) * EMIT_SEGS, EMIT_MAX_GRID), BLOCK, 0, st>>>(labels, a, s, limit_q10, capacity_b,
+                                                                                            capacity_n, branches, nodes, info);
   if (branch_map || out) graph_write<<<grid, BLOCK, 0, st>>>(labels, a, s, limit_q10, branch_map, out);
   CLX_CHECK_LAUNCH("clx_skeleton_graph");
   return CLX_OK;

@@ -186,12 +186,7 @@ __global__ __launch_bounds__(256) void broadcast_rows_kernel(const f32x4* __rest
   }
 }
 
-inline int rows_grid(long long total) {
-  long long g = (total + 255) / 256;
-  if (g > 16384) g = 16384;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int ROWS_MAX_GRID = 16384;    // blocks of a grid-stride launch
 
 }  // namespace
 
@@ -218,9 +213,9 @@ extern "C" int clx_changed_rows(const float* clean, const float* noisy, int T, i
   unsigned long long* bits = (unsigned long long*)workspace;
   const int nw = (IW + 63) / 64, onw = (OW + 63) / 64;
   const long long nwords_copy = (long long)ID * IH * nw, total_words = (long long)T * nwords_copy;
-  diff_bits_kernel<<<rows_grid(total_words * 64), 256, 0, st>>>(clean, noisy, C, (long long)ID * IH * IW, IW, nw, nwords_copy,
+  diff_bits_kernel<<<grid_for(total_words * 64, 256, ROWS_MAX_GRID), 256, 0, st>>>(clean, noisy, C, (long long)ID * IH * IW, IW, nw, nwords_copy,
                                                                 total_words, bits);
-  dilate_rows_kernel<<<rows_grid((long long)T * OD * OH * onw), 256, 0, st>>>(bits, T, IH, nw, nwords_copy, KD, KH, KW, OD, OH,
+  dilate_rows_kernel<<<grid_for((long long)T * OD * OH * onw, 256, ROWS_MAX_GRID), 256, 0, st>>>(bits, T, IH, nw, nwords_copy, KD, KH, KW, OD, OH,
                                                                             OW, onw, chunk, rows, counts, cap,
                                                                             bits + input_bit_words(T, ID, IH, IW));
   CLX_CHECK_LAUNCH("clx_changed_rows");
@@ -242,7 +237,7 @@ extern "C" int clx_changed_tiles(const void* workspace, int T, int ID, int IH, i
   const int nchunks = (T + chunk - 1) / chunk;
   CLX_REQUIRE(hipMemsetAsync(counts, 0, sizeof(int) * nchunks, st) == hipSuccess, "clx_changed_tiles: hipMemsetAsync failed");
   const unsigned long long* row_bits = (const unsigned long long*)workspace + input_bit_words(T, ID, IH, IW);
-  changed_tiles_kernel<<<rows_grid((long long)T * th * tw), 256, 0, st>>>(row_bits, T, OH, OW, (OW + 63) / 64, WH, WW, tile, th,
+  changed_tiles_kernel<<<grid_for((long long)T * th * tw, 256, ROWS_MAX_GRID), 256, 0, st>>>(row_bits, T, OH, OW, (OW + 63) / 64, WH, WW, tile, th,
                                                                           tw, chunk, tiles, counts, cap);
   CLX_CHECK_LAUNCH("clx_changed_tiles");
   return CLX_OK;
@@ -256,7 +251,7 @@ extern "C" int clx_gather_rows(const float* src, int ld_src, const int* rows, lo
   CLX_REQUIRE(width > 0 && width % 4 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0 && width <= ld_src && width <= ld_dst,
               "clx_gather_rows: widths must be multiples of 4 floats");
   CLX_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "clx_gather_rows: 16-byte alignment");
-  gather_rows_kernel<<<rows_grid(n * (width / 4)), 256, 0, (hipStream_t)stream>>>(src, ld_src, rows, n, width / 4, dst, ld_dst);
+  gather_rows_kernel<<<grid_for(n * (width / 4), 256, ROWS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(src, ld_src, rows, n, width / 4, dst, ld_dst);
   CLX_CHECK_LAUNCH("clx_gather_rows");
   return CLX_OK;
 }
@@ -269,7 +264,7 @@ extern "C" int clx_scatter_rows(const float* src, int ld_src, const int* rows, l
   CLX_REQUIRE(width > 0 && width % 4 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0 && width <= ld_src && width <= ld_dst,
               "clx_scatter_rows: widths must be multiples of 4 floats");
   CLX_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "clx_scatter_rows: 16-byte alignment");
-  scatter_rows_kernel<<<rows_grid(n * (width / 4)), 256, 0, (hipStream_t)stream>>>(src, ld_src, rows, n, width / 4, dst, ld_dst);
+  scatter_rows_kernel<<<grid_for(n * (width / 4), 256, ROWS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(src, ld_src, rows, n, width / 4, dst, ld_dst);
   CLX_CHECK_LAUNCH("clx_scatter_rows");
   return CLX_OK;
 }
@@ -278,7 +273,7 @@ extern "C" int clx_broadcast_rows(const float* src, long long nfloats, float* ds
   CLX_REQUIRE(src && dst, "clx_broadcast_rows: null pointer");
   CLX_REQUIRE(nfloats > 0 && nfloats % 4 == 0 && copies >= 1, "clx_broadcast_rows: bad extents");
   CLX_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "clx_broadcast_rows: 16-byte alignment");
-  broadcast_rows_kernel<<<rows_grid(nfloats / 4), 256, 0, (hipStream_t)stream>>>(
+  broadcast_rows_kernel<<<grid_for(nfloats / 4, 256, ROWS_MAX_GRID), 256, 0, (hipStream_t)stream>>>(
       reinterpret_cast<const f32x4*>(src), nfloats / 4, reinterpret_cast<f32x4*>(dst), copies);
   CLX_CHECK_LAUNCH("clx_broadcast_rows");
   return CLX_OK;

@@ -136,11 +136,8 @@ inline bool rounds_begin(const Rounds& w, int* info, hipStream_t st) {
   return hipMemsetAsync(info, 0, 3 * sizeof(int), st) == hipSuccess &&
          hipMemsetAsync(w.counters, 0, MAX_ROUNDS * sizeof(int), st) == hipSuccess;
 }
-inline int init_grid(long long npix) {
-  const long long blocks = (npix + BLOCK - 1) / BLOCK;
-  return (int)(blocks < INIT_MAX_GRID ? blocks : INIT_MAX_GRID);
-}
-inline int round_grid(const TileGrid& g) { return (int)(g.ntiles < TILE_MAX_GRID ? g.ntiles : TILE_MAX_GRID); }
+inline int init_grid(long long npix) { return grid_for(npix, BLOCK, INIT_MAX_GRID); }
+inline int round_grid(const TileGrid& g) { return grid_for(g.ntiles, 1, TILE_MAX_GRID); }
 // a call's epilogue, after its `rounds` launches
 inline void rounds_end(const Rounds& w, int rounds, int* info, hipStream_t st) {
   rounds_finish<<<1, 64, 0, st>>>(w.head, w.counters, rounds, info);

@@ -1,7 +1,8 @@
-// The lock-free union-find the label kernels share (cc_label.hip, label_holes.hip).  L is a parent array over raster indices;
-// links always point from the larger root to the smaller, so the final root of a set is its smallest index.  Stale reads of
-// the parent array are harmless (parents only decrease along a chain; progress is made by the values returned from the
-// atomics).
+// The lock-free union-find the label kernels share (cc_label.hip, label_holes.hip, skeleton_graph.hip; the walk over the map
+// they unite in is segments.h's).  L is a parent array over raster indices; links always point from the larger root to the
+// smaller, so the final root of a set is its smallest index.  Stale reads of the parent array are harmless (parents only
+// decrease along a chain; progress is made by the values returned from the atomics).  The rule its users keep: correctness
+// across blocks and XCDs rests on the values returned by atomics and on kernel boundaries alone -- no block waits for another.
 // BIAS is the offset at which parents are stored: node i's parent is L[i] - BIAS, and a parent p is written as p + BIAS.
 // The default 0 stores the index itself; with BIAS = 1 the array can double as a label image whose background is 0
 // (cc_label.hip's 2-D pipeline).  Arguments and results are always plain indices.

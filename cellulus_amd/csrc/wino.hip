@@ -20,12 +20,7 @@
 
 namespace {
 
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 16384) g = 16384;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int WINO_MAX_GRID = 16384;   // blocks of a grid-stride launch
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
@@ -796,11 +791,11 @@ int wino_fwd_t(const clx_conv_desc* d, hipStream_t st) {
       const long long tot_in = sp_items(Tin, C);
       int rc = clx_sp_zero_tail(V, Tin, C, AA, pbV, st);
       if (rc) return rc;
-      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R, true>), dim3(grid_for(tot_in, 256)), dim3(256), 0, st, S.ptr, S.ld, C / 4,
+      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R, true>), dim3(grid_for(tot_in, 256, WINO_MAX_GRID)), dim3(256), 0, st, S.ptr, S.ld, C / 4,
                       gin, V, tot_in, list, Tin, pbV);
     } else {
       const long long tot_in = Tin * (C / 4);
-      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R>), dim3(grid_for(tot_in, 256)), dim3(256), 0, st, S.ptr, S.ld, C / 4, gin, V,
+      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R>), dim3(grid_for(tot_in, 256, WINO_MAX_GRID)), dim3(256), 0, st, S.ptr, S.ld, C / 4, gin, V,
                       tot_in, list, Tin, 0ll);
     }
   }
@@ -831,7 +826,7 @@ int wino_fwd_t(const clx_conv_desc* d, hipStream_t st) {
                     d->mask == nullptr && d->mask_bits == nullptr && !d->accumulate,
                 "clx_conv_fwd(winograd): pool_out needs N %% 4 == 0, an aligned ld_pool >= N, and no mask / accumulate");
   }
-  CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_output_kernel<MT, R>), dim3(grid_for(tot_out, 256)), dim3(256), 0, st, M, Np / 4, gout, d->bias,
+  CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_output_kernel<MT, R>), dim3(grid_for(tot_out, 256, WINO_MAX_GRID)), dim3(256), 0, st, M, Np / 4, gout, d->bias,
                   d->relu, d->mask, d->ld_mask, d->out, d->ld_out, d->N, d->accumulate, d->gate_out, d->ld_gate, d->mask_bits,
                   d->ld_mask_bits, d->pool_out, d->ld_pool, tot_out, list, Tout);
   CLX_CHECK_LAUNCH("clx_conv_fwd(winograd)");
@@ -853,11 +848,11 @@ int wino_wgrad_t(const clx_conv_desc* d, const float* dy, int ld_dy, float* dwpa
       const long long tot_in = sp_items(gin.T, C);
       int rc = clx_sp_zero_tail(V, gin.T, C, AA, pbV, st);
       if (rc) return rc;
-      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R, true>), dim3(grid_for(tot_in, 256)), dim3(256), 0, st, S.ptr, S.ld, C / 4,
+      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R, true>), dim3(grid_for(tot_in, 256, WINO_MAX_GRID)), dim3(256), 0, st, S.ptr, S.ld, C / 4,
                       gin, V, tot_in, (const int*)nullptr, 0ll, pbV);
     } else {
       const long long tot_in = gin.T * (C / 4);
-      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R>), dim3(grid_for(tot_in, 256)), dim3(256), 0, st, S.ptr, S.ld, C / 4, gin, V,
+      CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_input_kernel<MT, R>), dim3(grid_for(tot_in, 256, WINO_MAX_GRID)), dim3(256), 0, st, S.ptr, S.ld, C / 4, gin, V,
                       tot_in, (const int*)nullptr, 0ll, 0ll);
     }
   }
@@ -875,7 +870,7 @@ int wino_wgrad_t(const clx_conv_desc* d, const float* dy, int ld_dy, float* dwpa
     gd.th = (gd.OH + MT - 1) / MT; gd.tw = (gd.OW + MT - 1) / MT;
     gd.T = (long long)gd.B * gd.th * gd.tw;
     const long long tot = spx ? sp_items(gd.T, N) : gd.T * (N / 4);
-    int blocks = grid_for(tot, 256);
+    int blocks = grid_for(tot, 256, WINO_MAX_GRID);
     if (dbias && blocks > 2048) blocks = 2048;
     if (spx) {
       const long long pbD = sp::planes_bytes(gd.T, N);
@@ -889,7 +884,7 @@ int wino_wgrad_t(const clx_conv_desc* d, const float* dy, int ld_dy, float* dwpa
     }
   } else {
     const long long tot_dy = spx ? sp_items(gout.T, N) : gout.T * (N / 4);
-    int blocks = grid_for(tot_dy, 256);
+    int blocks = grid_for(tot_dy, 256, WINO_MAX_GRID);
     if (blocks > 2048) blocks = 2048;
     if (spx)
       CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, (wino_dy_kernel<MT, R, true>), dim3(blocks), dim3(256), (size_t)N * sizeof(float), st, dy, ld_dy, N / 4,
@@ -998,7 +993,7 @@ static int wino_adjoint(const clx_conv_desc* d, hipStream_t st) {
   const int IH = OHf + 2, IW = OWf + 2;
   const int nseg = ((IH + 3) / 4 + ADJ_SEG - 1) / ADJ_SEG;
   const long long total = (long long)d->B * planes_dx * nseg * ((IW + 3) / 4) * (Cp / 4);
-  CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, wino_adjoint_output_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, P, Cp / 4,
+  CLX_LAUNCH_KIND(CLX_PROF_WINO_TRANSFORM, wino_adjoint_output_kernel, dim3(grid_for(total, 256, WINO_MAX_GRID)), dim3(256), 0, st, P, Cp / 4,
                   d->B * planes_dx, th, tw, IH, IW, d->mask, d->ld_mask, d->mask_bits, d->ld_mask_bits, d->out, d->ld_out, Cp, total);
   CLX_CHECK_LAUNCH("clx_conv_fwd(winograd adjoint)");
   return CLX_OK;
@@ -1037,7 +1032,7 @@ int clx_wino_pack(const float* w, float* wp, int cout, int cin, int cin_pad, int
   if (fused) dgrad = 0;
   const int rows = dgrad ? cin_pad : cout_pad, cols = dgrad ? cout_pad : cin_pad;
   const long long total = (long long)rows * kd * cols;
-  const int grid = grid_for(total, 256);
+  const int grid = grid_for(total, 256, WINO_MAX_GRID);
   if (ksize == 2) wino_filter_kernel<4, 2><<<grid, 256, 0, st>>>(w, wp, cout, cin, rows, cols, kd, dgrad, total, fused);
   else if (tile == 4) wino_filter_kernel<4, 3><<<grid, 256, 0, st>>>(w, wp, cout, cin, rows, cols, kd, dgrad, total, fused);
   else wino_filter_kernel<2, 3><<<grid, 256, 0, st>>>(w, wp, cout, cin, rows, cols, kd, dgrad, total, fused);
@@ -1062,7 +1057,7 @@ extern "C" int clx_unpack_wgrad_wino(const float* du, float* dw, int cout, int c
               "clx_unpack_wgrad_wino: (tile, ksize) must be (2, 3), (4, 3) or (4, 2)");
   CLX_REQUIRE(kd == 1 || (kd == ksize && tile == 4), "clx_unpack_wgrad_wino: kd must be 1 or ksize (F(4x4) only)");
   const long long total = (long long)cout * cin * kd;
-  const int grid = grid_for(total, 256);
+  const int grid = grid_for(total, 256, WINO_MAX_GRID);
   hipStream_t st = (hipStream_t)stream;
   if (ksize == 2) wino_unpack_kernel<4, 2><<<grid, 256, 0, st>>>(du, dw, cout, cin, rows, cin_pad, kd, total);
   else if (tile == 4) wino_unpack_kernel<4, 3><<<grid, 256, 0, st>>>(du, dw, cout, cin, rows, cin_pad, kd, total);

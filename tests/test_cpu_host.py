@@ -72,6 +72,22 @@ def test_round_frame_and_map_check_are_defined_once():
         assert [n for n in names if piece in text[n]] == ["clx_core.hip"], piece
 
 
+def test_segment_frame_and_capped_grid_are_defined_once():
+    # the frame of the segment-walking label kernels (cc_label.hip's run pipeline, label_holes.hip, skeleton_graph.hip,
+    # label_thin.hip's plane passes) has one copy, segments.h, and the capped launch grid one, beside cdiv
+    csrc = os.path.join(ROOT, "cellulus_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    text = {n: open(os.path.join(csrc, n), encoding="utf-8").read() for n in names}
+    for piece in ("struct Segments", "SegPos seg_pos(", "define FOR_EACH_SEGMENT", "Runs run_start_lane(bool continues_left, int lane)",
+                  "bool run_ends_here(", "int rank_below(", "void block_add2(", "int segment_grid("):
+        assert [n for n in names if piece in text[n]] == ["segments.h"], piece
+    assert [n for n in names if "rank_below(" in text[n]] == ["label_holes.hip", "segments.h", "skeleton_graph.hip"]
+    assert [n for n in names if "inline int grid_for(" in text[n]] == ["clx_common.h"]
+    for piece in ("HOLES_FOR_EACH_SEGMENT", "GRAPH_FOR_EACH_SEGMENT", "THIN_FOR_EACH_WORD", "struct At {", "struct Pos {", "pos_of(", "at_of(",
+                  "zero_run_start(", "pass_grid(", "map_grid(", "plane_grid("):
+        assert [n for n in names if piece in text[n]] == [], piece
+
+
 def test_compile_command_ignores_the_environment(monkeypatch):
     from cellulus_amd import _build
 

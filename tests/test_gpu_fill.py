@@ -3,9 +3,9 @@ face structure; per component the border test, the dilation ring and the area). 
 rows sorted by their first pixel and info must be EQUAL in every element.  Outputs and the workspace are prefilled with 0xAB
 bytes and sit between guard words that must stay untouched.
 
-The constants below mirror csrc/label_holes.hip: a wave takes a SEGMENT of 64 pixels of a row; the first four launches have at
-most MAX_GRID blocks of 4 waves, beyond which a wave takes more than one segment; the last has at most FILL_MAX_GRID blocks,
-each of which takes 4 x FILL_SEGS segments a trip."""
+The constants below mirror csrc/label_holes.hip and csrc/segments.h: a wave takes a SEGMENT of 64 pixels of a row (segments.h);
+the first four launches have at most MAX_GRID (there: HOLES_MAX_GRID) blocks of 4 waves, beyond which a wave takes more than one
+segment; the last has at most FILL_MAX_GRID blocks, each of which takes 4 x FILL_SEGS segments a trip."""
 
 import ctypes
 

@@ -2,9 +2,9 @@
 bits and integers: every element of out, info and the census words must be EQUAL.  Outputs and the workspace are prefilled
 with 0xAB bytes and sit between guard words that must stay untouched.
 
-The constants below mirror csrc/label_thin.hip: a word is 64 pixels of a row; a block loads an extent of 8 words x 128 rows, a
-TILE of 6 words x 96 rows with a halo of one word / 16 rows; a launch runs at most 8 iterations, a call at most 64; a launch has
-at most 1024 blocks, beyond which a block takes more than one tile."""
+The constants below mirror csrc/label_thin.hip: a word is 64 pixels of a row (a segment of csrc/segments.h); a block loads an
+extent of 8 words x 128 rows, a TILE of 6 words x 96 rows with a halo of one word / 16 rows; a launch runs at most 8 iterations,
+a call at most 64; a launch has at most 1024 blocks, beyond which a block takes more than one tile."""
 
 import ctypes
 

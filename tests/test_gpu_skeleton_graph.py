@@ -3,9 +3,9 @@ branch rows and the node rows (sorted by first: their order is unspecified), eve
 be EQUAL.  Outputs and the workspace are prefilled with 0xAB bytes and sit between guard words that must stay untouched; rows
 beyond the counts must stay untouched too.
 
-The constants below mirror csrc/skeleton_graph.hip: a wave owns a SEGMENT, 64 consecutive pixels of a row, a block four
-segments; the plain launches have at most 2048 blocks (8192 segments a trip), the emit launch at most 1024 blocks whose waves
-take 8 segments a trip (32768 segments)."""
+The constants below mirror csrc/skeleton_graph.hip and csrc/segments.h: a wave owns a SEGMENT, 64 consecutive pixels of a row,
+a block four segments (segments.h); the plain launches have at most 2048 blocks (8192 segments a trip), the emit launch at most
+1024 blocks whose waves take 8 segments a trip (32768 segments)."""
 
 import ctypes
 

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Compares the gfx950 code of the measure / relate kernels of two source trees, symbol by symbol.
 
-    python tools/compare_kernel_isa.py OLD_TREE NEW_TREE [-o profiles/measure_kernels_isa.txt]
+    python tools/compare_kernel_isa.py OLD_TREE NEW_TREE [--all | --only FILE ...] [-o profiles/measure_kernels_isa.txt]
 
-Every measure source of a tree (csrc/measure.hip, region_*.hip, label_*.hip, nucleus.hip) is compiled to device-only assembly with
-_build.py's flags.  A kernel's text is its instructions and labels: comment and directive lines are dropped, and the
-number of the function inside its file is taken out of the local labels, so a kernel that moved to another file
-compares equal.  Per kernel the table says "identical", or gives both trees' VGPRs, SGPRs, LDS bytes, scratch bytes and
-instruction count from the assembly's metadata.  Needs hipcc, no GPU.
+Every measure source of a tree (csrc/measure.hip, region_*.hip, label_*.hip, nucleus.hip), with --all every source of the
+tree, is compiled to device-only assembly with _build.py's flags.  A kernel's text is its instructions and labels: comment and
+directive lines are dropped, and the number of the function inside its file is taken out of the local labels, so a kernel
+that moved to another file compares equal.  A kernel whose symbol changed with the name of a parameter's type is paired by
+its own name (with its template arguments), where one symbol of that name left and one came; several instantiations or
+overloads that change symbol together stay unpaired and are listed as "only in" one tree.  Per kernel the table says
+"identical", or gives both trees' VGPRs, SGPRs, LDS bytes, scratch bytes and instruction count from the assembly's metadata.
+Needs hipcc, no GPU.
 """
 
 import argparse
@@ -72,9 +75,9 @@ def kernels_of(text):
     return out
 
 
-def tree_kernels(tree, only):
+def tree_kernels(tree, only, every):
     build = load_build(tree)
-    names = [n for n in measure_sources(build) if not only or n in only]
+    names = [n for n in (build.sources() if every or only else measure_sources(build)) if not only or n in only]
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=8) as pool:
         texts = list(pool.map(lambda n: assembly(build, n, tmp), names))
     out = {}
@@ -103,9 +106,17 @@ def main():
     ap.add_argument("new")
     ap.add_argument("-o", "--output")
     ap.add_argument("--only", nargs="*", help="source files to compare (default: all measure sources)")
+    ap.add_argument("--all", action="store_true", help="compare every source of the trees")
     args = ap.parse_args()
-    old, new = tree_kernels(args.old, args.only), tree_kernels(args.new, args.only)
+    old, new = tree_kernels(args.old, args.only, args.all), tree_kernels(args.new, args.only, args.all)
     nice = demangle(sorted(set(old) | set(new)))
+    # a kernel whose parameter types were renamed has another symbol: it is paired by its name where that is unambiguous
+    gone, come = [s for s in old if s not in new], [s for s in new if s not in old]
+    for sym in come:
+        twins = [s for s in gone if nice[s] == nice[sym]]
+        if len(twins) == 1 and sum(nice[s] == nice[sym] for s in come) == 1:
+            name, body, meta = new.pop(sym)
+            new[twins[0]] = (name, [line.replace(sym, twins[0]) for line in body], meta)
     rows = ["# kernel [file old -> new]: identical | old / new vgpr sgpr lds scratch insts (waves per SIMD)"]
     differ = worse = 0
     for sym in sorted(set(old) | set(new), key=lambda s: nice[s]):
